@@ -10,6 +10,9 @@ stress case: --stacks 8 --res 384 --bs 16 --dtype fp16):
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, or plain -- bench.py then
                                                           starts its N ranks itself, self_launch())
 
+    python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed, DIR/<name>.npy: two builds
+                                                          run with the same arguments get the same inputs and can be compared array by array)
+
 Prints ONE JSON line on rank 0 (contract in the task description).  `roofline` comes from HIP events
 recorded around every launch of the MFMA kernels on the engine's own stream during a second pass of K
 steps right after the timed region (same inputs, same kernels; the events are kept out of the timed
@@ -35,6 +38,7 @@ PROF_NAMES = ['conv_fwd_1x1', 'conv_fwd_3x3', 'conv_dgrad_1x1', 'conv_dgrad_3x3'
               'stem_fwd_7x7', 'stem_wgrad_7x7', 'unused', 'conv_fwd_lowres', 'conv_dgrad_lowres', 'conv_wgrad_lowres']
 HBM_PEAK = 8.0e12          # B/s   (MI355X_MICROARCH.md)
 MFMA_PEAK = 2.5e15         # FLOP/s dense bf16
+DUMP_BYTES = (64 << 20) - (64 << 10)     # --dump-outputs: array bytes of all files together (64 KB left for the .npy headers)
 
 
 def cpu_model():
@@ -222,6 +226,31 @@ def design_floor(net, opt, B, res, h, frame_hw=(720, 1280)):
                     'median per-launch size (25-100 MB buffers untouched for 640 MB of traffic); floor_ms_at_large_rate = design bytes / 1.6 GB copy rate'}
 
 
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 (float64 stays float64).  Smallest first, each array gets an even
+    share of what is left of `budget`; one larger than its share is replaced by a fixed sample of its flattened elements (sorted
+    positions drawn by numpy's generator seeded with 0: the same positions in every run with the same arguments).
+    Returns {name: {'shape': written, 'full_shape': computed, 'sampled': bool}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    left, info = budget, {}
+    names = sorted(host, key=lambda k: (host[k].nbytes, k))
+    for i, name in enumerate(names):
+        a = full = host[name]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+        info[name] = {'shape': list(a.shape), 'full_shape': list(full.shape), 'sampled': a is not full}
+    return info
+
+
 def self_launch(n):
     """Start ranks 0..n-1 of this command (same argv) and wait for them: RANK / LOCAL_RANK / WORLD_SIZE in the environment,
     rendezvous through a file store (POSEADV_DIST_INIT=file://...), HSA_ENABLE_IPC_MODE_LEGACY=0 kept for RCCL's dmabuf IPC.
@@ -283,6 +312,9 @@ def main():
                     'by default they run at N = 1 when rocprofv3 is on PATH, and the recorded profiles/ numbers are quoted otherwise')
     ap.add_argument('--no-floor', action='store_true', help='skip the design-bytes / cold-rate floor of the roofline object')
     ap.add_argument('--keep-profiles', action='store_true', help='keep the child passes\' rocprofv3 output under gpurun_out/')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='rank 0 writes what the last timed step computed as DIR/<name>.npy (loss, pckh, pckh_origin_res, the per-stack heat maps, '
+                         'the updated parameters and BatchNorm buffers; a fixed, seeded sample of an array past the 64 MB budget)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -347,6 +379,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax[0])
     value = world * B * args.steps / dt
+    # the loss is a slot of the engine's 16-entry loss ring: read it (and the meters) now, before the passes below overwrite it
+    step_loss, step_pckh, step_pckh_o = float(loss), float(pckh), float(pckh_o)
+    # what the last timed step handed its caller (train_step's three device scalars, the heat maps of its forward pass, the weights and
+    # running statistics it left), read back before the passes below run more steps on the same net
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {'loss': loss, 'pckh': pckh, 'pckh_origin_res': pckh_o,
+                                                  'heatmaps': torch.stack(net.heatmaps(B)), 'params': net.flat_params,
+                                                  'buffers': net.flat_buffers})
     # who actually took part: a one per rank summed THROUGH the collective backend, and the distinct devices behind the ranks
     ranks_seen, devices_seen, backend = 1, 1, None
     if world > 1 or (dist.is_available() and dist.is_initialized()):
@@ -501,8 +542,10 @@ def main():
                                           ('BASELINE configs[4]: ' if (args.stacks, args.chan, res, B, args.dtype) == (8, 256, 384, 16, 'fp16') else ''), args.stacks, args.chan, B, res, res),
                            'global_batch': world * B, 'parallelism': 'dp%d' % world + ('+overlapped-exchange' if args.overlap and world > 1 else ''),
                            'ranks_seen': ranks_seen, 'devices_seen': devices_seen, 'collective_backend': backend,
-                           'loss': float(loss), 'pckh': float(pckh), 'pckh_origin_res': float(pckh_o)},
+                           'loss': step_loss, 'pckh': step_pckh, 'pckh_origin_res': step_pckh_o},
                 'pckh_parity': parity, 'roofline': roofline, 'cpu_baseline': cpu}
+        if dumped is not None:
+            line['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         print(json.dumps(line))
     if dist.is_available() and dist.is_initialized():          # (world > 1, or one rank forced through RCCL: POSEADV_FORCE_DIST=1)
         dist.barrier()

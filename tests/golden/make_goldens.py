@@ -298,10 +298,23 @@ def gen_nets(R):
     net.zero_grad(); asn.zero_grad()
     loss.backward()
     assert all(p.grad is None for p in net.parameters())               # features are detached (:161-162)
+    grad_digest = digest([p.grad for p in asn.parameters()])
+    # the same gradients in float64 (same fp32 weights and inputs, widened): several digest entries are exact zeros of the math (a conv
+    # bias in front of a training-mode BatchNorm, the class sum of a softmax head), which fp32 leaves as rounding noise of the host's
+    # reduction order; in float64 they sit at ~1e-14 on any CPU
+    net.double(); asn.double()
+    ls64, lr64 = net(img.double(), asn, is_half_hg=True, is_aug=True)
+    ps64, pr64 = torch.softmax(ls64, 1), torch.softmax(lr64, 1)
+    gs64 = R['util'].gen_groundtruth(ps64, idx_s, reg.double(), ag.double())
+    gr64 = R['util'].gen_groundtruth(pr64, idx_r, ag.double(), reg.double())
+    loss64 = F.kl_div(torch.log(ps64 + 1e-7), gs64, reduction='mean') * 7 + \
+        F.kl_div(torch.log(pr64 + 1e-7), gr64, reduction='mean') * 7
+    asn.zero_grad()
+    loss64.backward()
     np.savez_compressed(os.path.join(OUT, 'asn_c16.npz'), logits_s=ls.detach().numpy(), logits_r=lr.detach().numpy(),
                         idx_s=idx_s.numpy(), idx_r=idx_r.numpy(), reg=reg.numpy(), ag=ag.numpy(),
                         gs=gs.numpy(), gr=gr.numpy(), loss=np.array(float(loss)),
-                        grad_digest=digest([p.grad for p in asn.parameters()]),
+                        grad_digest=grad_digest, grad_digest_f64=digest([p.grad for p in asn.parameters()]),
                         nparams=np.array(sum(p.numel() for p in asn.parameters())))
     print('asn', float(loss))
     # full-size parameter counts: 6 570 784 / 2 577 934

@@ -71,7 +71,8 @@ def test_flat_gradient_allreduce_world4():
 
 def _main_worker(rank, world, init, exp_dir, out):
     """stack_hg.main() -- the REAL host control flow -- on 2 gloo ranks with the engine stubbed at the C ABI."""
-    set_env(rank, world, init)
+    # gloo named explicitly: the stub's tensors live on the CPU, and init_distributed picks nccl (RCCL) whenever a GPU is visible
+    set_env(rank, world, init, POSEADV_DIST_BACKEND='gloo')
     from tests import abi_stub
     fake = abi_stub.install(rank)
     orig_ar, orig_save = dist.all_reduce, torch.save

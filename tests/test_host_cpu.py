@@ -311,3 +311,27 @@ def test_bench_self_launch_propagates_a_failing_rank():
                        capture_output=True, text=True, timeout=240)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith('{')]
+
+
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: small arrays are written whole, an array past its share of the 64 MB budget becomes a sample at the same
+    positions in every run; float32 files (float64 kept), all files together within the budget."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    arrays = {'loss': torch.tensor(0.25), 'pckh': torch.tensor(0.5, dtype=torch.float64), 'heatmaps': torch.rand(2, 3, 16, 8, 8, generator=g),
+              'params': torch.rand(20_000_000, generator=g)}
+    info = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ('a', 'b')]
+    assert info[0] == info[1]
+    assert not info[0]['heatmaps']['sampled'] and info[0]['heatmaps']['shape'] == [2, 3, 16, 8, 8]
+    assert info[0]['params']['sampled'] and info[0]['params']['full_shape'] == [20_000_000]
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == ['heatmaps.npy', 'loss.npy', 'params.npy', 'pckh.npy']
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(str(tmp_path / 'a' / f)), np.load(str(tmp_path / 'b' / f))
+        assert a.dtype == (np.float64 if f == 'pckh.npy' else np.float32) and np.array_equal(a, b)
+    p = np.load(str(tmp_path / 'a' / 'params.npy'))
+    assert np.isin(p, arrays['params'].numpy()).all()
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'heatmaps.npy')), arrays['heatmaps'].numpy())
