@@ -361,13 +361,23 @@ int pa_conv2d_time(int mode, int variant, int B, int Cin, int Cout, int H, int W
  * the caller's stream (clean per-kernel timings: bench.py's roofline pass); on = 1 restores the default. */
 int pa_net_set_multi_stream(pa_net* net, int on);
 
-/* Test hook: copy an internal activation (pending BatchNorm+ReLU applied) or, with grad != 0, its raw
- * gradient buffer out as NCHW fp32; shape4 receives {B, C, H, W} (out may be NULL to query the shape).
+/* Test hook: copy one view of an internal activation out as NCHW fp32; shape4 receives {B, C, H, W} (out may be NULL to query the
+ * shape).  grad selects the view:
+ *   0  the value: the stored tensor with its pending BatchNorm+ReLU applied (in fp32, not rounded to the storage type);
+ *   1  the stored gradient buffer: dz = d(value) * [value > 0] for an activation with a pending BatchNorm, the plain gradient otherwise;
+ *   2  the raw stored tensor (BatchNorm not applied);
+ *   3  the gradient with respect to the raw tensor: kA * dz + kB * raw + kC (in fp32) for an activation with a pending BatchNorm,
+ *      the plain gradient otherwise;
+ *   4  (the inner tensors ".x2" and the outputs of residual blocks) the same gradient as the data-gradient kernel of the tensor's
+ *      consumer stored it, in the storage type, for the weight gradient and the shortcut addend (dz2 / dz3); an error when this step
+ *      did not store it (the consumer's kernel computed it on the fly) or for any other tensor.
+ * 1 and 3 return an error for a tensor without a gradient buffer; any other grad value is an error.  Every buffer the hook names keeps
+ * its value to the end of the step (the arena gives each tensor its own storage).
  * Names: "stem", "res1".."res3", "pool0", "hg<i>.skip<k>|pool<k>|down<k>|up<k>|merge<k>|neck" (k=1..4),
  * "post<i>", "lin<i>", "xin<i>", optional suffix ".x1"/".x2" for a block's inner tensors. */
 int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int* shape4);
 
-/* The same hook for the agent: "in<k>" (k = 0..4: residual_skip1-4, residual_neck), "pa<k>", "merge<k>"
+/* The same hook (and the same views) for the agent: "in<k>" (k = 0..4: residual_skip1-4, residual_neck), "pa<k>", "merge<k>"
  * (k = 0..3), "deep<k>" (k = 0..2), optional suffix ".x1"/".x2". */
 int pa_asn_debug_tensor(pa_net* net, const char* which, int grad, float* out, int* shape4);
 

@@ -730,18 +730,35 @@ int pa_net_set_multi_stream(pa_net* net, int on) {
     return 0;
 }
 
+// the views of an activation the debug hooks copy out (include/poseadv.h): 0 value (pending BatchNorm+ReLU applied), 1 stored gradient
+// (dz = masked gradient with a pending BatchNorm, the plain gradient otherwise), 2 raw stored tensor, 3 gradient with respect to the raw
+// tensor (kA * dz + kB * raw + kC with a pending BatchNorm: Net::gradop), 4 that gradient as the data-gradient kernel of its consumer
+// stored it for the later readers (Residual::dz3 / dz2; `mat` = nullptr when this step did not materialise it)
+static int debug_copy(Net& n, const Act& a, int grad, float* out, int* shape4, const char* who, const bf16* mat) {
+    if (grad < 0 || grad > 4) { pa_set_error_msg((std::string(who) + ": grad must be 0 .. 4").c_str()); return 1; }
+    if ((grad == 1 || grad == 3) && !a.grad) { pa_set_error_msg((std::string(who) + ": this tensor has no gradient buffer").c_str()); return 1; }
+    if (grad == 4 && !mat) { pa_set_error_msg((std::string(who) + ": no stored BatchNorm-backward gradient of this tensor in this step").c_str()); return 1; }
+    shape4[0] = a.B; shape4[1] = a.C; shape4[2] = a.H; shape4[3] = a.W;
+    if (!out) return 0;
+    const PaOperand src = grad == 0 ? n.op(a) : grad == 1 ? pa_plain(a.grad) : grad == 2 ? pa_plain(a.raw) : grad == 3 ? n.gradop(a) : pa_plain(mat);
+    TRY(pa_launch_nhwc_bf16_to_nchw_f32(src, out, a.B, a.C, a.H, a.W, n.st));
+    return 0;
+}
+
 // debug / test hook: copy an internal activation (BatchNorm+ReLU applied) or its gradient buffer out as
 // NCHW fp32.  which: "stem", "res1", "pool0", "res2", "res3", "hg<i>.skip<k>", "hg<i>.pool<k>",
 // "hg<i>.down<k>", "hg<i>.neck", "hg<i>.up<k>", "hg<i>.merge<k>", "post<i>", "lin<i>", "xin<i>" (k = 1..4)
 // and "<name>.x1"/".x2" for the inner tensors of a residual block; "hg<i>.maskedskip<k>", "hg<i>.maskedneck" (occlusion branch).
-// grad != 0 -> the raw gradient buffer.
+// grad: which view (debug_copy above).
 int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int* shape4) {
     Net& n = net->n;
     std::string w(which);
     const Act* a = nullptr;
+    const bf16* mat = nullptr;       // view 4: the block's stored dz2 / dz3
     auto pick_res = [&](Residual& r, const std::string& rest) -> const Act* {
         if (rest == ".x1") return &r.x1;
-        if (rest == ".x2") return &r.x2;
+        if (rest == ".x2") { mat = r.dz2_valid ? r.dz2 : nullptr; return &r.x2; }
+        mat = r.dz3_valid ? r.dz3 : nullptr;
         return &r.x3;
     };
     auto starts = [&](const char* p) { return w.rfind(p, 0) == 0; };
@@ -771,11 +788,7 @@ int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int
         }
     }
     if (!a) { pa_set_error_msg("pa_hg_debug_tensor: unknown tensor name"); return 1; }
-    shape4[0] = a->B; shape4[1] = a->C; shape4[2] = a->H; shape4[3] = a->W;
-    if (!out) return 0;
-    PaOperand src = grad ? pa_plain(a->grad) : n.op(*a);
-    TRY(pa_launch_nhwc_bf16_to_nchw_f32(src, out, a->B, a->C, a->H, a->W, n.st));
-    return 0;
+    return debug_copy(n, *a, grad, out, shape4, "pa_hg_debug_tensor", mat);
 }
 
 
@@ -785,9 +798,11 @@ int pa_asn_debug_tensor(pa_net* net, const char* which, int grad, float* out, in
     Net& n = net->n;
     std::string w(which);
     const Act* a = nullptr;
+    const bf16* mat = nullptr;
     auto pick = [&](Residual& r, const std::string& rest) -> const Act* {
         if (rest == ".x1") return &r.x1;
-        if (rest == ".x2") return &r.x2;
+        if (rest == ".x2") { mat = r.dz2_valid ? r.dz2 : nullptr; return &r.x2; }
+        mat = r.dz3_valid ? r.dz3 : nullptr;
         return &r.x3;
     };
     auto starts = [&](const char* p) { return w.rfind(p, 0) == 0; };
@@ -796,11 +811,7 @@ int pa_asn_debug_tensor(pa_net* net, const char* which, int grad, float* out, in
     else if (starts("merge")) a = pick(n.asn_merge[w[5] - '0'], w.substr(6));
     else if (starts("deep")) a = pick(n.asn_deep[w[4] - '0'], w.substr(5));
     if (!a) { pa_set_error_msg("pa_asn_debug_tensor: unknown tensor name"); return 1; }
-    shape4[0] = a->B; shape4[1] = a->C; shape4[2] = a->H; shape4[3] = a->W;
-    if (!out) return 0;
-    PaOperand src = grad ? pa_plain(a->grad) : n.op(*a);
-    TRY(pa_launch_nhwc_bf16_to_nchw_f32(src, out, a->B, a->C, a->H, a->W, n.st));
-    return 0;
+    return debug_copy(n, *a, grad, out, shape4, "pa_asn_debug_tensor", mat);
 }
 
 }  // extern "C"

@@ -735,7 +735,7 @@ int Residual::bwd_a(Net& n, const Act& in, const PaOperand* extra) {
     // weight gradient, on the weight-gradient stream, is launched behind it)
     TRY(n.finish_grad_or_defer(x2, (n.fin_mask & 2) && n.fin_consumer_ok(c2, B, H, W, true)));
     PaOperand g2 = n.gradop(x2);
-    bool dz2_valid = false;
+    dz2_valid = false;
     TRY(n.conv_dgrad(c2, g2, B, H, W, pa_none(), pa_none(), n.final_ep(x1), x1.grad, dz2, &dz2_valid, x2.bn));
     if (dz2_valid) g2 = pa_plain(dz2);
     TRY(n.conv_wgrad(c2, g2, n.op(x1), B, H, W));

@@ -1,0 +1,376 @@
+"""Exact checks of the code that links the convolutions: every BatchNorm (statistics, finalize, running estimates, parameter gradients,
+backward, eval mode), every max pool forward and every upsample-add (forward and backward) of the hourglass net, each recomputed in
+float64 from the tensors the engine itself stored after ONE training step (pa_hg_debug_tensor views 0-4, include/poseadv.h).
+
+What 'bn backward' covers: view 3 applies the finalize's kA / kB / kC to dz and raw in the hook's own fp32 load, so that check pins the
+backward finalize constants (kB, kC carry the backward sums; kA the forward's invstd).  The tensors the data-gradient kernels store for
+the later readers (dz2 / dz3 of every residual block that materialises them: weight gradients, shortcut addends) are view 4; 'stored
+bn backward' compares them bit for bit with view 3 rounded once to the storage type -- the kernels' own fmaf(kA, dz, fmaf(kB, x, kC)).
+Where a block's consumer computes that gradient on the fly instead (not stored), the kernel's operand load is covered only through
+the node tests (tests/test_gpu_local.py).
+
+tests/test_gpu_bn_exact.py runs the legs; for the IEEE-half build it runs this file as a child process (one storage type per process,
+like tests/fp16_check.py).  tests/test_bn_exact_cpu.py shows on synthetic tensors that the bounds exclude the defects they are for.
+
+Bounds.  Nothing here is fitted to observed errors: every bound is a first-order forward error analysis of the fp32 evaluation of the
+formula the engine implements (bn_fin.h pa_bn_fwd_consts / pa_bn_running / pa_bn_bwd_consts, the epilogues' sums of dz and
+dz * (x - mean) * invstd, bn_eval_kernel), with u = 2^-24 and these rules (class E below):
+  * an fp32 add / sub / mul / correctly rounded division of two quantities known to within e_a, e_b adds |a| e_b + |b| e_a + e_a e_b of
+    propagated error and u (|result| + propagated error) of rounding; fmaf rounds once;
+  * rsqrtf (v_rsq_f32) is within 1 ulp = 2u: its bound is the exact interval [rsqrt(t + e), rsqrt(t - e)] widened by 2u;
+  * a per-channel sum of n fp32 values computed by any tree in which no value passes through more than D additions is within
+    D u sum|x_i| of the exact sum.  D (sum_depth) is derived from the kernels of the release build, in two parts:
+      - inside one partial row: a conv epilogue's row covers at most 128 pixels (the 1 x 1 / 3 x 3 tile kernels and the implicit-GEMM
+        kernels write 64- or 128-pixel rows, the fused upsample-add epilogue 16 low-resolution pixels; the three-tile 384-pixel 3 x 3
+        workgroups are not compiled in), and any tree over P values is at most P - 1 deep: <= 127.  A streaming kernel (max-pool /
+        upsample-add backward, ep_apply) keeps one channel group per thread: a chain over its items (<= ceil(n C / (8 * 65536)) + 4
+        pixels: <= 512 workgroups of >= 128 threads), at most 6 shuffle levels and a chain over <= 16 waves;
+      - the finalize over R partial rows: the launch form chains ceil(R / 64) rows per slice, then two 16-wide levels (+ 20); the
+        consumer-prologue form (R <= 128) is 8 + 4 deep.  R is at most the statistics capacity max(512, ceil(n / 64)), four times
+        that for the backward rows of bn3 in the up blocks (Residual::b3_rows_scale).
+  * the backward sum of dz * xhat is written in two forms: per term dz * (x - mean) * invstd (epilogue8, Bwd8, pa_conv_epilogue),
+    or per partial row invstd * (sum dz x - mean sum dz) (pa_conv_epilogue_lds_bwd, pa_conv_epilogue_lds_up), which cancels when
+    |mean| >> sigma.  The bound covers both: the rounding terms are taken over |dz| (|x - mean| + 2 |mean|), which bounds
+    |dz x| + |mean dz| as well as |dz (x - mean)|.
+  * a bound that has lost its meaning (the interval of invstd wider than 1 %: at these depths a channel whose |mean| / sigma exceeds
+    about 10) is reported as a failure of its own ('degenerate bound') instead of passing every check of that BatchNorm.
+The parameters, running estimates and stored tensors are fp32 / storage-type values, exact in float64.  Gradient quantities are compared
+in the engine's own units (the fp16 build carries pa_grad_scale() in every gradient: all checks are homogeneous in it).
+
+Pool forward, merge forward and merge backward involve no accumulation: one fp32 max / add / 2 x 2 sum in a fixed order, rounded once to
+the storage type (round to nearest even, the conversion of gfx950 and of torch), so they are compared bit for bit."""
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+U = 2.0 ** -24
+EPS, MOMENTUM = 1e-5, 0.1
+_F32 = lambda v: float(np.float32(v))
+# the fp32 constants the engine uses for eps, momentum and 1 - momentum, as (value, distance from the exact constant)
+EPS32 = (EPS, abs(_F32(EPS) - EPS))
+MOM32 = (MOMENTUM, abs(_F32(MOMENTUM) - MOMENTUM))
+ONE_MINUS_MOM32 = (1.0 - MOMENTUM, abs(_F32(np.float32(1.0) - np.float32(MOMENTUM)) - (1.0 - MOMENTUM)))
+
+
+def sum_depth(n, C, rows_scale=1):
+    """D: the most additions any value passes through in a per-channel sum over n pixels of C channels (module docstring)."""
+    stream = -(-n * C // (8 * 65536)) + 4 + 6 + 16
+    rows = rows_scale * max(512, -(-n // 64))
+    return max(127, stream) + -(-rows // 64) + 20
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# first-order error propagation of an fp32 evaluation: E(v, e) = the exact value v (float64) and a bound e on |fp32 result - v|
+class E(object):
+    def __init__(self, v, e=None):
+        self.v = v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
+        self.e = torch.zeros_like(self.v) if e is None else (e if torch.is_tensor(e) else torch.full_like(self.v, float(e)))
+
+    @staticmethod
+    def _r(v, e):
+        return E(v, e + U * (v.abs() + e))
+
+    def __add__(self, o):
+        return E._r(self.v + o.v, self.e + o.e)
+
+    def __sub__(self, o):
+        return E._r(self.v - o.v, self.e + o.e)
+
+    def __mul__(self, o):
+        return E._r(self.v * o.v, self.v.abs() * o.e + o.v.abs() * self.e + self.e * o.e)
+
+    def __truediv__(self, n):           # by an exact positive count
+        return E._r(self.v / n, self.e / n)
+
+    def __neg__(self):
+        return E(-self.v, self.e)
+
+    def rsqrt(self):
+        lo = (self.v + self.e).rsqrt()
+        hi = (self.v - self.e).clamp_min(1e-300).rsqrt()
+        v = self.v.rsqrt()
+        return E(v, torch.maximum(v - lo, hi - v) + 2 * U * hi)
+
+
+def fma(a, x, b):
+    """fmaf(a, x, b) with x exact (a tensor): one rounding."""
+    v = a.v * x + b.v
+    return E._r(v, a.e * x.abs() + b.e)
+
+
+def _chan(t):
+    return t.sum(dim=(0, 2, 3))
+
+
+def _bc(t):
+    return t.view(1, -1, 1, 1)
+
+
+DEGENERATE = 1e-2       # relative width of the invstd interval beyond which a bound says nothing
+
+
+def fwd_consts(raw, gamma, beta, rows_scale=1, chan=None):
+    """Reference statistics of raw (NCHW float64) and the engine's BatchNorm constants (pa_bn_fwd_consts) with their bounds.
+    rows_scale: capacity factor of the BatchNorm's BACKWARD partial rows (4 for bn3 of the up blocks); chan: the layer's channel count
+    for sum_depth when raw holds only some of its channels (tests/test_bn_exact_cpu.py)."""
+    n = raw.shape[0] * raw.shape[2] * raw.shape[3]
+    chan = chan or raw.shape[1]
+    D = sum_depth(n, chan, 1)
+    S1 = E(_chan(raw), D * U * _chan(raw.abs()))
+    S2 = E(_chan(raw * raw), D * U * _chan(raw * raw))
+    mu = S1 / n
+    var = S2 / n - mu * mu
+    mu_ref = _chan(raw) / n
+    var_ref = _chan((raw - _bc(mu_ref)) ** 2) / n                    # two-pass in float64: the reference's biased variance
+    var = E(var_ref, var.e)
+    inv = (var + E(*EPS32)).rsqrt()
+    scale = E(gamma) * inv
+    shift = E(beta) - mu * scale
+    return dict(n=n, mu=mu, var=var, inv=inv, scale=scale, shift=shift, S1=S1, S2=S2, Db=sum_depth(n, chan, rows_scale),
+                degenerate=float((inv.e / inv.v).max()))
+
+
+def _ratio(got, ref, bound):
+    d = (got.double() - ref).abs()
+    return float((d / bound.clamp_min(1e-300)).max())
+
+
+def check_forward(raw, val, k):
+    """val (view 0) = relu(gamma (raw - mean) / sqrt(var + eps) + beta) per element."""
+    pre = fma(_bc_e(k['scale']), raw, _bc_e(k['shift']))
+    return _ratio(val, pre.v.clamp_min(0), pre.e)
+
+
+def _bc_e(a):
+    return E(_bc(a.v), _bc(a.e))
+
+
+def check_running(k, rm0, rv0, rm1, rv1):
+    """running_mean / running_var after the step: momentum 0.1, UNBIASED variance (pa_bn_running)."""
+    n = k['n']
+    unb = k['var'] * E(torch.full_like(k['var'].v, float(n))) / (n - 1)
+    em = E(*ONE_MINUS_MOM32) * E(rm0.double()) + E(*MOM32) * k['mu']
+    ev = E(*ONE_MINUS_MOM32) * E(rv0.double()) + E(*MOM32) * unb
+    return max(_ratio(rm1, em.v, em.e), _ratio(rv1, ev.v, ev.e))
+
+
+def bwd_sums(raw, dz, k):
+    """sum dz and sum dz * xhat (reference, float64) with the bounds of the engine's fp32 sums of dz and dz * (x - mean) * invstd."""
+    D = k['Db']
+    mu, inv = _bc_e(k['mu']), _bc_e(k['inv'])
+    xc = raw - mu.v
+    T1 = E(_chan(dz), D * U * _chan(dz.abs()))
+    # |(x - mean_e) invstd_e - (x - mean) invstd| <= e_mu (inv + e_inv) + |x - mean| e_inv; then the roundings of either form: three per
+    # term or per row (products, the row's subtraction and scaling) and D in the sums, all on values <= |dz| (|x - mean| + 2 |mean| + e_mu)
+    adz = dz.abs()
+    e2 = _chan(adz * (mu.e * (inv.v + inv.e) + xc.abs() * inv.e)) + \
+        (D + 3) * U * _chan(adz * (xc.abs() + 2 * mu.v.abs() + mu.e) * (inv.v + inv.e))
+    T2 = E(_chan(dz * xc * inv.v), e2)
+    return T1, T2
+
+
+def check_param_grads(T1, T2, dgamma, dbeta):
+    return max(_ratio(dbeta, T1.v, T1.e), _ratio(dgamma, T2.v, T2.e))
+
+
+def check_backward(raw, dz, dx, k, T1, T2):
+    """dx (view 3) = gamma invstd (dz - mean(dz) - xhat mean(dz xhat)) per element (pa_bn_bwd_consts, then fmaf(kA, dz, fmaf(kB, x, kC)))."""
+    n = k['n']
+    s, inv, mu = k['scale'], k['inv'], k['mu']
+    b = (-s * inv * T2) / n
+    kC = (-s * T1) / n - b * mu
+    inner = fma(_bc_e(b), raw, _bc_e(kC))
+    out = fma(_bc_e(s), dz, inner)
+    xhat = (raw - _bc(mu.v)) * _bc(inv.v)
+    ref = _bc(s.v) * (dz - _bc(T1.v / n) - xhat * _bc(T2.v / n))
+    return _ratio(dx, ref, out.e)
+
+
+def check_eval(raw, val, gamma, beta, rm, rv):
+    """eval mode: relu(gamma (raw - running_mean) / sqrt(running_var + eps) + beta) (bn_eval_kernel, then the BNRELU load)."""
+    s = E(gamma.double()) * (E(rv.double()) + E(*EPS32)).rsqrt()
+    sh = E(beta.double()) - E(rm.double()) * s
+    pre = fma(_bc_e(s), raw, _bc_e(sh))
+    ref = (_bc(gamma.double()) * (raw - _bc(rm.double())) / _bc((rv.double() + EPS).sqrt()) + _bc(beta.double())).clamp_min(0)
+    return _ratio(val, ref, pre.e)
+
+
+# ---- bit-exact checks: the number of elements that differ
+def _mismatch(got, exp):
+    return int((got != exp).sum())
+
+
+def rnd(x, dtype):
+    return x.to(dtype).float()
+
+
+def check_pool(val_in, pooled, dtype):
+    """pooled = the 2 x 2 maximum of the (BatchNorm+ReLU-applied, fp32) input, rounded once to the storage type."""
+    return _mismatch(pooled, rnd(F.max_pool2d(val_in.float(), 2, 2), dtype))
+
+
+def up2(x):
+    return x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+
+
+def check_merge_fwd(val_up, val_skip, merged, dtype):
+    """merged = round(up2(up) + skip), the sum in fp32."""
+    return _mismatch(merged, rnd(up2(val_up.float()) + val_skip.float(), dtype))
+
+
+def sum2x2(d):
+    """((top-left + top-right) + bottom-left) + bottom-right in fp32 (the fused epilogue's and the streaming kernels' order)."""
+    d = d.float()
+    return ((d[:, :, 0::2, 0::2] + d[:, :, 0::2, 1::2]) + d[:, :, 1::2, 0::2]) + d[:, :, 1::2, 1::2]
+
+
+def check_merge_bwd(dmerged, val_up, val_skip, dup, dskip, dtype):
+    """d up = round(2 x 2 sum of d merged) masked by up > 0; d skip = d merged masked by skip > 0."""
+    e_up = rnd(sum2x2(dmerged), dtype) * (val_up > 0).float()
+    e_sk = dmerged.float() * (val_skip > 0).float()
+    return _mismatch(dup, e_up) + _mismatch(dskip, e_sk)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the legs (GPU)
+def bn_sites(stacks):
+    """(parameter prefix of the BatchNorm, debug-hook name of the tensor it normalises) for every BatchNorm of the pose net."""
+    blocks = [('residual1.', 'res1'), ('residual2.', 'res2'), ('residual3.', 'res3')]
+    for i in range(stacks):
+        for k in (1, 2, 3, 4):
+            for kind in ('skip', 'down', 'up'):
+                blocks.append(('hg.%d.%s%d.0.' % (i, kind, k), 'hg%d.%s%d' % (i, kind, k)))
+        blocks.append(('hg.%d.neck.0.' % i, 'hg%d.neck' % i))
+        blocks.append(('post_res.%d.0.' % i, 'post%d' % i))
+    sites = [('bn1', 'stem')]
+    for p, t in blocks:
+        sites += [(p + 'bn1', t + '.x1'), (p + 'bn2', t + '.x2'), (p + 'bn3', t)]
+    return sites + [('linear.%d.1' % i, 'lin%d' % i) for i in range(stacks)]
+
+
+def pool_sites(stacks):
+    """(pool output, its input) for pool0 and every hourglass pool."""
+    s = [('pool0', 'res1')]
+    for i in range(stacks):
+        s += [('hg%d.pool%d' % (i, k), 'xin%d' % i if k == 1 else 'hg%d.down%d' % (i, k - 1)) for k in (1, 2, 3, 4)]
+    return s
+
+
+# Names whose buffers do not hold their value at the end of the step (arena reuse) and are therefore not checked: none -- every
+# activation and gradient the hook names has storage of its own (Net::new_act).  A name added here needs its reason next to it.
+NOT_HELD = {}
+
+
+class Probe(object):
+    def __init__(self, net):
+        import ctypes
+        from pose_adv_aug_amd._lib import lib, check, ptr
+        self.C, self.lib, self.check, self.ptr = ctypes, lib(), check, ptr
+        self.h = net._net(net._last_B)
+
+    def has(self, name, view):
+        shp = (self.C.c_int * 4)()
+        return self.lib.pa_hg_debug_tensor(self.h, name.encode(), view, None, shp) == 0
+
+    def get(self, name, view):
+        assert name not in NOT_HELD, name
+        shp = (self.C.c_int * 4)()
+        self.check(self.lib.pa_hg_debug_tensor(self.h, name.encode(), view, None, shp))
+        out = torch.empty(tuple(shp), device='cuda')
+        self.check(self.lib.pa_hg_debug_tensor(self.h, name.encode(), view, self.ptr(out), shp))
+        return out
+
+
+KINDS = ('bn forward', 'running stats', 'beta/gamma grads', 'bn backward', 'stored bn backward', 'eval forward', 'pool forward',
+         'merge forward', 'merge backward', 'degenerate bound')
+
+
+def run_leg(stacks, chan, B, res, seed, log=print, stored_expected=('.x2', '')):
+    """One training step (loss_and_backward, default multi-stream mode, as bench.py runs it), then every check.  Returns
+    {kind: worst error / bound (bit-exact kinds: differing elements)} and the list of failures.  stored_expected: the inner tensors
+    ('.x2': dz2) and block outputs ('': dz3) of which at least one block must have stored its BatchNorm-backward gradient."""
+    from pose_adv_aug_amd._lib import act_dtype
+    from tests import inputs
+    from tests.test_gpu_net import t, _hg_pair
+    dtype = act_dtype()
+    torch.cuda.set_device(0)
+    ref, net = _hg_pair(stacks, chan, B, res, seed=seed)
+    del ref
+    sites = bn_sites(stacks)
+    sd = net.state_dict()
+    assert sorted(p for p, _ in sites) == sorted(k[:-len('.running_mean')] for k in sd if k.endswith('.running_mean')), \
+        'bn_sites must name every BatchNorm of the net'
+    before = {k: v.clone() for k, v in sd.items() if k.endswith('running_mean') or k.endswith('running_var')}
+    img = t(inputs.images(seed + 100, B, res)).cuda()
+    pts = t(inputs.heat_pts(seed + 101, B, res=res // 4)).cuda()
+    net.train()
+    net.loss_and_backward(img, pts)
+    torch.cuda.synchronize()
+    grads = {n: g.clone() for n, g in net.named_grads()}
+    sd = net.state_dict()
+    P = Probe(net)
+    worst = dict((k, 0.0) for k in KINDS)
+    fails = []
+
+    def note(kind, what, r, bit=False):
+        worst[kind] = max(worst[kind], r)
+        if (r != 0) if bit else not (r <= 1.0):          # ('degenerate bound': width / DEGENERATE, the same rule)
+            fails.append((kind, what, r))
+
+    stored = {'.x2': 0, '': 0}
+    for pre, name in sites:
+        raw = P.get(name, 2).double()
+        gamma, beta = sd[pre + '.weight'].double(), sd[pre + '.bias'].double()
+        up_bn3 = '.up' in name and not name.endswith(('.x1', '.x2'))
+        k = fwd_consts(raw, gamma, beta, rows_scale=4 if up_bn3 else 1)
+        note('degenerate bound', pre, k['degenerate'] / DEGENERATE)
+        note('bn forward', name, check_forward(raw, P.get(name, 0), k))
+        note('running stats', pre, check_running(k, before[pre + '.running_mean'], before[pre + '.running_var'],
+                                                sd[pre + '.running_mean'], sd[pre + '.running_var']))
+        dz = P.get(name, 1).double()
+        T1, T2 = bwd_sums(raw, dz, k)
+        note('beta/gamma grads', pre, check_param_grads(T1, T2, grads[pre + '.weight'], grads[pre + '.bias']))
+        dx = P.get(name, 3)
+        note('bn backward', name, check_backward(raw, dz, dx, k, T1, T2))
+        if P.has(name, 4):
+            stored['.x2' if name.endswith('.x2') else ''] += 1
+            note('stored bn backward', name, _mismatch(P.get(name, 4), rnd(dx, dtype)), bit=True)
+        del raw, dz, dx, k, T1, T2
+    # (a leg that expects a kind must have met it: the check must not go quiet because the kernels stopped storing)
+    for suf, cnt in stored.items():
+        if cnt == 0 and suf in stored_expected:
+            fails.append(('stored bn backward', 'no block stored its dz%s' % ('2' if suf else '3'), 0))
+    for out, src in pool_sites(stacks):
+        note('pool forward', out, check_pool(P.get(src, 0), P.get(out, 0), dtype), bit=True)
+    for i in range(stacks):
+        for k in (1, 2, 3, 4):
+            m, up, sk = 'hg%d.merge%d' % (i, k), 'hg%d.up%d' % (i, k), 'hg%d.skip%d' % (i, k)
+            vu, vs = P.get(up, 0), P.get(sk, 0)
+            note('merge forward', m, check_merge_fwd(vu, vs, P.get(m, 0), dtype), bit=True)
+            note('merge backward', m, check_merge_bwd(P.get(m, 1), vu, vs, P.get(up, 1), P.get(sk, 1), dtype), bit=True)
+    # eval mode: a forward pass with the running estimates this step left
+    net.eval()
+    net(img)
+    torch.cuda.synchronize()
+    for pre, name in sites:
+        note('eval forward', name, check_eval(P.get(name, 2).double(), P.get(name, 0), sd[pre + '.weight'], sd[pre + '.bias'],
+                                              sd[pre + '.running_mean'], sd[pre + '.running_var']))
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        log('bn_exact %s stacks %d chan %d B %d res %d: worst error / bound (bit-exact kinds: differing elements): %s'
+            % (torch.float16 if dtype == torch.float16 else 'bf16', stacks, chan, B, res,
+               ', '.join('%s %.3g' % (k, worst[k]) for k in KINDS)) + '; stored dz2 / dz3 checked in %d / %d blocks'
+            % (stored['.x2'], stored['']))
+    return worst, fails
+
+
+if __name__ == '__main__':          # the fp16 leg: tests/test_gpu_bn_exact.py runs this with POSEADV_DTYPE=fp16
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from pose_adv_aug_amd._lib import lib as _l
+    assert _l().pa_dtype() == 1, 'run with POSEADV_DTYPE=fp16'
+    worst, fails = run_leg(*[int(a) for a in sys.argv[1:6]], log=lambda s: print(s, flush=True))
+    print('FAILURES %d %s' % (len(fails), fails[:20]))
+    print('FP16 BN EXACT ' + ('PASSED' if not fails else 'FAILED'), flush=True)
+    sys.exit(1 if fails else 0)
