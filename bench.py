@@ -13,6 +13,12 @@ stress case: --stacks 8 --res 384 --bs 16 --dtype fp16):
     python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed, DIR/<name>.npy: two builds
                                                           run with the same arguments get the same inputs and can be compared array by array)
 
+    python bench.py ... --full                           (also everything beyond the headline figure, after the timed region: the
+                                                          median pass, roofline, PCKh parity against the oracle, CPU baseline)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: `ms_per_step_median`, `pckh_parity`,
+`roofline` and `cpu_baseline` are null there and filled in by --full (each of the last three can still be left out with its --no-* option).
+
 Prints ONE JSON line on rank 0 (contract in the task description).  `roofline` comes from HIP events
 recorded around every launch of the MFMA kernels on the engine's own stream during a second pass of K
 steps right after the timed region (same inputs, same kernels; the events are kept out of the timed
@@ -305,11 +311,13 @@ def main():
     ap.add_argument('--fin-rows', type=int, default=-1, help='>= 0: pa_net_set_fin_prologue(rows) -- row limit of the BatchNorm finalize in the consumer\'s prologue, 0 = every finalize a launch (A/B; default: the library\'s 128)')
     ap.add_argument('--graph', type=int, default=0, help='1: forward + backward replayed from a captured HIP graph (pa_hg_train_step)')
     ap.add_argument('--single-stream', type=int, default=0, help='1: the engine\'s side / weight-gradient streams off for the timed region too (experiments)')
+    ap.add_argument('--full', action='store_true', help='after the timed region, also run the median pass, roofline, PCKh parity and CPU baseline '
+                    '(a plain run only sets up, warms up, times the steps, writes --dump-outputs and prints the line)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-parity', action='store_true')
     ap.add_argument('--no-traffic', action='store_true', help='do not start the rocprofv3 child passes (PMC HBM traffic, kernel trace) of this command; '
-                    'by default they run at N = 1 when rocprofv3 is on PATH, and the recorded profiles/ numbers are quoted otherwise')
+                    'with --full they run at N = 1 when rocprofv3 is on PATH, and the recorded profiles/ numbers are quoted otherwise')
     ap.add_argument('--no-floor', action='store_true', help='skip the design-bytes / cold-rate floor of the roofline object')
     ap.add_argument('--keep-profiles', action='store_true', help='keep the child passes\' rocprofv3 output under gpurun_out/')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -401,7 +409,7 @@ def main():
     # median of per-step event intervals, in a pass of its own: an event record between two kernels of a queue
     # costs that queue a bubble, so it stays out of the timed region that `value` comes from
     median_ms = None
-    if os.environ.get('PA_BENCH_CHILD') != '1':          # (not inside the rocprofv3 child passes: their step counts are fixed)
+    if args.full and os.environ.get('PA_BENCH_CHILD') != '1':          # (not inside the rocprofv3 child passes: their step counts are fixed)
         nm = min(args.steps, 50)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(nm + 1)]
         evs[0].record()
@@ -411,7 +419,7 @@ def main():
         median_ms = per_step[nm // 2]
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         h = net._net(B)
         # per-kernel durations are taken with the engine's side streams off: with them on, launches of independent
         # branches overlap and a launch's event interval contains other kernels' work
@@ -524,11 +532,11 @@ def main():
                                    if (args.stacks, args.chan, res) == (2, 256, 256) else None)}
 
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         parity = pckh_parity(net, aug, batches[0], B, res)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.stacks, args.chan, B, res)
 
     if rank == 0:

@@ -192,7 +192,7 @@ def test_bench_line_from_two_ranks(overlap):
         env.pop(k, None)
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                         '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline', '--overlap', str(overlap)], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+                        '--full', '--no-cpu-baseline', '--overlap', str(overlap)], cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]                      # rank 0 alone prints

@@ -2,7 +2,7 @@
 parsers tools/pmc_to_json.py / tools/prof_pmc.sh share with it.
 
   traffic : two `rocprofv3 --pmc <C> --kernel-trace` passes (C = FETCH_SIZE, WRITE_SIZE -- separate passes, never combined with
-            sys / runtime / hip / hsa traces) of `python bench.py --steps 3 --warmup 1 ...` (4 steps + the 3 steps of its roofline leg, whose
+            sys / runtime / hip / hsa traces) of `python bench.py --steps 3 --warmup 1 --full ...` (4 steps + the 3 steps of its roofline leg, whose
             launches are matched with the engine's class sequence).  Counter unit:
             KiB as reported; FETCH_SIZE x2 (gfx950 tallies a wide coalesced 128-byte request at 64 bytes,
             /opt/skills/guides/MI355X_MICROARCH.md section HBM).
@@ -150,7 +150,7 @@ def measure_traffic(bench_args, timeout=120, keep=False):
             out = os.path.join(d, C)
             # 1 warm-up + 3 timed steps, then the roofline leg's 3 steps (single stream, class sequence recorded): 7 steps of the same work
             cmd = ['rocprofv3', '--pmc', C, '--kernel-trace', '--output-format', 'csv', '-d', out, '-o', 'bench', '--', sys.executable,
-                   os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-parity', '--no-traffic',
+                   os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-parity', '--no-traffic',
                    '--no-floor'] + list(bench_args)
             r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), PA_BENCH_SEQ_OUT=seq), capture_output=True, text=True, timeout=timeout)
             f = glob.glob(os.path.join(out, '**', '*counter_collection.csv'), recursive=True)
@@ -175,7 +175,7 @@ def measure_trace(bench_args, steps=5, timeout=120, keep=False):
     try:
         seq = os.path.join(d, 'seq.json')
         cmd = ['rocprofv3', '--kernel-trace', '--output-format', 'csv', 'rocpd', '-d', os.path.join(d, 'trace'), '-o', 'bench', '--', sys.executable,
-               os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', '2', '--no-cpu-baseline', '--no-parity', '--no-traffic', '--no-floor'] + list(bench_args)
+               os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', '2', '--full', '--no-cpu-baseline', '--no-parity', '--no-traffic', '--no-floor'] + list(bench_args)
         r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), PA_BENCH_SEQ_OUT=seq), capture_output=True, text=True, timeout=timeout)
         db = glob.glob(os.path.join(d, 'trace', '**', '*results.db'), recursive=True)
         if r.returncode != 0 or not db or not os.path.isfile(seq):

@@ -1,18 +1,19 @@
 #!/bin/bash
-# MFMA-busy per kernel over the bench step (PMC pass of its own, kernel-trace only); run via gpurun
+# MFMA-busy per kernel over the bench step (PMC pass of its own, kernel-trace only); output under $PROF_OUT (default prof_out/)
 TAG=${1:-r1}
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 export PA_BENCH_CHILD=1      # bench.py: no nested rocprofv3 child passes, no median pass (fixed step counts)
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d gpurun_out/mfma_$TAG -o bench -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-parity > gpurun_out/mfma_$TAG.log 2>&1
-tail -1 gpurun_out/mfma_$TAG.log | cut -c1-120
-python - $TAG > gpurun_out/mfma_summary_$TAG.txt <<'PY'
-import csv, sys, glob, collections
-tag = sys.argv[1]
-f = glob.glob('gpurun_out/mfma_%s/*counter_collection.csv' % tag)
-t = glob.glob('gpurun_out/mfma_%s/*kernel_trace.csv' % tag)
+export PROF_OUT=${PROF_OUT:-prof_out}; OUT=$PROF_OUT; mkdir -p $OUT
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/mfma_$TAG -o bench -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-parity > $OUT/mfma_$TAG.log 2>&1
+tail -1 $OUT/mfma_$TAG.log | cut -c1-120
+python - $TAG > $OUT/mfma_summary_$TAG.txt <<'PY'
+import csv, sys, glob, collections, os
+tag, out = sys.argv[1], os.environ['PROF_OUT']
+f = glob.glob('%s/mfma_%s/*counter_collection.csv' % (out, tag))
+t = glob.glob('%s/mfma_%s/*kernel_trace.csv' % (out, tag))
 if not f or not t:
-    print('no counter file', glob.glob('gpurun_out/mfma_%s/*' % tag)); sys.exit(0)
+    print('no counter file', glob.glob('%s/mfma_%s/*' % (out, tag))); sys.exit(0)
 dur = {}
 for r in csv.DictReader(open(t[0])):
     dur[r['Dispatch_Id']] = (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-9
@@ -39,4 +40,4 @@ for sec, k, b, i2, n, us, ins in rows[:40]:
     print('%9.1f %9.1f %9.1f %9.1f %12.0f  %s' % (b, i2, n, us, ins, k))
 print('# all kernels together: MFMA busy %.1f %% of the kernel time (%.2f ms/step serialised)' % (100 * tb / (SIMDS * ts * CLK), 1e3 * ts / 4))
 PY
-head -30 gpurun_out/mfma_summary_$TAG.txt
+head -30 $OUT/mfma_summary_$TAG.txt

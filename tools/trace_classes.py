@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-class kernel durations from a rocprofv3 --kernel-trace of bench.py (trace-grade twin of bench.py's event numbers).
 
-    PA_BENCH_SEQ_OUT=seq.json rocprofv3 --kernel-trace --stats -d out -o r -- python bench.py --steps K ...
+    PA_BENCH_SEQ_OUT=seq.json rocprofv3 --kernel-trace --stats -d out -o r -- python bench.py --steps K --full ...
     python tools/trace_classes.py out/r_results.db seq.json profiles/round2_trace_classes.json
 
 bench.py's roofline pass runs K steps single-stream and the engine records the class of every MFMA-kernel launch in launch
