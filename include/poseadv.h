@@ -374,7 +374,11 @@ int pa_net_set_multi_stream(pa_net* net, int on);
  * 1 and 3 return an error for a tensor without a gradient buffer; any other grad value is an error.  Every buffer the hook names keeps
  * its value to the end of the step (the arena gives each tensor its own storage).
  * Names: "stem", "res1".."res3", "pool0", "hg<i>.skip<k>|pool<k>|down<k>|up<k>|merge<k>|neck" (k=1..4),
- * "post<i>", "lin<i>", "xin<i>", optional suffix ".x1"/".x2" for a block's inner tensors. */
+ * "post<i>", "lin<i>", "xin<i>", optional suffix ".x1"/".x2" for a block's inner tensors; "heat<i>" (the heat maps as stored for
+ * in_conv, 64 channels of which 16..63 are zero; its gradient: d heat as stored for out_conv's weight gradient), "heat<i>.in"
+ * (in_conv's data gradient, 64 channels, no gradient) and "forth<i>" (forth_conv's stored output forth_conv(lin) + xin, no gradient)
+ * for the head layers between stacks i and i + 1; "hg<i>.poolgrad<k>" (no gradient): the gradient max pool k routes back to its
+ * input, plus for k = 1 the gradient reaching the hourglass input from the next stack, as skip k's conv1 data gradient adds it. */
 int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int* shape4);
 
 /* The same hook (and the same views) for the agent: "in<k>" (k = 0..4: residual_skip1-4, residual_neck), "pa<k>", "merge<k>"

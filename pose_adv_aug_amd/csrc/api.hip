@@ -748,7 +748,11 @@ static int debug_copy(Net& n, const Act& a, int grad, float* out, int* shape4, c
 // debug / test hook: copy an internal activation (BatchNorm+ReLU applied) or its gradient buffer out as
 // NCHW fp32.  which: "stem", "res1", "pool0", "res2", "res3", "hg<i>.skip<k>", "hg<i>.pool<k>",
 // "hg<i>.down<k>", "hg<i>.neck", "hg<i>.up<k>", "hg<i>.merge<k>", "post<i>", "lin<i>", "xin<i>" (k = 1..4)
-// and "<name>.x1"/".x2" for the inner tensors of a residual block; "hg<i>.maskedskip<k>", "hg<i>.maskedneck" (occlusion branch).
+// and "<name>.x1"/".x2" for the inner tensors of a residual block; "hg<i>.maskedskip<k>", "hg<i>.maskedneck" (occlusion branch);
+// "heat<i>": the heat maps in the storage type as in_conv reads them (64 channels, 16..63 zero), gradient: d heat as out_conv's
+// weight gradient reads it; "heat<i>.in": in_conv's data gradient (its part of d heat); "forth<i>": forth_conv's output
+// (forth_conv(lin) + xin), in_conv's addend; "hg<i>.poolgrad<k>": the gradient pool k routes back to its input (plus, k = 1, the
+// gradient reaching the hourglass input from outside), the second addend of skip k's conv1 data gradient.
 // grad: which view (debug_copy above).
 int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int* shape4) {
     Net& n = net->n;
@@ -762,7 +766,19 @@ int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int
         return &r.x3;
     };
     auto starts = [&](const char* p) { return w.rfind(p, 0) == 0; };
-    if (starts("stem")) a = &n.a0;
+    Act head;                        // buffers that are no activation of their own: "heat<i>", "heat<i>.in", "forth<i>", "hg<i>.poolgrad<k>"
+    head.B = n.B; head.H = head.W = n.res / 4;
+    if (starts("heat")) {
+        const bool in = w.size() == 8 && w.compare(5, 3, ".in") == 0;
+        const int i = (w.size() == 5 || in) ? w[4] - '0' : -1;
+        if (i >= 0 && i < (int)n.heat64.size() && n.heat64[i]) {
+            if (in) { if (i < (int)n.forth_tmp.size() && n.forth_tmp[i]) { head.raw = n.dheat_in[i]; head.C = 64; a = &head; } }
+            else { head.raw = n.heat64[i]; head.grad = n.dheat64[i]; head.C = 64; a = &head; }
+        }
+    } else if (starts("forth")) {
+        const int i = w.size() == 6 ? w[5] - '0' : -1;
+        if (i >= 0 && i < (int)n.forth_tmp.size() && n.forth_tmp[i]) { head.raw = n.forth_tmp[i]; head.C = n.chan; a = &head; }
+    } else if (starts("stem")) a = &n.a0;
     else if (starts("res1")) a = pick_res(n.res1, w.substr(4));
     else if (starts("pool0")) a = &n.pool0;
     else if (starts("res2")) a = pick_res(n.res2, w.substr(4));
@@ -777,7 +793,13 @@ int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int
         if (r.rfind("neck", 0) == 0) a = pick_res(h.neck, r.substr(4));
         else if (r == "maskedneck") a = &h.neckm;                                  // occlusion branch: neck * cell mask
         else if (r.rfind("maskedskip", 0) == 0) a = &h.skipm[r[10] - '1'];
-        else {
+        else if (r.rfind("poolgrad", 0) == 0) {                                     // the pool's gradient routed to its input (+ extra0)
+            const int k = r.size() == 9 ? r[8] - '1' : -1;
+            if (k >= 0 && k < 4 && h.poolgrad[k]) {
+                const Act& x = h.skip[k].x3;
+                head.raw = h.poolgrad[k]; head.B = x.B; head.H = x.H; head.W = x.W; head.C = x.C; a = &head;
+            }
+        } else {
             int k = r[r.find_first_of("1234")] - '1';
             std::string rest = r.substr(r.find_first_of("1234") + 1);
             if (r.rfind("skip", 0) == 0) a = pick_res(h.skip[k], rest);

@@ -1,0 +1,137 @@
+"""Every convolution of the hourglass net against a float64 recomputation from the engine's own operands after one real training step,
+element by element (checks and the derivation of every bound: tests/conv_exact.py).  tests/test_gpu_local.py bounds these convs at
+1e-2 / 4e-2 rel-rms and tests/test_gpu_conv.py at 4e-3 rel-rms: a dropped halo tap, a shifted tile, a wrong rounding mode, a wrong
+bias or addend or an 8-channel group with its neighbour's constants is a few percent in a few hundred elements, below both; here it is
+a failure.
+
+Legs (as tests/test_gpu_bn_exact.py): BASELINE configs[1] at full size; the configs[4] geometry (maps 96 / 48 / 24 / 12 / 6) at B 3; tiny
+maps; the IEEE-half build on the configs[4] geometry in a child process.  Then every shape of tests/test_gpu_conv.SHAPES through pa_conv2d
+in all three modes, and the split-count mirror against the library's workspace sizes.
+
+What a leg guards is geometric only: it has the map sizes that conv3x3_tile.hip's dispatch sends to the tiled 24 x 24 / 12 x 12 and masked
+6 x 6 variants (the 384 leg) and shapes the grouped weight-gradient kernel takes ('group', from the split mirror), and it checks every conv
+there; nothing the engine reports says which kernel ran.  The standalone shapes name those variants one by one (tests/test_gpu_conv.py)."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import conv_exact as X
+from tests import inputs
+from tests.test_gpu_conv import SHAPES, run_conv
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _leg(stacks, chan, B, res, seed, **kw):
+    worst, fails = X.run_leg(stacks, chan, B, res, seed, **kw)
+    assert not fails, '%d checks outside their bound, first: %s (worst per kind: %s)' % (len(fails), fails[:12], worst)
+
+
+def test_every_conv_is_exact_at_the_benchmark_size():
+    """BASELINE configs[1]: 2 stacks, chan 256, B 24, 256 x 256 (the grouped weight-gradient kernel takes the 64 x 64 layers)."""
+    _leg(2, 256, 24, 256, 41, expect=('group',))
+
+
+def test_every_conv_is_exact_on_the_384_geometry():
+    """configs[4] geometry (maps 96 / 48 / 24 / 12 / 6) at B 3."""
+    _leg(2, 256, 3, 384, 42, expect=('group',))
+
+
+def test_every_conv_is_exact_on_tiny_maps():
+    """chan 128, 128 x 128, B 2: 2 x 2 neck, the generic kernels."""
+    _leg(2, 128, 2, 128, 43)
+
+
+def test_every_conv_is_exact_in_the_fp16_build():
+    """The IEEE-half library on the configs[4] geometry, in a child process (one storage type per process)."""
+    env = dict(os.environ, POSEADV_DTYPE='fp16')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'conv_exact.py'), '2', '256', '3', '384', '44'], env=env,
+                       capture_output=True, text=True, timeout=900)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print(r.stdout)
+    assert r.returncode == 0 and 'FP16 CONV EXACT PASSED' in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('B,Cin,Cout,H,W,k', SHAPES)
+def test_standalone_conv_shapes_are_exact(B, Cin, Cout, H, W, k):
+    """pa_conv2d forward (with bias), data gradient and weight + bias gradient of every tests/test_gpu_conv shape, each element within
+    its bound.  (pa_conv2d declares the layer without a BatchNorm behind it: S is the layer's split count, grouped where the grouped
+    kernel takes the shape -- Net::layout_conv with the batch set.)"""
+    from pose_adv_aug_amd._lib import act_dtype
+    dt = act_dtype()
+    g = inputs.rng(500, B, Cin, Cout, H, W, k)
+    f = lambda *s: torch.from_numpy(g.standard_normal(s).astype(np.float32))
+    x, dy = f(B, Cin, H, W), f(B, Cout, H, W)
+    w = f(Cout, Cin, k, k) / float(np.sqrt(Cin * k * k))
+    bias = f(Cout)
+    xd, dyd, wd = X.rnd(x.double(), dt).cuda(), X.rnd(dy.double(), dt).cuda(), X.rnd(w.double(), dt).cuda()
+    worst = {}
+    y, _ = run_conv(0, x, None, w, bias, B, Cin, Cout, H, W, k)
+    worst['forward'] = X.check16(y.cuda(), X.conv_term(xd, wd, Cin * k * k, bias.double().cuda()), dt)
+    dx, _ = run_conv(1, dy, None, w, None, B, Cin, Cout, H, W, k)
+    worst['data gradient'] = X.check16(dx.cuda(), X.dgrad_term(dyd, wd, Cout * k * k), dt)
+    dw, db = run_conv(2, dy, x, w, None, B, Cin, Cout, H, W, k)
+    S = X.layer_splits(B, H, W, Cin, Cout, k)
+    worst['weight gradient'] = X.wgrad_check(dw.cuda(), xd, dyd, k, S)
+    worst['bias gradient'] = X.bgrad_check(db.cuda(), dyd, S)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print('conv_exact %s: S %d, worst error / bound, degenerate fraction: %s' % ((B, Cin, Cout, H, W, k), S, worst))
+    for kind, (r, deg) in worst.items():
+        assert r <= 1.0, (kind, r, worst)
+        assert deg <= X.DEGENERATE, ('degenerate bound', kind, deg)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _al(v):
+    return (v + 255) & ~255
+
+
+def _arena(sizes):
+    """bytes of an Arena after these takes (net.h Arena::take: each take starts 256-aligned), plus the final take(0)."""
+    off = 0
+    for s in sizes:
+        off = _al(off) + s
+    return _al(off)
+
+
+# the job tables at the front of ConvOp::build / WgradGroupOp::build (api.hip): PaPrepJob, PaWgradReduceJob, PaBnEvalJob, each < 256 bytes
+_TABLES = [48, 56, 56]
+
+
+@pytest.mark.parametrize('B,Cin,Cout,H,W,k', sorted(set(
+    [s for s in SHAPES] +
+    # the layers of the legs: 64 x 64 / 96 x 96 ... 4 x 4, 1 x 1 and 3 x 3, chan 128 / 256, the head's 16-channel layers padded to 64
+    [(24, 256, 128, 64 >> j, 64 >> j, 1) for j in range(5)] + [(24, 128, 128, 64 >> j, 64 >> j, 3) for j in range(5)] +
+    [(24, 128, 256, 64 >> j, 64 >> j, 1) for j in range(5)] + [(3, 256, 128, 96 >> j, 96 >> j, 1) for j in range(5)] +
+    [(3, 128, 128, 96 >> j, 96 >> j, 3) for j in range(5)] + [(2, 64, 64, 32 >> j, 32 >> j, 3) for j in range(4)] +
+    [(24, 256, 64, 64, 64, 1), (24, 64, 256, 64, 64, 1), (3, 64, 256, 96, 96, 1), (2, 64, 128, 32, 32, 1)])))
+def test_split_mirror_matches_the_library(B, Cin, Cout, H, W, k):
+    """S of tests/conv_exact.py (pa_wgrad_splits and pa_wgrad_group_splits) against the split counts the library's workspace sizes
+    reveal: pa_conv2d_workspace_bytes lays the layer out without a batch (no grouped split: pa_wgrad_splits), pa_wgrad_group_workspace_bytes
+    with it (the grouped split where the grouped kernel takes the shape).  Both workspaces hold S slabs of Cout * taps * Cin floats."""
+    from pose_adv_aug_amd._lib import lib
+    L = lib()
+    M, wn = B * H * W, Cout * k * k * Cin
+    # ConvOp::build: tables, wf, wb, part [S][wn], dbpart [S][Cout] (declared without a BatchNorm behind it), xin, yout
+    fixed = lambda S, db: _arena(_TABLES + [2 * wn, 2 * wn, 4 * S * wn] + ([4 * S * Cout] if db else []) + [2 * M * Cin, 2 * M * Cout])
+    got = L.pa_conv2d_workspace_bytes(B, Cin, Cout, H, W, k)
+    S1 = [S for S in range(1, 4097) if fixed(S, True) == got]
+    assert S1 == [X.wgrad_splits(M, H, W, Cin, Cout, k * k)], (got, S1)
+
+    class Job(ctypes.Structure):
+        _fields_ = [(n, ctypes.c_int) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'k')] + \
+                   [(n, ctypes.c_void_p) for n in ('dy', 'dy_q', 'dy_k', 'x', 'x_k', 'dw', 'db')]
+    j = Job(B, Cin, Cout, H, W, k)
+    got = L.pa_wgrad_group_workspace_bytes(ctypes.addressof(j), 1)
+    nparams = ((Cout * Cin * k * k + 3) & ~3) + Cout
+    # WgradGroupOp::build (one job, no bias gradient): tables, wf, wb, part [S][wn], dy, x, pbuf, gbuf
+    grp = lambda S: _arena(_TABLES + [2 * wn, 2 * wn, 4 * S * wn, 2 * M * Cout, 2 * M * Cin, 4 * (nparams + 8), 4 * (nparams + 8)])
+    S2 = [S for S in range(1, 4097) if grp(S) == got]
+    assert S2 == [X.layer_splits(B, H, W, Cin, Cout, k)], (got, S2)
