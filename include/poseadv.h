@@ -205,7 +205,9 @@ typedef struct pa_net pa_net;
  * fixed per-GPU batch B and input resolution res (256).  chan must be a multiple of 128. */
 pa_net* pa_hg_create(int num_stacks, int num_classes, int chan, int B, int res);
 /* create_asn(chan, chan, scale_num, rotation_num, is_aug=True) (models/asn_stacked_hg.py:441-444) bound
- * to the feature shapes of a pose net with neck resolution res/64. */
+ * to the feature shapes of a pose net with neck resolution res/64.  The head is the reference's AvgPool2d(4) + view +
+ * Linear(chan, K): the mean of the TOP-LEFT 4 x 4 window of the res/64 top map (the whole map at res 256), gradient df / 16 inside
+ * that window and 0 outside.  256 <= res <= 448 (one pool window); any other res returns NULL with pa_last_error() set. */
 pa_net* pa_asn_create(int chan, int scale_num, int rotation_num, int B, int res);
 /* create_asn(chan, chan, is_dropout=True) (models/asn_stacked_hg.py:378-379,437-439): the same trunk with the occlusion
  * head out_conv = Conv2d(chan, 1, 1) on the 4x4 map.  res must be 256 (the mask is the 4x4 neck map). */

@@ -447,6 +447,12 @@ pa_net* pa_asn_create(int chan, int scale_num, int rotation_num, int B, int res)
         pa_set_error_msg("pa_asn_create: need chan % 128 == 0, res % 64 == 0, scale_num + rotation_num <= 64");
         return nullptr;
     }
+    // the head is AvgPool2d(4) + view + Linear(chan, K) (reference :375, :430-436): the pool of the res / 64 top map must have exactly
+    // one output (a map below 4 x 4 has none: the reference raises; from 8 x 8 on there are four and its Linear does not fit)
+    if (res / 64 < 4 || res / 64 > 7) {
+        pa_set_error_msg("pa_asn_create: need 256 <= res <= 448 (a res / 64 top map of 4 x 4 .. 7 x 7: one AvgPool2d(4) window)");
+        return nullptr;
+    }
     pa_net* p = new (std::nothrow) pa_net;
     if (!p) return nullptr;
     Net& n = p->n;

@@ -49,20 +49,21 @@ static int launch_pooladd_fwd(const PaOperand& hi, const PaOperand& lo, bf16* ou
 }
 
 // ------------------------------------------------------------------------------------------------
-// AvgPool2d(4) over the 4x4 map + fc_scale / fc_rotation (Linear C -> K) + softmax  (reference :430-436;
-// softmax: joint-train-pose-s-r-agent.py:252-253).  One workgroup per sample.
-__global__ void asn_head_fwd_kernel(PaOperand x, int HW, int C, const float* ws, const float* bs, const float* wr, const float* br,
+// AvgPool2d(4) + view + fc_scale / fc_rotation (Linear C -> K) + softmax  (reference :375, :430-436; softmax:
+// joint-train-pose-s-r-agent.py:252-253).  The Linear takes C features, so the pool has exactly one output: the mean of the TOP-LEFT
+// 4 x 4 window of the H x W top map (4 <= H, W <= 7, pa_asn_create) -- the whole map only at 4 x 4.  One workgroup per sample.
+__global__ void asn_head_fwd_kernel(PaOperand x, int H, int W, int C, const float* ws, const float* bs, const float* wr, const float* br,
                                     int Ks, int Kr, float* feat, float* logits, float* probs) {
     extern __shared__ float sm[];          // [C] features, then [Ks+Kr] logits
     const int b = blockIdx.x;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         float acc = 0.f;
-        for (int p = 0; p < HW; ++p) {
-            float v = (float)x.p[((size_t)b * HW + p) * C + c];
+        for (int p = 0; p < 16; ++p) {
+            float v = (float)x.p[((size_t)b * H * W + (p >> 2) * W + (p & 3)) * C + c];
             if (x.mode == PA_LD_BNRELU) v = fmaxf(fmaf(x.k0[c], v, x.k1[c]), 0.f);
             acc += v;
         }
-        acc /= (float)HW;
+        acc /= 16.f;
         sm[c] = acc;
         feat[(size_t)b * C + c] = acc;
     }
@@ -90,9 +91,9 @@ __global__ void asn_head_fwd_kernel(PaOperand x, int HW, int C, const float* ws,
 // KL loss (joint-train-pose-s-r-agent.py:399-407): sum over the two heads of
 //   K * mean_{b,k} t * (log t - log(p + eps)),  p = softmax(logits); eps = 1e-7 in the joint loop, 0 in the agent
 //   pre-training (pretrain-s-r-agent.py:177-190 uses LogSoftmax)
-// d/dlogits, d/dfeat (spread back over the HW pixels as the gradient of the average pool), loss value.
+// d/dlogits, d/dfeat (the gradient of the average pool: df / 16 inside the top-left 4 x 4 window, 0 outside it), loss value.
 __global__ void asn_head_bwd_kernel(const float* probs, const float* target_s, const float* target_r, const float* ws, const float* wr,
-                                    int Ks, int Kr, int HW, int C, int B, float* dlogits, bf16* dact, float* loss, float leps) {
+                                    int Ks, int Kr, int H, int W, int C, int B, float* dlogits, bf16* dact, float* loss, float leps) {
     extern __shared__ float sm[];          // [Ks+Kr] dlogits
     const int b = blockIdx.x, K = Ks + Kr;
     if (threadIdx.x < 2) {
@@ -117,8 +118,8 @@ __global__ void asn_head_bwd_kernel(const float* probs, const float* target_s, c
         float df = 0.f;
         for (int k = 0; k < Ks; ++k) df = fmaf(sm[k], ws[(size_t)k * C + c], df);
         for (int k = 0; k < Kr; ++k) df = fmaf(sm[Ks + k], wr[(size_t)k * C + c], df);
-        const bf16 v = (bf16)(df / (float)HW);
-        for (int p = 0; p < HW; ++p) dact[((size_t)b * HW + p) * C + c] = v;
+        const bf16 v = (bf16)(df / 16.f), zero = (bf16)0.f;
+        for (int p = 0; p < H * W; ++p) dact[((size_t)b * H * W + p) * C + c] = (p / W < 4 && p % W < 4) ? v : zero;
     }
 }
 
@@ -287,8 +288,8 @@ int Net::asn_forward(Net& pose, bool train, float* logits_s, float* logits_r) {
     if (asn_dropout) { pa_set_error_msg("asn_forward: this agent was created with the occlusion-mask head"); return 1; }
     const Act* x = nullptr;
     TRY(asn_forward_trunk(pose, train, &x));
-    const int HW = x->H * x->W, K = scale_num + rot_num;
-    hipLaunchKernelGGL(asn_head_fwd_kernel, dim3(B), dim3(256), (chan + K) * sizeof(float), st, op(*x), HW, chan,
+    const int K = scale_num + rot_num;
+    hipLaunchKernelGGL(asn_head_fwd_kernel, dim3(B), dim3(256), (chan + K) * sizeof(float), st, op(*x), x->H, x->W, chan,
                        params + p_fcs_w, params + p_fcs_b, params + p_fcr_w, params + p_fcr_b, scale_num, rot_num, asn_feat,
                        asn_logits, asn_probs);
     TRY((int)hipGetLastError());
@@ -303,10 +304,10 @@ int Net::asn_forward(Net& pose, bool train, float* logits_s, float* logits_r) {
 int Net::asn_backward(Net& pose, const float* target_s, const float* target_r, float* loss_out) {
     if (asn_dropout) { pa_set_error_msg("asn_backward: this agent was created with the occlusion-mask head"); return 1; }
     const Act& top = asn_deep[2].x3;
-    const int HW = top.H * top.W, K = scale_num + rot_num;
-    bf16* dact = asn_pa[3].grad;                   // scratch of the right size [B][4][4][C]; rewritten later in this pass
+    const int K = scale_num + rot_num;
+    bf16* dact = asn_pa[3].grad;                   // scratch of the right size (the top map's); rewritten later in this pass
     hipLaunchKernelGGL(asn_head_bwd_kernel, dim3(B), dim3(256), K * sizeof(float), st, asn_probs, target_s, target_r,
-                       params + p_fcs_w, params + p_fcr_w, scale_num, rot_num, HW, chan, B, asn_dlogits, dact, loss_dev, asn_log_eps);
+                       params + p_fcs_w, params + p_fcr_w, scale_num, rot_num, top.H, top.W, chan, B, asn_dlogits, dact, loss_dev, asn_log_eps);
     TRY((int)hipGetLastError());
     hipLaunchKernelGGL(asn_fc_wgrad_kernel, dim3(8), dim3(256), 0, st, asn_dlogits, asn_feat, B, scale_num, rot_num, chan,
                        grads + p_fcs_w, grads + p_fcs_b, grads + p_fcr_w, grads + p_fcr_b);

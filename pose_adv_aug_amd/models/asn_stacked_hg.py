@@ -288,6 +288,7 @@ class HourglassNet(_HipModule):
         self._last_B = B
         p = pts.to(torch.float64).contiguous()
         losses = torch.empty(self.num_stacks, dtype=torch.float32, device=self.flat_params.device)      # the engine copies every entry
+        self._last_losses = losses                                  # per-stack values of this step (the returned loss is their sum)
         if self.use_graph and x is None and dropout_masks is None:
             check(lib().pa_hg_train_step(h, ptr(img4), ptr(p), 1 if self.training else 0, 1, ptr(losses)), 'pa_hg_train_step')
             if self.training:

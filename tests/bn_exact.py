@@ -18,6 +18,8 @@ dz * (x - mean) * invstd, bn_eval_kernel), with u = 2^-24 and these rules (class
   * an fp32 add / sub / mul / correctly rounded division of two quantities known to within e_a, e_b adds |a| e_b + |b| e_a + e_a e_b of
     propagated error and u (|result| + propagated error) of rounding; fmaf rounds once;
   * rsqrtf (v_rsq_f32) is within 1 ulp = 2u: its bound is the exact interval [rsqrt(t + e), rsqrt(t - e)] widened by 2u;
+  * expf / logf (the agent's softmax and KL loss, tests/asn_exact.py): the exact interval of the function over its argument's interval,
+    widened by 2 ulp = 4u of the result -- an ASSUMPTION (see tests/asn_exact.py);
   * a per-channel sum of n fp32 values computed by any tree in which no value passes through more than D additions is within
     D u sum|x_i| of the exact sum.  D (sum_depth) is derived from the kernels of the release build, in two parts:
       - inside one partial row: a conv epilogue's row covers at most 128 pixels (the 1 x 1 / 3 x 3 tile kernels and the implicit-GEMM
@@ -38,7 +40,18 @@ The parameters, running estimates and stored tensors are fp32 / storage-type val
 in the engine's own units (the fp16 build carries pa_grad_scale() in every gradient: all checks are homogeneous in it).
 
 Pool forward, merge forward and merge backward involve no accumulation: one fp32 max / add / 2 x 2 sum in a fixed order, rounded once to
-the storage type (round to nearest even, the conversion of gfx950 and of torch), so they are compared bit for bit."""
+the storage type (round to nearest even, the conversion of gfx950 and of torch), so they are compared bit for bit.
+
+Pool backward (maxpool_bwd_kernel elementwise.hip:518-532, the streaming maxpool_bwd_s_kernel :589-609, both `if (v[k] > m)` over
+k = 0..3 = top-left, top-right, bottom-left, bottom-right: the FIRST maximum in scan order keeps the gradient) is bit-exact too: the
+value compared is the fp32 BatchNorm+ReLU value view 0 (the kernels' own fmaxf(fmaf(k0, raw, k1), 0)), the routed gradient takes at
+most one fp32 add (the addend: d xin<i+1> into poolgrad1 of an inner stack, Hourglass::bwd net.hip:885) and one rounding; with a
+BatchNorm-backward epilogue (pool0 into res1, net.hip:1092; the agent's merges) the stored view 1 is the ReLU-masked routed gradient.
+After ReLU most windows of a map hold several zeros, so ties are the common case: a leg must have met tied windows ('tied pool
+windows'), or 'first maximum' was not tested.
+
+check_bn_site / check_bn_eval_site are the per-BatchNorm checks; the probe of the tensor is an argument, so tests/asn_exact.py runs
+the same checks (one definition of each bound) over the agent's BatchNorms through AsnProbe."""
 import os
 import sys
 
@@ -87,6 +100,22 @@ class E(object):
 
     def __neg__(self):
         return E(-self.v, self.e)
+
+    def div(self, o):                   # by another E whose interval excludes 0: correctly rounded (hipcc's default for fp32 '/')
+        v = self.v / o.v
+        return E._r(v, (self.e + v.abs() * o.e) / (o.v.abs() - o.e).clamp_min(1e-300))
+
+    def exp(self, ulps=2):              # expf within `ulps` ulp (1 ulp <= 2u relative) of the exact exponential of its fp32 argument
+        v = self.v.exp()
+        e = v * torch.expm1(self.e)
+        return E(v, e + ulps * 2 * U * (v + e))
+
+    def log(self, ulps=2):              # logf of a positive quantity
+        v = self.v.log()
+        lo = (self.v - self.e).clamp_min(1e-300).log()
+        hi = (self.v + self.e).log()
+        e = torch.maximum(v - lo, hi - v)
+        return E(v, e + ulps * 2 * U * (v.abs() + e))
 
     def rsqrt(self):
         lo = (self.v + self.e).rsqrt()
@@ -212,6 +241,39 @@ def check_pool(val_in, pooled, dtype):
     return _mismatch(pooled, rnd(F.max_pool2d(val_in.float(), 2, 2), dtype))
 
 
+def _win(x):
+    """the four pixels of every 2 x 2 window in scan order: top-left, top-right, bottom-left, bottom-right"""
+    return torch.stack([x[:, :, 0::2, 0::2], x[:, :, 0::2, 1::2], x[:, :, 1::2, 0::2], x[:, :, 1::2, 1::2]], 0)
+
+
+def _unwin(w):
+    out = torch.zeros(w.shape[1], w.shape[2], 2 * w.shape[3], 2 * w.shape[4], dtype=w.dtype, device=w.device)
+    out[:, :, 0::2, 0::2], out[:, :, 0::2, 1::2], out[:, :, 1::2, 0::2], out[:, :, 1::2, 1::2] = w[0], w[1], w[2], w[3]
+    return out
+
+
+def route(g, val_in, last=False):
+    """the pooled map's gradient g sent to the FIRST maximum (scan order) of every 2 x 2 window of val_in (fp32), 0 elsewhere; returns
+    (routed, number of windows with two or more equal maxima).  last=True: the last maximum (a defect, tests/test_asn_exact_cpu.py)."""
+    v = _win(val_in.float())
+    eq = v == v.max(0).values
+    order = eq.flip(0) if last else eq
+    first = order & (order.cumsum(0) == 1)
+    first = first.flip(0) if last else first
+    return _unwin(first.float() * g.float().unsqueeze(0)), int((eq.sum(0) >= 2).sum())
+
+
+def check_pool_bwd(dpooled, val_in, got, dtype, addend=None, masked=False):
+    """got = round(route(d pooled) + addend) (one fp32 add, one rounding), times [val_in > 0] under a BatchNorm-backward epilogue.
+    Returns (differing elements, tied windows)."""
+    r, ties = route(dpooled, val_in)
+    if addend is not None:
+        r = rnd(r + addend.float(), dtype)
+    if masked:
+        r = r * (val_in > 0).float()
+    return _mismatch(got, r), ties
+
+
 def up2(x):
     return x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
 
@@ -270,22 +332,64 @@ class Probe(object):
         from pose_adv_aug_amd._lib import lib, check, ptr
         self.C, self.lib, self.check, self.ptr = ctypes, lib(), check, ptr
         self.h = net._net(net._last_B)
+        self.fn = self.lib.pa_hg_debug_tensor
 
     def has(self, name, view):
         shp = (self.C.c_int * 4)()
-        return self.lib.pa_hg_debug_tensor(self.h, name.encode(), view, None, shp) == 0
+        return self.fn(self.h, name.encode(), view, None, shp) == 0
 
     def get(self, name, view):
         assert name not in NOT_HELD, name
         shp = (self.C.c_int * 4)()
-        self.check(self.lib.pa_hg_debug_tensor(self.h, name.encode(), view, None, shp))
+        self.check(self.fn(self.h, name.encode(), view, None, shp))
         out = torch.empty(tuple(shp), device='cuda')
-        self.check(self.lib.pa_hg_debug_tensor(self.h, name.encode(), view, self.ptr(out), shp))
+        self.check(self.fn(self.h, name.encode(), view, self.ptr(out), shp))
         return out
 
 
+class AsnProbe(Probe):
+    """the same views of the agent's tensors (pa_asn_debug_tensor: in0..4, pa0..3, merge0..3, deep0..2, .x1 / .x2)"""
+    def __init__(self, agent):
+        Probe.__init__(self, agent)
+        self.fn = self.lib.pa_asn_debug_tensor
+
+
 KINDS = ('bn forward', 'running stats', 'beta/gamma grads', 'bn backward', 'stored bn backward', 'eval forward', 'pool forward',
-         'merge forward', 'merge backward', 'degenerate bound')
+         'merge forward', 'merge backward', 'degenerate bound', 'pool backward')
+
+
+def make_note(worst, fails):
+    def note(kind, what, r, bit=False):
+        worst[kind] = max(worst[kind], r)
+        if (r != 0) if bit else not (r <= 1.0):          # ('degenerate bound': width / DEGENERATE, the same rule)
+            fails.append((kind, what, r))
+    return note
+
+
+def check_bn_site(P, pre, name, sd, before, grads, dtype, note, stored, rows_scale=1):
+    """every check of ONE BatchNorm after a training step.  P: probe of the net that owns the tensor `name`; pre: its parameter prefix
+    in sd (after the step) / before (the running estimates before it) / grads; stored: counters of the blocks that stored dz2 / dz3."""
+    raw = P.get(name, 2).double()
+    gamma, beta = sd[pre + '.weight'].double(), sd[pre + '.bias'].double()
+    k = fwd_consts(raw, gamma, beta, rows_scale=rows_scale)
+    note('degenerate bound', pre, k['degenerate'] / DEGENERATE)
+    note('bn forward', name, check_forward(raw, P.get(name, 0), k))
+    note('running stats', pre, check_running(k, before[pre + '.running_mean'], before[pre + '.running_var'],
+                                            sd[pre + '.running_mean'], sd[pre + '.running_var']))
+    dz = P.get(name, 1).double()
+    T1, T2 = bwd_sums(raw, dz, k)
+    note('beta/gamma grads', pre, check_param_grads(T1, T2, grads[pre + '.weight'], grads[pre + '.bias']))
+    dx = P.get(name, 3)
+    note('bn backward', name, check_backward(raw, dz, dx, k, T1, T2))
+    if P.has(name, 4):
+        stored['.x2' if name.endswith('.x2') else ''] += 1
+        note('stored bn backward', name, _mismatch(P.get(name, 4), rnd(dx, dtype)), bit=True)
+
+
+def check_bn_eval_site(P, pre, name, sd, note):
+    """eval mode: view 0 of the tensor against the running estimates in sd"""
+    note('eval forward', name, check_eval(P.get(name, 2).double(), P.get(name, 0), sd[pre + '.weight'], sd[pre + '.bias'],
+                                          sd[pre + '.running_mean'], sd[pre + '.running_var']))
 
 
 def run_leg(stacks, chan, B, res, seed, log=print, stored_expected=('.x2', '')):
@@ -314,37 +418,32 @@ def run_leg(stacks, chan, B, res, seed, log=print, stored_expected=('.x2', '')):
     P = Probe(net)
     worst = dict((k, 0.0) for k in KINDS)
     fails = []
-
-    def note(kind, what, r, bit=False):
-        worst[kind] = max(worst[kind], r)
-        if (r != 0) if bit else not (r <= 1.0):          # ('degenerate bound': width / DEGENERATE, the same rule)
-            fails.append((kind, what, r))
-
+    note = make_note(worst, fails)
     stored = {'.x2': 0, '': 0}
     for pre, name in sites:
-        raw = P.get(name, 2).double()
-        gamma, beta = sd[pre + '.weight'].double(), sd[pre + '.bias'].double()
         up_bn3 = '.up' in name and not name.endswith(('.x1', '.x2'))
-        k = fwd_consts(raw, gamma, beta, rows_scale=4 if up_bn3 else 1)
-        note('degenerate bound', pre, k['degenerate'] / DEGENERATE)
-        note('bn forward', name, check_forward(raw, P.get(name, 0), k))
-        note('running stats', pre, check_running(k, before[pre + '.running_mean'], before[pre + '.running_var'],
-                                                sd[pre + '.running_mean'], sd[pre + '.running_var']))
-        dz = P.get(name, 1).double()
-        T1, T2 = bwd_sums(raw, dz, k)
-        note('beta/gamma grads', pre, check_param_grads(T1, T2, grads[pre + '.weight'], grads[pre + '.bias']))
-        dx = P.get(name, 3)
-        note('bn backward', name, check_backward(raw, dz, dx, k, T1, T2))
-        if P.has(name, 4):
-            stored['.x2' if name.endswith('.x2') else ''] += 1
-            note('stored bn backward', name, _mismatch(P.get(name, 4), rnd(dx, dtype)), bit=True)
-        del raw, dz, dx, k, T1, T2
+        check_bn_site(P, pre, name, sd, before, grads, dtype, note, stored, rows_scale=4 if up_bn3 else 1)
     # (a leg that expects a kind must have met it: the check must not go quiet because the kernels stopped storing)
     for suf, cnt in stored.items():
         if cnt == 0 and suf in stored_expected:
             fails.append(('stored bn backward', 'no block stored its dz%s' % ('2' if suf else '3'), 0))
+    ties = 0
     for out, src in pool_sites(stacks):
-        note('pool forward', out, check_pool(P.get(src, 0), P.get(out, 0), dtype), bit=True)
+        vin = P.get(src, 0)
+        note('pool forward', out, check_pool(vin, P.get(out, 0), dtype), bit=True)
+        # pool backward (module docstring): pool0 writes d res1 through res1's BatchNorm-backward epilogue (view 1: the masked gradient);
+        # hourglass pool k writes poolgrad<k>, with d xin<i+1> added for k = 1 of an inner stack
+        if out == 'pool0':
+            r, n = check_pool_bwd(P.get(out, 1), vin, P.get(src, 1), dtype, masked=True)
+        else:
+            i, k = int(out[2]), int(out[-1])
+            add = P.get('xin%d' % (i + 1), 1) if (k == 1 and i + 1 < stacks) else None
+            r, n = check_pool_bwd(P.get(out, 1), vin, P.get('hg%d.poolgrad%d' % (i, k), 2), dtype, addend=add)
+        note('pool backward', out, r, bit=True)
+        ties += n
+        del vin
+    if ties == 0:
+        fails.append(('pool backward', 'no 2 x 2 window of this leg had tied maxima: first-maximum routing was not tested', 0))
     for i in range(stacks):
         for k in (1, 2, 3, 4):
             m, up, sk = 'hg%d.merge%d' % (i, k), 'hg%d.up%d' % (i, k), 'hg%d.skip%d' % (i, k)
@@ -356,13 +455,12 @@ def run_leg(stacks, chan, B, res, seed, log=print, stored_expected=('.x2', '')):
     net(img)
     torch.cuda.synchronize()
     for pre, name in sites:
-        note('eval forward', name, check_eval(P.get(name, 2).double(), P.get(name, 0), sd[pre + '.weight'], sd[pre + '.bias'],
-                                              sd[pre + '.running_mean'], sd[pre + '.running_var']))
+        check_bn_eval_site(P, pre, name, sd, note)
     if os.environ.get('POSEADV_TEST_VERBOSE'):
         log('bn_exact %s stacks %d chan %d B %d res %d: worst error / bound (bit-exact kinds: differing elements): %s'
             % (torch.float16 if dtype == torch.float16 else 'bf16', stacks, chan, B, res,
                ', '.join('%s %.3g' % (k, worst[k]) for k in KINDS)) + '; stored dz2 / dz3 checked in %d / %d blocks'
-            % (stored['.x2'], stored['']))
+            % (stored['.x2'], stored['']) + '; %d tied pool windows' % ties)
     return worst, fails
 
 

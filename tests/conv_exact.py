@@ -324,13 +324,153 @@ def conv_names(stacks):
     return n
 
 
-KINDS = ('conv forward', 'conv data gradient', 'weight gradient', 'bias gradient', 'zero bias gradient', 'degenerate bound')
+KINDS = ('conv forward', 'conv data gradient', 'weight gradient', 'bias gradient', 'zero bias gradient', 'degenerate bound', 'heat gradient',
+         'loss')
+
+
+class Checker(object):
+    """The bookkeeping and the per-block checks of one leg over ONE net's parameters: sd0 (its state_dict before the step), grads (its
+    named gradients after it), B.  The probes of the tensors are arguments of every check, so a block may read its input from another
+    net (the agent's five input blocks read the pose net's features in place: tests/asn_exact.py)."""
+    def __init__(self, sd0, grads, dtype, B):
+        self.sd0, self.grads, self.dtype, self.B = sd0, grads, dtype, B
+        self.worst = dict((k, 0.0) for k in KINDS)
+        self.fails = []
+        self.met = {'group': 0}
+        self.checked = set()         # (conv, kind): what each conv's checks covered
+
+    def W(self, n):
+        return rnd(self.sd0[n + '.weight'].double(), self.dtype)
+
+    def bias(self, n):
+        return self.sd0[n + '.bias'].double()
+
+    def note(self, kind, what, r_deg, convs=()):
+        for c in convs:
+            self.checked.add((c, 'bias' if kind.endswith('bias gradient') else kind))
+        r, deg = r_deg
+        self.worst[kind] = max(self.worst[kind], r)
+        self.worst['degenerate bound'] = max(self.worst['degenerate bound'], deg / DEGENERATE)
+        if not (r <= 1.0):
+            self.fails.append((kind, what, r))
+        if deg > DEGENERATE:
+            self.fails.append(('degenerate bound', '%s %s' % (kind, what), deg))
+
+    def grad_op(self, P, name):
+        """the gradient operand the consumers of `name` read: view 4 where the step stored it, else rnd(view 3)."""
+        return (P.get(name, 4) if P.has(name, 4) else rnd(P.get(name, 3), self.dtype)).double()
+
+    def wg(self, conv, x, dy, k, H, stride=1, pad=None, has_bias=False):
+        B, grads = self.B, self.grads
+        S = layer_splits(B, H, H, x.shape[1], dy.shape[1], k)
+        if k != 7 and group_splits(B, H, H, pad64(x.shape[1]), pad64(dy.shape[1]), k * k) > 0:
+            self.met['group'] += 1
+        self.note('weight gradient', conv, wgrad_check(grads[conv + '.weight'], x, dy, k, S, stride, pad), (conv,))
+        if has_bias:
+            self.note('bias gradient', conv, bgrad_check(grads[conv + '.bias'], dy, S), (conv,))
+        else:
+            z = grads[conv + '.bias']
+            self.worst['zero bias gradient'] = max(self.worst['zero bias gradient'], float(z.abs().max()))
+            self.checked.add((conv, 'bias'))
+            if bool((z != 0).any()):
+                self.fails.append(('zero bias gradient', conv, float(z.abs().max())))
+
+    def block(self, p, out, Po, Pi, inp, input_grad=True, ad=False, add2=None, in_masked=True):
+        """One residual block (Residual::fwd / bwd_a / bwd_b, net.hip:691-763): forward of conv1 / conv2 / conv3 (+ adapter), the inner data
+        gradients, the weight gradients at the layer's split count, zero bias gradients, and -- input_grad -- the data gradient of the
+        block's input.  p: parameter prefix; out: hook name of the output in probe Po; inp: hook name of the input in probe Pi;
+        ad: the block has an adapter; add2: a second addend of the input's data gradient (the pool's routed gradient); in_masked: the
+        input has a pending BatchNorm (its gradient is stored ReLU-masked).  input_grad=False (Residual::bwd with need_dx = false): the
+        input belongs to another net and gets no gradient; the caller asserts that net's gradients stayed zero."""
+        dtype, note, W, bias, wg = self.dtype, self.note, self.W, self.bias, self.wg
+        grad_op = lambda n: self.grad_op(Po, n)
+        sv0 = lambda n: rnd(Po.get(n, 0), dtype).double()
+        cin = Pi.get(inp, 0).shape[1]
+        H = Po.get(out, 2).shape[2]
+        mid = Po.get(out + '.x1', 2).shape[1]
+        xin = Pi.get(inp, 0).double()
+        x_in = rnd(xin, dtype)
+        t1 = conv_term(x_in, W(p + 'conv1'), pad64(cin), bias(p + 'conv1'))
+        note('conv forward', p + 'conv1', check16(Po.get(out + '.x1', 2), t1, dtype), (p + 'conv1',))
+        del t1
+        x1v = sv0(out + '.x1')
+        t2 = conv_term(x1v, W(p + 'conv2'), 9 * pad64(mid), bias(p + 'conv2'))
+        note('conv forward', p + 'conv2', check16(Po.get(out + '.x2', 2), t2, dtype), (p + 'conv2',))
+        del t2
+        x2v = sv0(out + '.x2')
+        if ad:      # x3 = conv3(x2) + b3 + adout, adout = rnd(adapter(in) + b_ad): not exposed, one more half ulp
+            short = rounded(conv_term(x_in, W(p + 'adapter'), pad64(cin), bias(p + 'adapter')), dtype)
+        else:       # the identity shortcut: the block input's fp32 value (the epilogue's BNRELU / plain load)
+            short = xin
+        t3 = conv_term(x2v, W(p + 'conv3'), pad64(mid), bias(p + 'conv3'), (short,))
+        note('conv forward', p + 'conv3', check16(Po.get(out, 2), t3, dtype), (p + 'conv3',) + ((p + 'adapter',) if ad else ()))
+        del t3, short
+        # inner data gradients: one consumer each, masked by the ReLU of the tensor's own value
+        g3 = grad_op(out)
+        g2 = grad_op(out + '.x2')
+        m2 = (Po.get(out + '.x2', 0) > 0).double()
+        note('conv data gradient', p + 'conv3', check16(Po.get(out + '.x2', 1), dgrad_term(g3, W(p + 'conv3'), pad64(g3.shape[1])), dtype, m2),
+             (p + 'conv3',))
+        m1 = (Po.get(out + '.x1', 0) > 0).double()
+        note('conv data gradient', p + 'conv2', check16(Po.get(out + '.x1', 1), dgrad_term(g2, W(p + 'conv2'), 9 * pad64(mid)), dtype, m1),
+             (p + 'conv2',))
+        g1 = grad_op(out + '.x1')
+        wg(p + 'conv3', x2v, g3, 1, H)
+        wg(p + 'conv2', x1v, g2, 3, H)
+        wg(p + 'conv1', x_in, g1, 1, H)
+        if ad:
+            wg(p + 'adapter', x_in, g3, 1, H)
+        if not input_grad:
+            return
+        # d in = mask * (conv1^T(g1) + add1 [+ add2]) (Residual::bwd_b, net.hip:750-763)
+        if ad:      # add1 = adgrad = rnd(adapter^T(g3)), not exposed; residual1 / residual3 have no other reader of their input
+            adds = (rounded(dgrad_term(g3, W(p + 'adapter'), pad64(g3.shape[1])), dtype),)
+        else:       # add1: the x3 gradient as conv1's epilogue loads it, dz3 (view 4) or the LIN2 value in fp32 (view 3)
+            adds = ((Po.get(out, 4) if Po.has(out, 4) else Po.get(out, 3)).double(),)
+        if add2 is not None:
+            adds += (add2.double(),)
+        mask = (xin > 0).double() if in_masked else None
+        note('conv data gradient', inp, check16(Pi.get(inp, 1), dgrad_term(g1, W(p + 'conv1'), pad64(mid), adds), dtype, mask),
+             (p + 'conv1',) + ((p + 'adapter',) if ad else ()))
+
+
+def loss_depth(M):
+    """the most additions a squared difference passes through in head_fwd_kernel's loss (pose_ops.hip:107-166, the launch :173-178):
+    a lane adds its 4 joints of every group it visits, groups = ceil(M / 16) strided over 4 waves of blocks = min(768, ceil(groups / 4))
+    workgroups; 6 shuffle levels; 3 adds of the waves' sums; up to blocks - 1 atomic adds in any order."""
+    groups = -(-M // 16)
+    blocks = min(768, -(-groups // 4))
+    return 4 * -(-groups // (4 * blocks)) + 6 + 3 + (blocks - 1)
+
+
+def loss_check(got, heat, target):
+    """one stack's MSE (fp32) against float64 over the returned fp32 heat maps: per term d = heat - target and d * d (two roundings, or
+    one with the sum's fma), loss_depth additions, then the product with the fp32 1 / (M * 16) (two roundings).  All terms are >= 0."""
+    from tests.bn_exact import E
+    d2 = ((heat.double() - target.double()) ** 2).sum()
+    M = heat.shape[0] * heat.shape[2] * heat.shape[3]
+    s = E(d2, (loss_depth(M) + 3) * U * d2) * E(1.0 / (16.0 * M), U / (16.0 * M))
+    return s, ratio(got.reshape(1), s.v.reshape(1), s.e.reshape(1))
+
+
+def heat_grad_check(got, heat, target, gscale, add, dtype):
+    """d heat (storage type) against 2 (heat - target) gscale (+ add): heat_grad_kernel pose_ops.hip:198-200 -- a subtraction, the exact
+    doubling, the product with the fp32 gscale = grad_scale / (B * 16 * H * H) (itself one rounded division, net.hip:1055), the add of
+    in_conv's data gradient: three or four roundings, fewer where the compiler contracts the product and the add into one fma (a
+    first-order bound over the separate operations admits both); then the half ulp of the storage type."""
+    from tests.bn_exact import E
+    g = (E(heat.double()) - E(target.double())) * E(torch.full_like(heat.double(), 2.0 * gscale), 2.0 * gscale * U)
+    mag = 2.0 * gscale * (heat.double().abs() + target.double().abs())
+    if add is not None:
+        g = g + E(add.double())
+        mag = mag + add.double().abs()
+    return check16(got, Term(g.v, g.e, mag), dtype)
 
 
 def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
     """One training step (loss_and_backward, default multi-stream mode), then every check.  Returns {kind: worst error / bound} and the
     failures.  expect: weight-gradient split kinds this leg must meet ('group': a layer whose split count is the grouped kernel's)."""
-    from pose_adv_aug_amd._lib import act_dtype
+    from pose_adv_aug_amd._lib import act_dtype, grad_scale
     from tests import inputs
     from tests.bn_exact import Probe
     from tests.test_gpu_net import t, _hg_pair
@@ -343,49 +483,19 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
     assert sorted(names) == sorted(k[:-len('.weight')] for k in sd0 if k.endswith('.weight') and sd0[k].dim() == 4), \
         'conv_names must name every conv of the net'
     img = t(inputs.images(seed + 100, B, res)).cuda()
-    pts = t(inputs.heat_pts(seed + 101, B, res=res // 4)).cuda()
+    pts_np = inputs.heat_pts(seed + 101, B, res=res // 4)
+    pts = t(pts_np).cuda()
     net.train()
-    _, outs = net.loss_and_backward(img, pts, want_outputs=True)
+    loss_total, outs = net.loss_and_backward(img, pts, want_outputs=True)
+    loss_total = loss_total.clone()
     torch.cuda.synchronize()
     grads = {n: g.clone() for n, g in net.named_grads()}
     P = Probe(net)
-    W = lambda n: rnd(sd0[n + '.weight'].double(), dtype)
-    bias = lambda n: sd0[n + '.bias'].double()
+    ck = Checker(sd0, grads, dtype, B)
+    W, bias, note, wg, worst, fails, met, checked = ck.W, ck.bias, ck.note, ck.wg, ck.worst, ck.fails, ck.met, ck.checked
+    grad_op = lambda n: ck.grad_op(P, n)
     v0 = lambda n: P.get(n, 0).double()
     sv0 = lambda n: rnd(P.get(n, 0), dtype).double()
-    worst = dict((k, 0.0) for k in KINDS)
-    fails = []
-    met = {'group': 0}
-    checked = set()         # (conv, kind): what each conv's checks covered
-
-    def note(kind, what, r_deg, convs=()):
-        for c in convs:
-            checked.add((c, 'bias' if kind.endswith('bias gradient') else kind))
-        r, deg = r_deg
-        worst[kind] = max(worst[kind], r)
-        worst['degenerate bound'] = max(worst['degenerate bound'], deg / DEGENERATE)
-        if not (r <= 1.0):
-            fails.append((kind, what, r))
-        if deg > DEGENERATE:
-            fails.append(('degenerate bound', '%s %s' % (kind, what), deg))
-
-    def grad_op(name):
-        """the gradient operand the consumers of `name` read: view 4 where the step stored it, else rnd(view 3)."""
-        return (P.get(name, 4) if P.has(name, 4) else rnd(P.get(name, 3), dtype)).double()
-
-    def wg(conv, x, dy, k, H, stride=1, pad=None, has_bias=False):
-        S = layer_splits(B, H, H, x.shape[1], dy.shape[1], k)
-        if k != 7 and group_splits(B, H, H, pad64(x.shape[1]), pad64(dy.shape[1]), k * k) > 0:
-            met['group'] += 1
-        note('weight gradient', conv, wgrad_check(grads[conv + '.weight'], x, dy, k, S, stride, pad), (conv,))
-        if has_bias:
-            note('bias gradient', conv, bgrad_check(grads[conv + '.bias'], dy, S), (conv,))
-        else:
-            z = grads[conv + '.bias']
-            worst['zero bias gradient'] = max(worst['zero bias gradient'], float(z.abs().max()))
-            checked.add((conv, 'bias'))
-            if bool((z != 0).any()):
-                fails.append(('zero bias gradient', conv, float(z.abs().max())))
 
     # ---- stem: 7 x 7 stride 2 over the image (rounded to the storage type by the layout converter), K = 7 x 7 x 4 padded to 256
     xs = rnd(img.double(), dtype)
@@ -397,60 +507,18 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
     # The input of skip block k of hourglass i (xin<i>, hg<i>.down<k-1>) also feeds max pool k: Hourglass::bwd routes the pool's
     # gradient back (plus, k = 1, d xin<i+1> from the next stack's forth_conv addend) into poolgrad[k] (net.hip:881-885, stored in the
     # storage type), and skip k's conv1 data gradient adds it as its SECOND addend (Residual::bwd_b, net.hip:760).  res1's output has
-    # no conv reader (pool0 only): nothing to check here.
+    # no conv reader (pool0 only): nothing to check here.  (That the pool routed correctly: tests/bn_exact.py 'pool backward'.)
     skip_k = dict([('xin%d' % i, (i, 1)) for i in range(stacks)] + [('hg%d.down%d' % (i, k), (i, k + 1)) for i in range(stacks) for k in (1, 2, 3)])
     # a pending BatchNorm (masked gradient): the stem and block outputs (xin0 is residual3's); not the pools, merges or xin<i>, i >= 1
     has_bn = lambda n: not ('pool' in n or 'merge' in n or (n.startswith('xin') and n != 'xin0'))
     for p, out, inp, ad in block_sites(stacks):
-        cin = P.get(inp, 0).shape[1]
-        H = P.get(out, 2).shape[2]
-        mid = P.get(out + '.x1', 2).shape[1]
-        xin = v0(inp)
-        x_in = rnd(xin, dtype)
-        t1 = conv_term(x_in, W(p + 'conv1'), pad64(cin), bias(p + 'conv1'))
-        note('conv forward', p + 'conv1', check16(P.get(out + '.x1', 2), t1, dtype), (p + 'conv1',))
-        del t1
-        x1v = sv0(out + '.x1')
-        t2 = conv_term(x1v, W(p + 'conv2'), 9 * pad64(mid), bias(p + 'conv2'))
-        note('conv forward', p + 'conv2', check16(P.get(out + '.x2', 2), t2, dtype), (p + 'conv2',))
-        del t2
-        x2v = sv0(out + '.x2')
-        if ad:      # x3 = conv3(x2) + b3 + adout, adout = rnd(adapter(in) + b_ad): not exposed, one more half ulp
-            short = rounded(conv_term(x_in, W(p + 'adapter'), pad64(cin), bias(p + 'adapter')), dtype)
-        else:       # the identity shortcut: the block input's fp32 value (the epilogue's BNRELU / plain load)
-            short = xin
-        t3 = conv_term(x2v, W(p + 'conv3'), pad64(mid), bias(p + 'conv3'), (short,))
-        note('conv forward', p + 'conv3', check16(P.get(out, 2), t3, dtype), (p + 'conv3',) + ((p + 'adapter',) if ad else ()))
-        del t3, short
-        # inner data gradients: one consumer each, masked by the ReLU of the tensor's own value
-        g3 = grad_op(out)
-        g2 = grad_op(out + '.x2')
-        m2 = (P.get(out + '.x2', 0) > 0).double()
-        note('conv data gradient', p + 'conv3', check16(P.get(out + '.x2', 1), dgrad_term(g3, W(p + 'conv3'), pad64(g3.shape[1])), dtype, m2),
-             (p + 'conv3',))
-        m1 = (P.get(out + '.x1', 0) > 0).double()
-        note('conv data gradient', p + 'conv2', check16(P.get(out + '.x1', 1), dgrad_term(g2, W(p + 'conv2'), 9 * pad64(mid)), dtype, m1),
-             (p + 'conv2',))
-        g1 = grad_op(out + '.x1')
-        wg(p + 'conv3', x2v, g3, 1, H)
-        wg(p + 'conv2', x1v, g2, 3, H)
-        wg(p + 'conv1', x_in, g1, 1, H)
-        if ad:
-            wg(p + 'adapter', x_in, g3, 1, H)
-        # d in = mask * (conv1^T(g1) + add1 [+ add2]) (Residual::bwd_b, net.hip:750-763)
-        if ad:      # add1 = adgrad = rnd(adapter^T(g3)), not exposed; residual1 / residual3 have no other reader of their input
-            adds = (rounded(dgrad_term(g3, W(p + 'adapter'), pad64(g3.shape[1])), dtype),)
-        else:       # add1: the x3 gradient as conv1's epilogue loads it, dz3 (view 4) or the LIN2 value in fp32 (view 3)
-            adds = ((P.get(out, 4) if P.has(out, 4) else P.get(out, 3)).double(),)
-        if inp in skip_k:                                           # add2: the pool's routed gradient
-            adds += (P.get('hg%d.poolgrad%d' % skip_k[inp], 2).double(),)
-        mask = (xin > 0).double() if has_bn(inp) else None
-        note('conv data gradient', inp, check16(P.get(inp, 1), dgrad_term(g1, W(p + 'conv1'), pad64(mid), adds), dtype, mask),
-             (p + 'conv1',) + ((p + 'adapter',) if ad else ()))
-        del adds, mask
-        del xin, x_in, x1v, x2v, g1, g2, g3, m1, m2
+        add2 = P.get('hg%d.poolgrad%d' % skip_k[inp], 2) if inp in skip_k else None          # the pool's routed gradient
+        ck.block(p, out, P, P, inp, True, ad, add2, has_bn(inp))
+        del add2
     # ---- head (Net::forward_pose_body / backward_stack, net.hip:1036-1083)
     Hh = res // 4
+    target = t(inputs.heatmaps_from_pts(pts_np, res=Hh)).cuda()
+    loss_sum = None
     for i in range(stacks):
         lin = 'linear.%d.0' % i
         pv = sv0('post%d' % i)
@@ -466,8 +534,19 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
         heat = conv_term(lv, W(oc), chan, bias(oc))                     # fp32 heat maps (the head kernel), then rnd for heat64
         note('conv forward', oc, check32(outs[i].double(), heat), (oc,))
         note('conv forward', oc + ' (stored)', check16(P.get('heat%d' % i, 2)[:, :16], heat, dtype), (oc,))
-        dheat = P.get('heat%d' % i, 1)[:, :16].double()
+        dh64 = P.get('heat%d' % i, 1)
+        dheat = dh64[:, :16].double()
         wg(oc, lv, dheat, 1, Hh, has_bias=True)
+        # the loss and its gradient, from the returned fp32 heat maps and the oracle's Gaussian maps of the same joints (exact in fp32:
+        # pa_gauss_tab, pose_ops.hip:13-19, is the reference's table)
+        inner_add = P.get('heat%d.in' % i, 2)[:, :16] if i + 1 < stacks else None
+        note('heat gradient', 'heat%d' % i, heat_grad_check(dh64[:, :16], outs[i], target, grad_scale() / (B * 16.0 * Hh * Hh), inner_add, dtype))
+        if bool((dh64[:, 16:] != 0).any()):
+            fails.append(('heat gradient', 'heat%d padded channels' % i, float('inf')))
+        ls, r = loss_check(net._last_losses[i], outs[i], target)
+        note('loss', 'stack %d' % i, (r, 0.0))
+        loss_sum = ls if loss_sum is None else loss_sum + ls                # loss_out_kernel (elementwise.hip:1202-1208): s += v, from 0
+        del dh64, inner_add
         if i + 1 < stacks:
             fc, ic = 'forth_conv.%d' % i, 'in_conv.%d' % i
             ft = conv_term(lv, W(fc), chan, bias(fc), (v0('xin%d' % i),))
@@ -494,6 +573,7 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
             t = oct_
         note('conv data gradient', 'lin%d' % i, check16(P.get('lin%d' % i, 1), t, dtype, lm), (oc,) + ((fc,) if i + 1 < stacks else ()))
         del lm, oct_, t
+    note('loss', 'total', (ratio(loss_total.reshape(1), loss_sum.v.reshape(1), loss_sum.e.reshape(1)), 0.0))
     # coverage: every conv of the net has each kind of check (the stem has no data gradient: its input is the image)
     want = set((c, k) for c in names for k in ('conv forward', 'weight gradient', 'bias') + (('conv data gradient',) if c != 'conv1' else ()))
     if want - checked:
