@@ -1,5 +1,6 @@
 """Exact checks of the ASN agent (csrc/asn.hip) after ONE agent step -- the pose net in eval mode, the agent in train mode, the modes
-of train_agent_sr -- recomputed in float64 from the tensors the engine itself stored (pa_asn_debug_tensor / pa_hg_debug_tensor views
+of train_agent_sr; the first agent step after the bind ('fresh') or one behind pose and agent optimizer steps or eval-mode and
+unfinished agent forwards (tests/exact_history.py) -- recomputed in float64 from the tensors the engine itself stored (pa_asn_debug_tensor / pa_hg_debug_tensor views
 0-4, include/poseadv.h):
   * the 12 residual blocks (in0..4 = residual_skip1-4 / residual_neck, merge0..3 = merge1-4, deep0..2 = deep_merge.0-2) with the per-block
     checks of tests/conv_exact.py (Checker.block) and the per-BatchNorm checks of tests/bn_exact.py (check_bn_site): one definition of
@@ -387,21 +388,25 @@ def _guards(agent):
         'bn_sites must name every BatchNorm of the agent'
 
 
-def run_leg(chan, B, res, seed, log=print, expect=()):
-    """The scale/rotation agent: half hourglass (eval) + agent (train), one loss_and_backward per log_eps, then every check.  Returns
-    ({kind: worst}, failures)."""
+def run_leg(chan, B, res, seed, log=print, expect=(), history='fresh'):
+    """The scale/rotation agent: half hourglass (eval) + agent (train) behind `history` (tests/exact_history.py: 'fresh' = the first agent
+    step after the bind), one loss_and_backward per log_eps, then every check.  Returns ({kind: worst}, failures)."""
     from pose_adv_aug_amd._lib import act_dtype, grad_scale
-    from tests import inputs
-    from tests.test_gpu_net import t
+    from tests import exact_history
     dtype = act_dtype()
     gsc = grad_scale()
     torch.cuda.set_device(0)
     net, agent = _pair(chan, B, res, seed)
     _guards(agent)
-    sd0 = {k: v.clone() for k, v in agent.state_dict().items()}
-    img = t(inputs.images(seed + 100, B, res)).cuda()
-    net.eval(); agent.train()
-    ls, lr = net(img, asn=agent, is_half_hg=True, is_aug=True)
+
+    def backward(out, k):
+        gs_h, gr_h = _targets(seed + 10 + k, out[0], out[1], B)
+        net.zero_grad(); agent.zero_grad()
+        agent.loss_and_backward(gs_h, gr_h)
+    fwd = exact_history.agent_history(net, agent, B, res, seed, history,
+                                      lambda **im: net(im.get('x'), asn=agent, is_half_hg=True, is_aug=True, img4=im.get('img4')), backward)
+    sd0 = {k: v.clone() for k, v in agent.state_dict().items()}          # immediately before the checked step
+    ls, lr = fwd()
     gs_t, gr_t = _targets(seed + 2, ls, lr, B)
     assert bool((gs_t == 0).any()) or bool((gr_t == 0).any()), 'the targets of a leg must hold zeros (the t > 0 branch of the loss)'
     L = Leg(net, agent, sd0, dtype, B)
@@ -410,7 +415,7 @@ def run_leg(chan, B, res, seed, log=print, expect=()):
     Wall = torch.cat([Ws, Wr], 0)
     for eps in (0.0, 1e-7):       # one forward + backward each; the last one (the joint loop's) leaves the trunk's tensors for the checks below
         before = {k: v.clone() for k, v in agent.state_dict().items() if k.endswith('running_mean') or k.endswith('running_var')}
-        ls, lr = net(img, asn=agent, is_half_hg=True, is_aug=True)
+        ls, lr = fwd()
         net.zero_grad(); agent.zero_grad()
         loss = agent.loss_and_backward(gs_t, gr_t, log_eps=eps).clone()
         torch.cuda.synchronize()
@@ -444,27 +449,33 @@ def run_leg(chan, B, res, seed, log=print, expect=()):
     L.note('mode 2 running stats', 'all', sum(BX._mismatch(sd2[k], sd1[k]) for k in before), bit=True)
     L.note('mode 2 logits', 'both', BX._mismatch(ls2, ls) + BX._mismatch(lr2, lr), bit=True)
     L.eval_mode(lambda: agent.forward_features(net))
-    L.report(log, 'chan %d B %d res %d' % (chan, B, res))
+    L.report(log, '%s chan %d B %d res %d' % (history, chan, B, res))
     worst = dict(L.worst); worst.update(L.bworst); worst.update(L.ck.worst)
     return worst, L.fails
 
 
-def run_mask_leg(chan, B, seed, log=print, expect=()):
-    """The occlusion agent (res 256): forward, backward_masks with a seeded gradient, then the trunk checks and the mask head's."""
+def run_mask_leg(chan, B, seed, log=print, expect=(), history='fresh'):
+    """The occlusion agent (res 256) behind `history`: forward, backward_masks with a seeded gradient, then the trunk checks and the mask
+    head's."""
     from pose_adv_aug_amd._lib import act_dtype, grad_scale
-    from tests import inputs
+    from tests import exact_history, inputs
     from tests.test_gpu_net import t
     dtype = act_dtype()
     gsc = grad_scale()
     torch.cuda.set_device(0)
     net, agent = _pair(chan, B, 256, seed, dropout=True)
     _guards(agent)
-    sd0 = {k: v.clone() for k, v in agent.state_dict().items()}
+    seeded = lambda k: t(inputs.rng(seed + k).standard_normal((B, 1, 4, 4)).astype(np.float32)).cuda()
+
+    def backward(out, k):
+        net.zero_grad(); agent.zero_grad()
+        agent.backward_masks(seeded(10 + k))
+    fwd = exact_history.agent_history(net, agent, B, 256, seed, history,
+                                      lambda **im: net(im.get('x'), asn=agent, is_half_hg=True, is_dropout=True, img4=im.get('img4')), backward)
+    sd0 = {k: v.clone() for k, v in agent.state_dict().items()}          # immediately before the checked step
     before = {k: v for k, v in sd0.items() if k.endswith('running_mean') or k.endswith('running_var')}
-    img = t(inputs.images(seed + 100, B, 256)).cuda()
-    net.eval(); agent.train()
-    pm = net(img, asn=agent, is_half_hg=True, is_dropout=True)
-    gy = t(inputs.rng(seed + 2).standard_normal((B, 1, 4, 4)).astype(np.float32)).cuda()
+    pm = fwd()
+    gy = seeded(2)
     net.zero_grad(); agent.zero_grad()
     agent.backward_masks(gy)
     torch.cuda.synchronize()
@@ -481,15 +492,15 @@ def run_mask_leg(chan, B, seed, log=print, expect=()):
     L.trunk(grads, before, expect)
     L.coverage(grads)
     L.eval_mode(lambda: agent.forward_masks(net))
-    L.report(log, 'occlusion chan %d B %d' % (chan, B))
+    L.report(log, 'occlusion %s chan %d B %d' % (history, chan, B))
     worst = dict(L.worst); worst.update(L.bworst); worst.update(L.ck.worst)
     return worst, L.fails
 
 
-if __name__ == '__main__':          # the fp16 leg: tests/test_gpu_asn_exact.py runs this with POSEADV_DTYPE=fp16
+if __name__ == '__main__':          # the fp16 legs: tests/test_gpu_asn_exact.py runs this with POSEADV_DTYPE=fp16
     from pose_adv_aug_amd._lib import lib as _l
     assert _l().pa_dtype() == 1, 'run with POSEADV_DTYPE=fp16'
-    worst, fails = run_leg(*[int(a) for a in sys.argv[1:5]], log=lambda s: print(s, flush=True))
+    worst, fails = run_leg(*[int(a) for a in sys.argv[1:5]], log=lambda s: print(s, flush=True), **BX._child_kw(sys.argv[5:]))
     print('FAILURES %d %s' % (len(fails), fails[:20]))
     print('FP16 ASN EXACT ' + ('PASSED' if not fails else 'FAILED'), flush=True)
     sys.exit(1 if fails else 0)

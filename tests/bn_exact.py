@@ -1,6 +1,8 @@
 """Exact checks of the code that links the convolutions: every BatchNorm (statistics, finalize, running estimates, parameter gradients,
 backward, eval mode), every max pool forward and every upsample-add (forward and backward) of the hourglass net, each recomputed in
-float64 from the tensors the engine itself stored after ONE training step (pa_hg_debug_tensor views 0-4, include/poseadv.h).
+float64 from the tensors the engine itself stored after ONE training step (pa_hg_debug_tensor views 0-4, include/poseadv.h).  That step is
+the first one after the bind ('fresh') or one behind a history of optimizer steps, graph replays, eval-mode and unfinished forwards, entered
+as bench.py enters its timed steps (tests/exact_history.py); parameters and running estimates are those held immediately before it.
 
 What 'bn backward' covers: view 3 applies the finalize's kA / kB / kC to dz and raw in the hook's own fp32 load, so that check pins the
 backward finalize constants (kB, kC carry the backward sums; kA the forward's invstd).  The tensors the data-gradient kernels store for
@@ -18,6 +20,7 @@ dz * (x - mean) * invstd, bn_eval_kernel), with u = 2^-24 and these rules (class
   * an fp32 add / sub / mul / correctly rounded division of two quantities known to within e_a, e_b adds |a| e_b + |b| e_a + e_a e_b of
     propagated error and u (|result| + propagated error) of rounding; fmaf rounds once;
   * rsqrtf (v_rsq_f32) is within 1 ulp = 2u: its bound is the exact interval [rsqrt(t + e), rsqrt(t - e)] widened by 2u;
+    sqrtf (the optimizer, tests/optim_exact.py) by the same rule: [sqrt(t - e), sqrt(t + e)] widened by 2u;
   * expf / logf (the agent's softmax and KL loss, tests/asn_exact.py): the exact interval of the function over its argument's interval,
     widened by 2 ulp = 4u of the result -- an ASSUMPTION (see tests/asn_exact.py);
   * a per-channel sum of n fp32 values computed by any tree in which no value passes through more than D additions is within
@@ -121,6 +124,12 @@ class E(object):
         lo = (self.v + self.e).rsqrt()
         hi = (self.v - self.e).clamp_min(1e-300).rsqrt()
         v = self.v.rsqrt()
+        return E(v, torch.maximum(v - lo, hi - v) + 2 * U * hi)
+
+    def sqrt(self):                     # sqrtf of a quantity >= 0 (the optimizer, tests/optim_exact.py): the rule of rsqrt
+        lo = (self.v - self.e).clamp_min(0).sqrt()
+        hi = (self.v + self.e).sqrt()
+        v = self.v.sqrt()
         return E(v, torch.maximum(v - lo, hi - v) + 2 * U * hi)
 
 
@@ -392,29 +401,20 @@ def check_bn_eval_site(P, pre, name, sd, note):
                                           sd[pre + '.running_mean'], sd[pre + '.running_var']))
 
 
-def run_leg(stacks, chan, B, res, seed, log=print, stored_expected=('.x2', '')):
-    """One training step (loss_and_backward, default multi-stream mode, as bench.py runs it), then every check.  Returns
-    {kind: worst error / bound (bit-exact kinds: differing elements)} and the list of failures.  stored_expected: the inner tensors
-    ('.x2': dz2) and block outputs ('': dz3) of which at least one block must have stored its BatchNorm-backward gradient."""
+def run_leg(stacks, chan, B, res, seed, log=print, stored_expected=('.x2', ''), history='fresh'):
+    """One training step (loss_and_backward, default multi-stream mode, as bench.py runs it) behind `history` (tests/exact_history.py:
+    'fresh' = the first step after the bind), then every check.  Returns {kind: worst error / bound (bit-exact kinds: differing
+    elements)} and the list of failures.  stored_expected: the inner tensors ('.x2': dz2) and block outputs ('': dz3) of which at
+    least one block must have stored its BatchNorm-backward gradient."""
     from pose_adv_aug_amd._lib import act_dtype
-    from tests import inputs
-    from tests.test_gpu_net import t, _hg_pair
+    from tests import exact_history
     dtype = act_dtype()
-    torch.cuda.set_device(0)
-    ref, net = _hg_pair(stacks, chan, B, res, seed=seed)
-    del ref
     sites = bn_sites(stacks)
+    S = exact_history.pose_step(stacks, chan, B, res, seed, history)
+    net, before, img, grads = S.net, S.before, S.img, S.grads
     sd = net.state_dict()
     assert sorted(p for p, _ in sites) == sorted(k[:-len('.running_mean')] for k in sd if k.endswith('.running_mean')), \
         'bn_sites must name every BatchNorm of the net'
-    before = {k: v.clone() for k, v in sd.items() if k.endswith('running_mean') or k.endswith('running_var')}
-    img = t(inputs.images(seed + 100, B, res)).cuda()
-    pts = t(inputs.heat_pts(seed + 101, B, res=res // 4)).cuda()
-    net.train()
-    net.loss_and_backward(img, pts)
-    torch.cuda.synchronize()
-    grads = {n: g.clone() for n, g in net.named_grads()}
-    sd = net.state_dict()
     P = Probe(net)
     worst = dict((k, 0.0) for k in KINDS)
     fails = []
@@ -457,18 +457,23 @@ def run_leg(stacks, chan, B, res, seed, log=print, stored_expected=('.x2', '')):
     for pre, name in sites:
         check_bn_eval_site(P, pre, name, sd, note)
     if os.environ.get('POSEADV_TEST_VERBOSE'):
-        log('bn_exact %s stacks %d chan %d B %d res %d: worst error / bound (bit-exact kinds: differing elements): %s'
-            % (torch.float16 if dtype == torch.float16 else 'bf16', stacks, chan, B, res,
+        log('bn_exact %s %s stacks %d chan %d B %d res %d: worst error / bound (bit-exact kinds: differing elements): %s'
+            % ('fp16' if dtype == torch.float16 else 'bf16', history, stacks, chan, B, res,
                ', '.join('%s %.3g' % (k, worst[k]) for k in KINDS)) + '; stored dz2 / dz3 checked in %d / %d blocks'
             % (stored['.x2'], stored['']) + '; %d tied pool windows' % ties)
     return worst, fails
 
 
-if __name__ == '__main__':          # the fp16 leg: tests/test_gpu_bn_exact.py runs this with POSEADV_DTYPE=fp16
+def _child_kw(args):
+    """the optional sixth argument of the child-process entry points: the history"""
+    return {'history': args[0]} if args else {}
+
+
+if __name__ == '__main__':          # the fp16 legs: tests/test_gpu_bn_exact.py runs this with POSEADV_DTYPE=fp16
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pose_adv_aug_amd._lib import lib as _l
     assert _l().pa_dtype() == 1, 'run with POSEADV_DTYPE=fp16'
-    worst, fails = run_leg(*[int(a) for a in sys.argv[1:6]], log=lambda s: print(s, flush=True))
+    worst, fails = run_leg(*[int(a) for a in sys.argv[1:6]], log=lambda s: print(s, flush=True), **_child_kw(sys.argv[6:]))
     print('FAILURES %d %s' % (len(fails), fails[:20]))
     print('FP16 BN EXACT ' + ('PASSED' if not fails else 'FAILED'), flush=True)
     sys.exit(1 if fails else 0)

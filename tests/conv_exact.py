@@ -2,7 +2,9 @@
 residual block; every block input as mask * (conv1^T + the epilogue's one or two addends), the skip blocks' inputs with the pool's routed
 gradient as the second addend; post, lin and in_conv's gradient of the heat maps), every weight gradient and every bias gradient, each
 recomputed in float64 from the operands the engine itself used in ONE training step (pa_hg_debug_tensor views 0-4 and the head / pool
-buffers it names, include/poseadv.h), and the same bounds over the standalone shapes of tests/test_gpu_conv.py.
+buffers it names, include/poseadv.h), and the same bounds over the standalone shapes of tests/test_gpu_conv.py.  That step is the first
+one after the bind ('fresh') or one behind a history of optimizer steps (repacked weight copies), graph replays, eval-mode and unfinished
+forwards, entered as bench.py enters its timed steps (tests/exact_history.py); the weights are those held immediately before it.
 
 Why this is exact up to a derived bound.  Every conv prologue computes its operand in fp32 and rounds it ONCE to the storage type: the
 BatchNorm+ReLU value fmaxf(fmaf(k0, raw, k1), 0) (view 0) or the BatchNorm-backward gradient fmaf(k0, p, fmaf(k1, q, k2)) (view 3); where
@@ -467,29 +469,20 @@ def heat_grad_check(got, heat, target, gscale, add, dtype):
     return check16(got, Term(g.v, g.e, mag), dtype)
 
 
-def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
-    """One training step (loss_and_backward, default multi-stream mode), then every check.  Returns {kind: worst error / bound} and the
-    failures.  expect: weight-gradient split kinds this leg must meet ('group': a layer whose split count is the grouped kernel's)."""
+def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
+    """One training step (loss_and_backward, default multi-stream mode) behind `history` (tests/exact_history.py: 'fresh' = the first
+    step after the bind), then every check.  Returns {kind: worst error / bound} and the failures.  expect: weight-gradient split
+    kinds this leg must meet ('group': a layer whose split count is the grouped kernel's)."""
     from pose_adv_aug_amd._lib import act_dtype, grad_scale
-    from tests import inputs
+    from tests import exact_history, inputs
     from tests.bn_exact import Probe
-    from tests.test_gpu_net import t, _hg_pair
+    from tests.test_gpu_net import t
     dtype = act_dtype()
-    torch.cuda.set_device(0)
-    ref, net = _hg_pair(stacks, chan, B, res, seed=seed)
-    del ref
-    sd0 = {k: v.clone() for k, v in net.state_dict().items()}          # before the step
+    S = exact_history.pose_step(stacks, chan, B, res, seed, history)
+    net, sd0, img, pts_np, outs, loss_total, grads = S.net, S.sd0, S.img, S.pts_np, S.outs, S.loss_total, S.grads
     names = conv_names(stacks)
     assert sorted(names) == sorted(k[:-len('.weight')] for k in sd0 if k.endswith('.weight') and sd0[k].dim() == 4), \
         'conv_names must name every conv of the net'
-    img = t(inputs.images(seed + 100, B, res)).cuda()
-    pts_np = inputs.heat_pts(seed + 101, B, res=res // 4)
-    pts = t(pts_np).cuda()
-    net.train()
-    loss_total, outs = net.loss_and_backward(img, pts, want_outputs=True)
-    loss_total = loss_total.clone()
-    torch.cuda.synchronize()
-    grads = {n: g.clone() for n, g in net.named_grads()}
     P = Probe(net)
     ck = Checker(sd0, grads, dtype, B)
     W, bias, note, wg, worst, fails, met, checked = ck.W, ck.bias, ck.note, ck.wg, ck.worst, ck.fails, ck.met, ck.checked
@@ -543,7 +536,7 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
         note('heat gradient', 'heat%d' % i, heat_grad_check(dh64[:, :16], outs[i], target, grad_scale() / (B * 16.0 * Hh * Hh), inner_add, dtype))
         if bool((dh64[:, 16:] != 0).any()):
             fails.append(('heat gradient', 'heat%d padded channels' % i, float('inf')))
-        ls, r = loss_check(net._last_losses[i], outs[i], target)
+        ls, r = loss_check(S.losses[i], outs[i], target)
         note('loss', 'stack %d' % i, (r, 0.0))
         loss_sum = ls if loss_sum is None else loss_sum + ls                # loss_out_kernel (elementwise.hip:1202-1208): s += v, from 0
         del dh64, inner_add
@@ -584,17 +577,18 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=()):
         if not met[kind]:
             fails.append(('coverage', 'no layer of this leg has a shape of the %s weight-gradient split' % kind, 0))
     if os.environ.get('POSEADV_TEST_VERBOSE'):
-        log('conv_exact %s stacks %d chan %d B %d res %d: worst error / bound: %s; %d convs, %d with grouped splits'
-            % ('fp16' if dtype == torch.float16 else 'bf16', stacks, chan, B, res,
+        log('conv_exact %s %s stacks %d chan %d B %d res %d: worst error / bound: %s; %d convs, %d with grouped splits'
+            % ('fp16' if dtype == torch.float16 else 'bf16', history, stacks, chan, B, res,
                ', '.join('%s %.3g' % (k, worst[k]) for k in KINDS), len(set(c for c, _ in checked)), met['group']))
     return worst, fails
 
 
-if __name__ == '__main__':          # the fp16 leg: tests/test_gpu_conv_exact.py runs this with POSEADV_DTYPE=fp16
+if __name__ == '__main__':          # the fp16 legs: tests/test_gpu_conv_exact.py runs this with POSEADV_DTYPE=fp16
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pose_adv_aug_amd._lib import lib as _l
     assert _l().pa_dtype() == 1, 'run with POSEADV_DTYPE=fp16'
-    worst, fails = run_leg(*[int(a) for a in sys.argv[1:6]], log=lambda s: print(s, flush=True))
+    from tests.bn_exact import _child_kw
+    worst, fails = run_leg(*[int(a) for a in sys.argv[1:6]], log=lambda s: print(s, flush=True), **_child_kw(sys.argv[6:]))
     print('FAILURES %d %s' % (len(fails), fails[:20]))
     print('FP16 CONV EXACT ' + ('PASSED' if not fails else 'FAILED'), flush=True)
     sys.exit(1 if fails else 0)

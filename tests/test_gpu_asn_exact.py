@@ -46,6 +46,26 @@ def test_occlusion_agent_is_exact_at_chan_128():
     _ok(A.run_mask_leg(128, 2, 55))
 
 
+# ---- a history in front of the checked agent step (tests/exact_history.py), at the smallest res the agent accepts
+@pytest.mark.parametrize('history', ('warm', 'after_eval'))
+def test_agent_is_exact_after_a_history(history):
+    _ok(A.run_leg(128, 2, 256, 57, history=history))
+
+
+@pytest.mark.parametrize('history', ('warm', 'after_eval'))
+def test_occlusion_agent_is_exact_after_a_history(history):
+    _ok(A.run_mask_leg(128, 2, 58, history=history))
+
+
+def test_agent_is_exact_after_warm_steps_in_the_fp16_build():
+    env = dict(os.environ, POSEADV_DTYPE='fp16')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'asn_exact.py'), '128', '2', '256', '59', 'warm'], env=env,
+                       capture_output=True, text=True, timeout=900)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print(r.stdout)
+    assert r.returncode == 0 and 'FP16 ASN EXACT PASSED' in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
 def test_agent_is_exact_in_the_fp16_build():
     env = dict(os.environ, POSEADV_DTYPE='fp16')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'asn_exact.py'), '256', '3', '384', '56'], env=env,

@@ -40,6 +40,34 @@ def test_every_bn_pool_and_merge_is_exact_on_tiny_maps():
     _leg(2, 128, 2, 128, 33, stored_expected=('.x2',))
 
 
+# ---- a history in front of the checked step (tests/exact_history.py).  State does not depend on the map size: the smallest shapes
+# that still reach every kernel family.
+@pytest.mark.parametrize('history', ('warm', 'graph', 'phased', 'after_eval'))
+def test_every_bn_pool_and_merge_is_exact_after_a_history_on_tiny_maps(history):
+    """The tiny-maps size (chan 128, 128 x 128, B 2) with steps before the checked one, which runs through the benchmark's path."""
+    _leg(2, 128, 2, 128, 35, stored_expected=('.x2',), history=history)
+
+
+@pytest.mark.parametrize('history', ('warm', 'graph', 'after_half'))
+def test_every_bn_pool_and_merge_is_exact_after_a_history_at_256(history):
+    """chan 128, B 2, 256 x 256: 64 x 64 maps (the tile kernels, the grouped weight-gradient kernel).  'after_half' runs here and not on
+    the tiny maps: the agent it needs accepts no res below 256."""
+    _leg(2, 128, 2, 256, 36, history=history)
+
+
+def _fp16_child(args):
+    env = dict(os.environ, POSEADV_DTYPE='fp16')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'bn_exact.py')] + args, env=env, capture_output=True, text=True, timeout=900)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print(r.stdout)
+    assert r.returncode == 0 and 'FP16 BN EXACT PASSED' in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+def test_every_bn_pool_and_merge_is_exact_after_warm_steps_in_the_fp16_build():
+    """The IEEE-half library, 'warm' at chan 128, B 2, 256 x 256, in a child process."""
+    _fp16_child(['2', '128', '2', '256', '37', 'warm'])
+
+
 def test_every_bn_pool_and_merge_is_exact_in_the_fp16_build():
     """The IEEE-half library on the configs[4] geometry, in a child process (one storage type per process)."""
     env = dict(os.environ, POSEADV_DTYPE='fp16')

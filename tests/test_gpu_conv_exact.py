@@ -48,6 +48,32 @@ def test_every_conv_is_exact_on_tiny_maps():
     _leg(2, 128, 2, 128, 43)
 
 
+# ---- a history in front of the checked step (tests/exact_history.py)
+@pytest.mark.parametrize('history', ('warm', 'graph', 'phased', 'after_eval'))
+def test_every_conv_is_exact_after_a_history_on_tiny_maps(history):
+    """The tiny-maps size with steps before the checked one: the weight copies the convs read were repacked by the optimizer steps
+    (Checker.W rounds the current fp32 parameters), the loss accumulators were used and cleared by earlier forward passes."""
+    _leg(2, 128, 2, 128, 45, history=history)
+
+
+@pytest.mark.parametrize('history', ('warm', 'graph', 'after_half'))
+def test_every_conv_is_exact_after_a_history_at_256(history):
+    """chan 128, B 2, 256 x 256: the 64 x 64 maps give 2 * 8 * 4 = 64 tiles of 8 x 16 (>= 48), so the grouped weight-gradient kernel
+    takes the 3 x 3 layers there ('group', from the split mirror), beside the tile kernels.  'after_half' runs here: the agent accepts
+    no res below 256."""
+    _leg(2, 128, 2, 256, 46, expect=('group',), history=history)
+
+
+def test_every_conv_is_exact_after_warm_steps_in_the_fp16_build():
+    """The IEEE-half library, 'warm' at chan 128, B 2, 256 x 256, in a child process."""
+    env = dict(os.environ, POSEADV_DTYPE='fp16')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'conv_exact.py'), '2', '128', '2', '256', '47', 'warm'], env=env,
+                       capture_output=True, text=True, timeout=900)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print(r.stdout)
+    assert r.returncode == 0 and 'FP16 CONV EXACT PASSED' in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
 def test_every_conv_is_exact_in_the_fp16_build():
     """The IEEE-half library on the configs[4] geometry, in a child process (one storage type per process)."""
     env = dict(os.environ, POSEADV_DTYPE='fp16')
