@@ -107,6 +107,51 @@ int pa_crop_design_bytes(int B, int Hs, int Ws, int res, double* out_host);
 int pa_crop(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const double* params, int B, int res, void* workspace,
             void* out4, float* outf, uint8_t* out8, void* stream);
 
+/* JPEG decode split between host and device (the reference decodes on the host inside its DataLoader workers: utils/imutils.py:38-41
+ * over data/mpii_for_mpii.py:97): the serial Huffman stage runs on the host, everything after the coefficients (dequantisation,
+ * 8x8 inverse DCT, chroma upsampling, colour conversion, padding) on the device, byte-exact with libjpeg's integer pipeline
+ * (jidctint / jdsample "fancy" / jdcolor) and therefore with Pillow's Image.open(f).convert('RGB').
+ *
+ * Supported files: SOF0 / SOF1 (8-bit, Huffman), ONE interleaved scan with all components (or the single component of a grayscale
+ * file), chroma components 1x1 with luma 1x1, 2x1 or 2x2, and a colour space that libjpeg resolves to YCbCr or grayscale (a JFIF
+ * marker; or Adobe transform 1; or neither marker and component ids that are not 'R','G','B').  Everything else that is a
+ * well-formed JPEG -- progressive or arithmetic coding, 12-bit samples, several scans, CMYK / YCCK / RGB, other sampling factors,
+ * a subsampled component narrower than 3 samples (libjpeg switches to its plain upsampler there) -- returns PA_JPEG_UNSUPPORTED;
+ * corrupt or truncated input returns PA_JPEG_CORRUPT, a coefficient buffer that is too small PA_JPEG_CAPACITY, both with a message.
+ *
+ * The two *_host functions are pure host code (no HIP call, no global state, re-entrant from many threads, usable without a GPU).
+ * pa_jpeg_info_host parses the markers up to SOS and fills the descriptor; pa_jpeg_entropy_host does the same parse and then
+ * decodes the scan into coef_host (never reading past data_host + n, never writing past capacity_elems): per component the blocks
+ * in raster order over its MCU-padded block grid (3 components: mcus_w * h x mcus_h * v blocks; 1 component: ceil(W/8) x ceil(H/8)),
+ * 64 int16 per block in natural (row-major) order, NOT dequantised, DC prediction resolved. */
+#define PA_JPEG_UNSUPPORTED 19024
+#define PA_JPEG_CORRUPT 19025
+#define PA_JPEG_CAPACITY 19026
+typedef struct pa_jpeg_comp {
+    int32_t h, v;              /* sampling factors (1x1 for a single-component file, whatever its header says) */
+    int32_t bw, bh;            /* block grid of the coefficient plane */
+    int64_t offset;            /* of the plane inside the image's coefficients, in int16 elements */
+} pa_jpeg_comp;
+typedef struct pa_jpeg_desc {
+    int32_t width, height;
+    int32_t ncomp;             /* 1 or 3; 0 = "not decoded here" for pa_jpeg_decode */
+    int32_t restart_interval;  /* in MCUs, 0 = none */
+    int64_t total_elems;       /* int16 elements of all planes */
+    pa_jpeg_comp comp[3];
+    uint16_t quant[3][64];     /* per COMPONENT, natural order */
+} pa_jpeg_desc;
+int pa_jpeg_info_host(const uint8_t* data_host, size_t n, pa_jpeg_desc* desc_host);
+int pa_jpeg_entropy_host(const uint8_t* data_host, size_t n, int16_t* coef_host, size_t capacity_elems, pa_jpeg_desc* desc_host);
+/* The device half for a batch: coef (int16), descs [B], coef_base int64 [B] (image b's offset into coef, a multiple of 8 elements)
+ * are DEVICE pointers; frames: uint8 [B][Hs][Ws][3] top-left aligned, zero outside each image, sizes: int32 [B][2] = (w, h) --
+ * what pa_crop consumes.  An entry with ncomp == 0 (and any entry whose descriptor is not one the host functions produce, or does not
+ * fit Hs x Ws) gets an all-zero frame and its sizes row is left untouched: the caller fills both in.  Two launches: (a) dequantise +
+ * inverse DCT + range limit into uint8 component planes inside `workspace` (pa_jpeg_workspace_bytes() bytes, no initialisation
+ * needed), (b) upsampling + colour conversion + padding into frames. */
+size_t pa_jpeg_workspace_bytes(int B, int Hs, int Ws);
+int pa_jpeg_decode(const int16_t* coef, const pa_jpeg_desc* descs, const int64_t* coef_base, int B, int Hs, int Ws, void* workspace,
+                   uint8_t* frames, int32_t* sizes, void* stream);
+
 /* Validation with flip test-time augmentation (stack-hg.py:222-230).
  * pa_flip_lr_nhwc4: mirror the bf16 NHWC4 network input along W (img.numpy()[:, :, :, ::-1], :223).
  * pa_flip_tta_merge: merged = (out + shuffle_channels_for_horizontal_flipping(flip_channels(out_flipped))) / 2

@@ -79,6 +79,10 @@ _PROTOS = {
     'pa_crop_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'pa_crop_design_bytes': (_i, [_i, _i, _i, _i, C.POINTER(C.c_double)]),
     'pa_crop': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'pa_jpeg_info_host': (_i, [_vp, _sz, _vp]),
+    'pa_jpeg_entropy_host': (_i, [_vp, _sz, _vp, _sz, _vp]),
+    'pa_jpeg_workspace_bytes': (_sz, [_i, _i, _i]),
+    'pa_jpeg_decode': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'pa_flip_lr_nhwc4': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'pa_flip_tta_merge': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'pa_sample_aug': (_i, [_vp, _vp, _vp, _i, _u64, _u64, _i, _vp, _vp]),

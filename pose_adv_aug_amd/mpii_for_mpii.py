@@ -18,6 +18,7 @@ from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
 import numpy as np
 import torch
 
+from . import _lib
 from .data import DeviceBatch
 
 
@@ -79,6 +80,30 @@ class FrameSlots(object):
 
     def close(self):
         self.pool.shutdown(wait=False, cancel_futures=True)
+
+
+class CoefSlots(object):
+    """`depth` page-locked host staging sets of the device-decode feed, handed out through a free list: the int16 coefficients of one
+    batch (grown to the largest batch seen), its descriptors and its per-image coefficient offsets."""
+
+    def __init__(self, depth, batch_size):
+        from .pylib import Jpeg
+        self.pin = torch.cuda.is_available()
+        self.slots = [{'coef': self._host(1 << 16, torch.int16), 'descs': self._host(batch_size * Jpeg.DESC_BYTES, torch.uint8),
+                       'base': self._host(batch_size, torch.int64)} for _ in range(depth)]
+        self.free = queue.Queue()
+        for k in range(depth):
+            self.free.put(k)
+
+    def _host(self, n, dtype):
+        t = torch.empty(n, dtype=dtype)
+        return t.pin_memory() if self.pin else t
+
+    def coef(self, k, elems):
+        """slot k's coefficient buffer with room for `elems` (sized from the descriptors of the batch it is about to hold)"""
+        if self.slots[k]['coef'].numel() < elems:
+            self.slots[k]['coef'] = self._host(int(elems * 1.25), torch.int16)
+        return self.slots[k]['coef']
 
 
 class MPII(object):
@@ -152,7 +177,13 @@ class MPII(object):
         caller trains on the current one -- a few hundred images/s.
         decoder='process': the reference's DataLoader workers (stack-hg.py:75 num_workers) at the engine's rate: `workers`
         forked processes decode straight into page-locked frame slots shared with this process, `prefetch` batches are
-        assembled concurrently and copied to the device on their own stream."""
+        assembled concurrently and copied to the device on their own stream.
+        decoder='device': only the Huffman stage of the JPEG decode runs on the host (pa_jpeg_entropy_host from `workers` threads:
+        C++ with the GIL released, no fork, no shared mapping) into page-locked coefficient slots; the coefficients are copied to
+        the device on the copy stream and pa_jpeg_decode (inverse DCT, upsampling, colour, padding) writes the same padded frames
+        there, byte for byte.  A file outside the decoder's set (progressive, CMYK, ...: include/poseadv.h) is decoded with PIL
+        as in the other feeds and copied into its frame behind the kernel; feed.fallbacks counts them.
+        Any other value of `decoder` selects 'thread'.  feed.decoder names the path that runs."""
         from .data import BatchFeed
         n = len(self)
         nb_all = n // batch_size if drop_last else (n + batch_size - 1) // batch_size
@@ -203,9 +234,42 @@ class MPII(object):
                         except Exception:
                             pass
 
+        def one_pass_device():
+            chunks = chunks_of_pass()
+            slots = self._coef_slots(batch_size, prefetch)
+            if getattr(self, '_decode_stream', None) is None:      # one per dataset; the assembler threads share it: every decode call owns its workspace (pylib/Jpeg.py)
+                self._decode_stream = torch.cuda.Stream()
+            copy_stream = self._decode_stream
+            with ThreadPoolExecutor(max_workers=max(1, workers)) as pool, ThreadPoolExecutor(max_workers=max(1, prefetch)) as assemblers:
+                futs = [assemblers.submit(self._assemble_device, c, slots, copy_stream, pool, feed) for c in chunks[:prefetch]]
+                released = 0
+                try:
+                    for k in range(len(chunks)):
+                        batch, ev, slot = futs[k].result()
+                        torch.cuda.current_stream().wait_event(ev)
+                        batch.record_stream(torch.cuda.current_stream())
+                        if k + prefetch < len(chunks):
+                            futs.append(assemblers.submit(self._assemble_device, chunks[k + prefetch], slots, copy_stream, pool, feed))
+                        yield batch
+                        ev.synchronize()                      # the coefficient upload is long done: the slot may be refilled
+                        slots.free.put(slot)
+                        released = k + 1
+                finally:
+                    for f in futs[released:]:
+                        try:
+                            _, ev, slot = f.result()
+                            ev.synchronize()
+                            slots.free.put(slot)
+                        except Exception:
+                            pass
+
         total = sum(min(batch_size, n - k * batch_size) for k in (range(rank, nb_all, world) if world > 1 else range(nb_all)))
-        return BatchFeed(nb, total if world == 1 else min(total, nb * batch_size), one_pass_processes if decoder == 'process' else one_pass_threads,
-                         dataset_size=n)
+        make_iter = {'process': one_pass_processes, 'device': one_pass_device}.get(decoder, one_pass_threads)
+        feed = BatchFeed(nb, total if world == 1 else min(total, nb * batch_size), make_iter, dataset_size=n)
+        feed.decoder = decoder if decoder in ('process', 'device') else 'thread'
+        feed.fallbacks = 0                  # decoder='device': images so far that were decoded with PIL instead
+        feed.lock = threading.Lock()
+        return feed
 
     # ---- process-pool path
     MAX_FRAME = (1088, 1920)                  # slot size: MPII images are at most 1920 x 1080
@@ -235,5 +299,86 @@ class MPII(object):
                                 np.stack([r[1] for r in recs]), np.asarray([r[4] for r in recs]), sizes=sizes, index=list(indices))
             ev = torch.cuda.Event()
             ev.record(copy_stream)
+        batch.ready = ev
+        return batch, ev, slot
+
+    # ---- device-decode path
+    def _coef_slots(self, batch_size, prefetch):
+        key = (batch_size, prefetch)
+        if getattr(self, '_cslots_key', None) != key:
+            self._cslots = CoefSlots(prefetch + 2, batch_size)
+            self._cslots_key = key
+        return self._cslots
+
+    @staticmethod
+    def _read_and_describe(path):
+        """a decode thread, first visit: the file's bytes and its descriptor (header parse only)"""
+        from .pylib import Jpeg
+        with open(path, 'rb') as f:
+            data = f.read()
+        rc, desc = Jpeg.jpeg_info(data)
+        if rc == Jpeg.PA_JPEG_UNSUPPORTED or (rc != 0 and data[:2] != b'\xff\xd8'):       # a good file of another kind: PIL's turn
+            return data, None, MPII.load_image(path)
+        if rc != 0:
+            raise _lib.PoseAdvError('%s: %s' % (path, Jpeg.last_error()))
+        return data, desc, None
+
+    @staticmethod
+    def _entropy_into(args):
+        """a decode thread, second visit: Huffman-decode into the image's share of the page-locked slot"""
+        from .pylib import Jpeg
+        path, data, coef = args
+        rc, desc = Jpeg.jpeg_entropy(data, coef)
+        if rc != 0:
+            raise _lib.PoseAdvError('%s: %s' % (path, Jpeg.last_error()))
+        return desc
+
+    def _assemble_device(self, indices, slots, copy_stream, pool, feed):
+        """one batch: file bytes + descriptors -> entropy decode into a free coefficient slot -> asynchronous upload and
+        pa_jpeg_decode on `copy_stream` (-> PIL pixels of the files the decoder does not take, behind the kernel)"""
+        import ctypes
+        from .pylib import Jpeg
+        recs = [self.record(i) for i in indices]
+        B = len(recs)
+        first = list(pool.map(self._read_and_describe, [r[0] for r in recs]))
+        sizes = np.asarray([(d.width, d.height) if d is not None else (im.shape[1], im.shape[0]) for _, d, im in first], dtype=np.int32)
+        Hs, Ws = int(sizes[:, 1].max()), int(sizes[:, 0].max())
+        elems = [int(d.total_elems) if d is not None else 0 for _, d, _ in first]          # multiples of 64: every base is 16-byte aligned
+        base = np.concatenate([[0], np.cumsum(elems)]).astype(np.int64)
+        total = max(64, int(base[-1]))
+        slot = slots.free.get()
+        try:
+            coef = slots.coef(slot, total)
+            live = [b for b in range(B) if first[b][1] is not None]
+            descs = list(pool.map(self._entropy_into, [(recs[b][0], first[b][0], coef[int(base[b]):int(base[b + 1])]) for b in live]))
+            hd, hb = slots.slots[slot]['descs'], slots.slots[slot]['base']
+            hd[:B * Jpeg.DESC_BYTES].zero_()                                                  # ncomp == 0: not decoded on the device
+            for b, d in zip(live, descs):
+                ctypes.memmove(hd.data_ptr() + b * Jpeg.DESC_BYTES, ctypes.addressof(d), Jpeg.DESC_BYTES)
+            hb[:B] = torch.from_numpy(base[:B])
+            dev = torch.device('cuda', torch.cuda.current_device())
+            with torch.cuda.stream(copy_stream):
+                dcoef = coef[:total].to(dev, non_blocking=slots.pin)
+                ddesc = hd[:B * Jpeg.DESC_BYTES].to(dev, non_blocking=slots.pin)
+                dbase = hb[:B].to(dev, non_blocking=slots.pin)
+                frames, dsizes = Jpeg.jpeg_decode_batch(dcoef, ddesc, dbase, Hs, Ws, stream=copy_stream)
+                for b in range(B):
+                    if first[b][1] is None:
+                        im = first[b][2]
+                        frames[b, :im.shape[0], :im.shape[1]].copy_(torch.from_numpy(im))
+                        dsizes[b].copy_(torch.from_numpy(sizes[b]))
+                batch = DeviceBatch(frames, np.stack([r[2] for r in recs]), np.asarray([r[3] for r in recs]),
+                                    np.stack([r[1] for r in recs]), np.asarray([r[4] for r in recs]), sizes=sizes, index=list(indices))
+                batch.sizes = dsizes                     # (w, h) as the decode kernel wrote them: the same numbers as `sizes`
+                ev = torch.cuda.Event()
+                ev.record(copy_stream)
+        except BaseException:
+            if torch.cuda.is_available():
+                copy_stream.synchronize()            # an upload already enqueued may still read the slot's page-locked buffers
+            slots.free.put(slot)
+            raise
+        if len(live) < B:
+            with feed.lock:
+                feed.fallbacks += B - len(live)
         batch.ready = ev
         return batch, ev, slot

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Row f2 end to end: MPII-format JSON + JPEG files -> host decode (thread / process pool) -> padded uint8 frames on the
 device -> device augmentation -> training step.  Writes N synthetic 1280x720 JPEGs and an annotation file to a temp
-directory, then reports (a) decoded images/sec of the feeder alone for several worker counts and (b) images/sec of
-stack_hg.train over that feed beside the engine's rate on resident frames.
+directory, then reports (a) decoded images/sec of the feeder alone for several decoders and worker counts -- 'device' is the
+feed whose host threads only Huffman-decode and whose pixels come from pa_jpeg_decode -- and (b) images/sec of stack_hg.train
+over the process feed and over the device feed beside the engine's rate on resident frames.
 
     python tools/bench_feed.py [N=240]"""
 import json
@@ -47,27 +48,32 @@ def main():
     path = make_dataset(root, n)
     ds = MPII(path, root, is_train=True, log=lambda m: None)
     print('host: %d cores (%s)' % (os.cpu_count(), open('/proc/cpuinfo').read().split('model name')[1].split('\n')[0].strip(': \t')))
-    for decoder, workers in (('thread', 8), ('thread', 32), ('process', 32), ('process', 64), ('process', 96)):
+    rows = (('thread', 8), ('thread', 32), ('process', 16), ('process', 32), ('process', 64), ('process', 96), ('device', 8), ('device', 16))
+    for decoder, workers in rows:
         feed = ds.batches(24, shuffle=False, drop_last=True, workers=workers, decoder=decoder)
-        if decoder == 'process':
-            for b in feed:                                   # first pass forks the pool and page-locks the slots
+        if decoder in ('process', 'device'):
+            for b in feed:                                   # first pass forks the pool and page-locks the slots / sizes the coefficient slots
                 pass
         t0 = time.perf_counter(); cnt = 0
         for b in feed:
             cnt += b.B
         torch.cuda.synchronize()
-        print('feeder alone   decoder=%-7s workers=%2d : %7.1f img/s (decode + pad + H2D of %d images)' % (decoder, workers, cnt / (time.perf_counter() - t0), cnt))
+        print('feeder alone   decoder=%-7s workers=%2d : %7.1f img/s (decode + pad + H2D of %d images)%s' % (decoder, workers, cnt / (time.perf_counter() - t0), cnt,
+              '  fallbacks: %d' % feed.fallbacks if decoder == 'device' else ''))
     net = create_hg(2, 1, 16, 256, default_batch=24); net.reset_parameters(seed=0)
     opt_ = RMSprop(net, lr=2.5e-4)
     aug = Augmenter(seed=1)
     opt = types.SimpleNamespace(print_freq=10 ** 9)
-    feed = ds.batches(24, shuffle=True, drop_last=True, workers=64, decoder='process')
-    print('frame slots page-locked:', ds._frame_slots(24, 64, 6).pinned)
-    stack_hg.train(feed, net, opt_, aug, 0, opt, log=lambda m: None)                   # warm-up pass (pools, kernels)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    stack_hg.train(feed, net, opt_, aug, 1, opt, log=lambda m: None)
-    torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print('stack_hg.train over MPII.batches (64 forked decode workers, 6 batches in flight): %.1f img/s fed (%d images, %.2f s)' % (feed.num_samples / dt, feed.num_samples, dt))
+    legs = (('device', 16), ('process', 16), ('process', 64))          # the last leg's batches are the resident ones below, as before
+    for decoder, workers in legs:
+        feed = ds.batches(24, shuffle=True, drop_last=True, workers=workers, decoder=decoder)
+        if decoder == 'process':
+            print('frame slots page-locked:', ds._frame_slots(24, workers, 6).pinned)
+        stack_hg.train(feed, net, opt_, aug, 0, opt, log=lambda m: None)                   # warm-up pass (pools, kernels)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        stack_hg.train(feed, net, opt_, aug, 1, opt, log=lambda m: None)
+        torch.cuda.synchronize(); dt = time.perf_counter() - t0
+        print('stack_hg.train over MPII.batches (decoder=%s, %d workers, 6 batches in flight): %.1f img/s fed (%d images, %.2f s)' % (decoder, workers, feed.num_samples / dt, feed.num_samples, dt))
     resident = list(feed)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     stack_hg.train(resident, net, opt_, aug, 2, opt, log=lambda m: None)
