@@ -158,7 +158,6 @@ struct ResidualOp {
         n.bneval_jobs = a.get<PaBnEvalJob>(n.bns.size());
         in = n.new_act(a, B, H, W, C, nullptr, true);
         r.layout(n, a, B, H, W, true);
-        n.layout_shared(a);
         a.take(0);
         return a.off;
     }
@@ -211,7 +210,6 @@ struct ConvOp {
         n.layout_conv(c, a, B * H * W, H, W);
         xin = a.get<bf16>((size_t)B * H * W * c.pcin);
         yout = a.get<bf16>((size_t)B * H * W * c.pcout);
-        n.layout_shared(a);
         a.take(0);
         return a.off;
     }
@@ -284,7 +282,6 @@ struct WgradGroupOp {
         }
         pbuf = a.get<float>(n.n_params + 8);
         gbuf = a.get<float>(n.n_params + 8);
-        n.layout_shared(a);
         a.take(0);
         return a.off;
     }
@@ -435,7 +432,6 @@ pa_net* pa_hg_create(int num_stacks, int num_classes, int chan, int B, int res) 
     if (!p) return nullptr;
     Net& n = p->n;
     n.stacks = num_stacks; n.classes = num_classes; n.chan = chan; n.B = B; n.res = res;
-    n.immediate_reduce = pa_getenv("PA_SHARED_SLAB") != nullptr;
     n.declare_pose();
     n.workspace_bytes = n.layout_all(nullptr);
     return p;
@@ -457,7 +453,6 @@ pa_net* pa_asn_create(int chan, int scale_num, int rotation_num, int B, int res)
     if (!p) return nullptr;
     Net& n = p->n;
     n.chan = chan; n.B = B; n.res = res; n.scale_num = scale_num; n.rot_num = rotation_num; n.stacks = 0;
-    n.immediate_reduce = pa_getenv("PA_SHARED_SLAB") != nullptr;
     n.declare_asn();
     n.workspace_bytes = n.layout_asn(nullptr);
     return p;
@@ -473,7 +468,6 @@ pa_net* pa_asn_create_dropout(int chan, int B, int res) {
     if (!p) return nullptr;
     Net& n = p->n;
     n.chan = chan; n.B = B; n.res = res; n.stacks = 0; n.asn_dropout = true;
-    n.immediate_reduce = pa_getenv("PA_SHARED_SLAB") != nullptr;
     n.declare_asn();
     n.workspace_bytes = n.layout_asn(nullptr);
     return p;
@@ -732,7 +726,7 @@ int pa_net_profile_classes(const pa_net* net, int32_t* out, int cap) {
 int pa_net_set_multi_stream(pa_net* net, int on) {
     if (net->n.ensure_streams()) return 1;
     net->n.release_graph();
-    net->n.multi_stream = on != 0 && net->n.side[0] != nullptr;
+    net->n.multi_stream = on != 0 && net->n.side != nullptr;
     return 0;
 }
 

@@ -217,7 +217,6 @@ size_t Net::layout_asn(char* base) {
     asn_logits = a.get<float>((size_t)B * (asn_dropout ? 16 : scale_num + rot_num));
     asn_probs = a.get<float>((size_t)B * (scale_num + rot_num));
     asn_dlogits = a.get<float>((size_t)B * (scale_num + rot_num));
-    layout_shared(a);
     a.take(0);
     return a.off;
 }
@@ -238,7 +237,7 @@ int Net::forward_half(const float* img_nchw, const bf16* img4_in, bool train) {
     TRY(res3.fwd(*this, res2.x3));
     TRY(hg[0].encode(*this, xin[0]));
     if (multi_stream)                      // no decoder here: join the skip branches before anyone reads them
-        for (int k = 0; k < 4; ++k) if (forks(k)) TRY(wait_join(k));
+        for (int k = 0; k < 4; ++k) TRY(wait_join(k));
     return 0;
 }
 

@@ -39,13 +39,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
     } while (0)
 
 // A/B switches (PA_* environment variables selecting between parity-tested code paths) exist only in a
-// tuning build (PA_TUNING=1 bash build.sh -> -DPA_TUNING); the release library reads no environment at all.
-#include <stdlib.h>
-#ifdef PA_TUNING
-inline const char* pa_getenv(const char* name) { return getenv(name); }
-#else
-inline const char* pa_getenv(const char*) { return nullptr; }
-#endif
+// tuning build (PA_TUNING=1 bash build.sh -> -DPA_TUNING); the release library reads no environment at all.  tuning.h is their table.
+#include "tuning.h"
 // Cycle stamps inside a kernel (tuning builds; tools/conv3_clocks.py): PA_STAMP_DECL(sym, fn) defines the device array and its C accessor
 // in one translation unit, PA_STAMP_AT(sym, on, i) records {s_memtime (shader cycles), wall_clock64 (100 MHz)} of thread 0 of workgroup (0, 0).
 #ifdef PA_TUNING

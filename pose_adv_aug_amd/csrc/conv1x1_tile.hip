@@ -27,11 +27,9 @@ PA_STAMP_DECL(pa_conv1t_clk, pa_debug_conv1t_clocks)
 #define PA_STAMPT(i) do { } while (0)
 #endif
 
-#define PA_CONV1_K32_DEFAULT 1
 #ifndef PA_CONV1_UP_OCC
 #define PA_CONV1_UP_OCC(up) 3          // workgroups per CU of the 3-workgroup instances (the UP instance included)
 #endif
-#define PA_CONV1_C64_BM64_DEFAULT 1
 #define PA_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define PA_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
@@ -221,26 +219,25 @@ __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CI
     PA_STAMPT(6);
 }
 
-template <int CIN, int BM, int BN, int KS = 64>
+// LIN2_ONLY: an instance that only BatchNorm-backward inputs reach (the 128-row fallback of the 128-channel layers)
+template <int CIN, int BM, int BN, int KS = 64, bool LIN2_ONLY = false>
 static void launch_row_ld(const PaConvArgs& a0, dim3 grid, int nbw, hipStream_t st) {
     PaConvArgs a = a0;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = pa_getenv("PA_CONV1T_DBG"); dbg = e ? atoi(e) : 0; }      // tuning builds: cycle stamps
-    a.dbg = dbg;
-    switch (a.in.mode) {
-        case PA_LD_PLAIN: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_PLAIN, KS>), grid, dim3(256), 0, st, a, nbw); break;
-        case PA_LD_BNRELU: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_BNRELU, KS>), grid, dim3(256), 0, st, a, nbw); break;
-        default: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_LIN2, KS>), grid, dim3(256), 0, st, a, nbw); break;
+    a.dbg = pa_tuning().conv1t_dbg;      // tuning builds: cycle stamps
+    if constexpr (LIN2_ONLY) {
+        hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_LIN2, KS>), grid, dim3(256), 0, st, a, nbw);
+    } else {
+        switch (a.in.mode) {
+            case PA_LD_PLAIN: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_PLAIN, KS>), grid, dim3(256), 0, st, a, nbw); break;
+            case PA_LD_BNRELU: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_BNRELU, KS>), grid, dim3(256), 0, st, a, nbw); break;
+            default: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_LIN2, KS>), grid, dim3(256), 0, st, a, nbw); break;
+        }
     }
 }
 
 // 64-row tiles also for 128 input channels: at B = 24, 64x64 maps the 768 tiles of 128 rows fill 256 CUs x 2
 // workgroups 1.5 times (the last round runs half empty); 1536 tiles of 64 rows at 3 workgroups/CU are 2 full rounds
-static int row_bm(int Cin) {
-    static int big = -1;
-    if (big < 0) big = pa_getenv("PA_CONV1_BM128") ? 1 : 0;
-    return (Cin == 256 || (Cin == 128 && !big)) ? 64 : 128;
-}
+static int row_bm(int Cin) { return (Cin == 256 || Cin == 128) ? 64 : 128; }
 
 // the UP instance: 128 -> 256 (any multiple of 128) channels, BatchNorm backward on load, one plain addend, plain output, maps whose rows are
 // multiples of 32 pixels with an even row count, enough tiles for the row-tile kernel
@@ -281,9 +278,7 @@ int pa_launch_conv1x1_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) 
     const int M = a.B * a.H * a.W;
     int bm = row_bm(a.Cin);
     // 64 input channels, 128 output channels: 64-row tiles at three workgroups per CU (the 128-row instance spills at 168 registers)
-    static int c64bm = -1;
-    if (c64bm < 0) { const char* e = pa_getenv("PA_CONV1_C64_BM64"); c64bm = e ? atoi(e) : PA_CONV1_C64_BM64_DEFAULT; }
-    if (a.Cin == 64 && a.Cout % 128 == 0 && c64bm && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a))) bm = 64;
+    if (a.Cin == 64 && a.Cout % 128 == 0 && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a))) bm = 64;
     // the 64-row, 128-channel BatchNorm-backward instance (3 workgroups per CU) has the LDS epilogue only
     if (a.Cin == 128 && bm == 64 && a.in.mode == PA_LD_LIN2 && a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a)) bm = 128;
     const int tiles = (M + bm - 1) / bm;
@@ -293,13 +288,11 @@ int pa_launch_conv1x1_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) 
     const int nb = a.Cout / (bigN ? 128 : 64);
     const int nbw = tiles >= 512 ? nb : 1;          // enough row tiles: loop over the channel blocks inside (input read once)
     dim3 grid(tiles, nb / nbw);
-    static int k32 = -1;
-    if (k32 < 0) { const char* e = pa_getenv("PA_CONV1_K32"); k32 = e ? atoi(e) : PA_CONV1_K32_DEFAULT; }
     // 256 channels: the three-workgroup instance (32-channel weight slices) unless the launch needs the direct BatchNorm-backward epilogue
-    const bool three = k32 && bigN && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a));
+    const bool three = bigN && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a));
     if (a.Cin == 256) { if (bigN && three) launch_row_ld<256, 64, 128, 32>(a, grid, nbw, st); else if (bigN) launch_row_ld<256, 64, 128>(a, grid, nbw, st); else launch_row_ld<256, 64, 64>(a, grid, nbw, st); }
     else if (a.Cin == 128 && bm == 64) { if (bigN) launch_row_ld<128, 64, 128>(a, grid, nbw, st); else launch_row_ld<128, 64, 64>(a, grid, nbw, st); }
-    else if (a.Cin == 128) { if (bigN) launch_row_ld<128, 128, 128>(a, grid, nbw, st); else launch_row_ld<128, 128, 64>(a, grid, nbw, st); }
+    else if (a.Cin == 128) { if (bigN) launch_row_ld<128, 128, 128, 64, true>(a, grid, nbw, st); else launch_row_ld<128, 128, 64, 64, true>(a, grid, nbw, st); }      // (bm == 128 here: a.in.mode is LIN2)
     else if (bm == 64) launch_row_ld<64, 64, 128>(a, grid, nbw, st);
     else { if (bigN) launch_row_ld<64, 128, 128>(a, grid, nbw, st); else launch_row_ld<64, 128, 64>(a, grid, nbw, st); }
     return (int)hipGetLastError();

@@ -52,25 +52,19 @@ template <int N> __device__ __forceinline__ void pa_wait_vmcnt() {
     else static_assert(N == 0, "unsupported vmcnt");
 }
 
-// TRI (NT = 512 threads, 16 x 8 tiles): THREE pixel tiles per workgroup = 384 pixels = exactly one CU's share of a 24 x 64 x 64 map.
-// The three tiles share ONE weight ring, so the L2 -> LDS weight stream per pixel is a third (it is what bounds the K loop of the
-// 128-pixel kernel: 295 KB per tile against 3.9 us of MFMA work, two workgroups per CU streaming at once), every K step has 24 MFMAs
-// per wave between two barriers instead of 16, and the launch is ONE full round of 256 workgroups instead of 768 on 512 slots.
-// 8 waves = 4 (pixels: 6 fragments of 16 each) x 2 (channels: 4 fragments); LDS 135 KB of halos + a ring of 3 slices: one workgroup
-// per CU, whose memory phases (staging, epilogue) run as chip-wide bursts.
 // FIN: the instance that can carry the input's BatchNorm finalize in its prologue (bn_fin.h): instantiated for the tilings the maps with
-// <= 128 statistics rows use (launch_tile_shape); all other instances are the plain kernel.
+// <= 128 statistics rows use (the launchers below); all other instances are the plain kernel.
 // PA_TUNING builds only: a.dbg -- phase ablation (1 no K loop, 2 no epilogue, 4 no staging: wrong results, timing) and bit 8, per-workgroup tap rotation
-// NT = 512 / 1024 on the maps that give at most one workgroup per CU (8 x 8, 4 x 4, 16 x 16): with ONE wave per SIMD nothing overlaps -- cycle
+// NT = 512 on the maps that give at most one workgroup per CU (8 x 8, 4 x 4, 16 x 16): with ONE wave per SIMD nothing overlaps -- cycle
 // stamps (tools/conv3_clocks.py) show a K-loop step as the plain SUM of its parts (barrier ~100 cycles, each LDS-DMA issue 100-150, the ds_read
 // round trip ~150, 17 per MFMA: 45-60 cycles per MFMA instead of 17), and the staging / epilogue are load / store round trips of 4 waves.  Two
-// or four waves per SIMD (the same 128 pixels x 64 channels, MI = 2 or 1 fragments per wave) let one wave's MFMAs run under another's waits.
+// waves per SIMD (the same 128 pixels x 64 channels, MI = 2 fragments per wave) let one wave's MFMAs run under another's waits (measured 8x8:
+// 14.1 / 10.6 / 12.8 us at 256 / 512 / 1024 threads).
 // cycle stamps (tuning builds, a.dbg & 64): entry / weight ring issued / own halo part staged / K loop / barrier / epilogue
 PA_STAMP_DECL(pa_conv3_clk, pa_debug_conv3_clocks)
 #define PA_STAMP(i) PA_STAMP_AT(pa_conv3_clk, a.dbg & 64, i)
 template <int CIN, int BN, int LDMODE, int TW = 16, int TH = 8, int SPS = 1, bool PF = false, int NT = 256, bool FIN = false>
 __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS == 1 ? 3 : 2) : 2) : 1))) void conv3x3_tile_kernel(PaConvArgs a) {
-    constexpr bool TRI = NT == 512 && TW == 16 && TH == 8;
     PA_SET_MAIN_PRIO();
     PA_STAMP(0);
 #if defined(PA_TUNING) && !defined(PA_CONV3_CONSTDBG)      // (PA_EXTRA=-DPA_CONV3_CONSTDBG: the release code with the cycle stamps only)
@@ -85,8 +79,8 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
         for (int i = 0; i < (a.dbg >> 8); ++i) __builtin_amdgcn_s_sleep(16);
 #endif
     constexpr int NW = NT / 64, WM = NW / 2;                             // waves; waves along the pixels (2 along the channels)
-    constexpr int BM = TRI ? 384 : ((TW == 16 && TH == 4) ? 64 : 128);
-    constexpr int IMG = BM / (TW * TH), PW = TW + 2, PHh = TH + 2, HP = IMG * PHh * PW;   // 180 / 108 / 200 / 288 / 540 halo pixels
+    constexpr int BM = (TW == 16 && TH == 4) ? 64 : 128;
+    constexpr int IMG = BM / (TW * TH), PW = TW + 2, PHh = TH + 2, HP = IMG * PHh * PW;   // 180 / 108 / 200 / 288 halo pixels
     constexpr int CPP = CIN / 8;                                         // 16-byte chunks per pixel
     constexpr int NI = BN / 32, MI = BM / (16 * WM);
     constexpr int NSL = CIN / 32;                                        // 32-channel weight slices per tap
@@ -97,10 +91,9 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
     constexpr int NIW = DEAL ? 0 : BN / (16 * NW), PPS = SPS * BN / (16 * NW);
     static_assert(PPS >= 1 && PPS * 16 * NW == SPS * BN, "every wave issues the same number of weight pieces per step");
     constexpr int NST = NIT / SPS, GPT = NSL / SPS;                      // K-loop steps, steps per tap
-    constexpr int NBUF = TRI ? 3 : (SPS == 1 ? (BM == 64 ? 3 : 4) : 3);  // ring of NBUF step buffers [SPS][BN][32]
+    constexpr int NBUF = SPS == 1 ? (BM == 64 ? 3 : 4) : 3;  // ring of NBUF step buffers [SPS][BN][32]
     constexpr int AHEAD = NBUF - 2;                                      // steps still in flight while one is consumed
     static_assert(NSL % SPS == 0, "a step stays inside one tap");
-    static_assert(!TRI || (TW == 16 && TH == 8 && PF && SPS == 1), "three-tile workgroups: 16 x 8 tiles, pipelined K loop");
     constexpr int PSTEP = NT / CPP;                                      // halo pixels staged per pass
     constexpr int NPASS = (HP + PSTEP - 1) / PSTEP;
     // ONE shared object (a second one makes hipcc drain vmcnt(0) before every ds_read of the pipeline)
@@ -115,31 +108,16 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
     // consecutive workgroups go to different XCDs (round robin), each with its own L2: give every XCD one contiguous range
     // of tiles so that the halo rows / columns shared by neighbouring tiles are found in that L2
     int t = (a.xcd & 1) ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int t0 = t * IMG;                            // TRI: first of the workgroup's three consecutive tiles
+    const int t0 = t * IMG;                            // first sub-tile of the workgroup
     const int tx = t % tiles_x; t /= tiles_x;
     const int ty = t % tiles_y;
     const int b = (t / tiles_y) * IMG;                 // first image of this workgroup (small maps: tile = image)
     const int y0 = ty * TH, x0 = tx * TW;
     const int n0 = blockIdx.y * BN;
     const int K = 9 * CIN;
-    // origin of sub-tile `im` of the workgroup: small maps -- image b + im at (0, 0); TRI -- tile t0 + im of the tile grid
-    // (three wave-uniform origins, selected per lane)
-    int ob[3], oy[3], ox[3];
-    if constexpr (TRI) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            int tt = t0 + j;
-            ox[j] = (tt % tiles_x) * TW; tt /= tiles_x;
-            oy[j] = (tt % tiles_y) * TH;
-            ob[j] = tt / tiles_y;
-        }
-    }
+    // origin of sub-tile `im` of the workgroup
     auto origin = [&](int im, int& bb, int& yy, int& xx) {
-        if constexpr (TRI) {
-            bb = im == 0 ? ob[0] : (im == 1 ? ob[1] : ob[2]);
-            yy = im == 0 ? oy[0] : (im == 1 ? oy[1] : oy[2]);
-            xx = im == 0 ? ox[0] : (im == 1 ? ox[1] : ox[2]);
-        } else if constexpr (IMG > 1) {
+        if constexpr (IMG > 1) {
             // small tiles (8 x 8 / 4 x 4): the tile IS the image (8 x 8 / 4 x 4 maps) -- or, round 6, sub-tile t0 + im of the tile grid of a map
             // whose sides are multiples of the tile (24 x 24, 12 x 12 of the 384 x 384 configuration); a workgroup's sub-tiles may lie in two images
             if (tiles_x * tiles_y == 1) { bb = b + im; yy = 0; xx = 0; }
@@ -204,7 +182,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
         float k0[8], k1[8], k2[8];
         if (LDMODE != PA_LD_PLAIN) {
             bool done = false;
-            if constexpr (FIN && !TRI) {
+            if constexpr (FIN) {
                 if (a.fin.rows > 0) {
                     // the input's BatchNorm finalize from the producer's <= 128 partial rows (bn_fin.h) instead of a launch of its own in
                     // front of this kernel; table + scratch sit in the halo region, which nobody writes before the barrier below
@@ -227,7 +205,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
                 }
             }
         }
-        constexpr int UN = LDMODE == PA_LD_LIN2 ? 6 : (TRI ? 9 : 12);      // loads in flight per thread before the first transform
+        constexpr int UN = LDMODE == PA_LD_LIN2 ? 6 : 12;      // loads in flight per thread before the first transform
 #pragma unroll
         for (int p0 = 0; p0 < NPASS; p0 += UN) {
             bf16x8 ra[UN], rq[UN];
@@ -444,54 +422,36 @@ static void launch_tile_ld(const PaConvArgs& a, dim3 grid, hipStream_t st) {
     }
 }
 
-// SPS: slices per K-loop step of the latency-bound variants (128 input channels): a whole tap for the 8x8 / 4x4 maps, half a
-// tap for the 16 x 4 tiles; 1 everywhere else (the 16 x 8 tiles of the big maps are throughput-bound and need their LDS for 2
-// workgroups per CU).  The 16 x 8 tiles run the software-pipelined K loop (PA_CONV3_PF=0: the plain one).
-template <int TW, int TH, int SPS>
-static void launch_tile_shape(const PaConvArgs& a, dim3 grid, bool bigN, hipStream_t st) {
-    if constexpr (TW != 16) {                      // the small maps always run 64-channel halves (bigN is false for them)
-        if (a.Cin == 128) {
-            if constexpr (SPS == 4) {
-                static int nt = -1;
-                if (nt < 0) { const char* e = pa_getenv("PA_CONV3_NT"); nt = e ? atoi(e) : 512; }      // measured 8x8: 14.1 / 10.6 / 12.8 us at 256 / 512 / 1024 threads
-                if (nt == 512) { launch_tile_ld<128, 64, TW, TH, SPS, false, true, 512>(a, grid, st); return; }
-                if (nt == 1024) { launch_tile_ld<128, 64, TW, TH, SPS, false, true, 1024>(a, grid, st); return; }
-            }
-            launch_tile_ld<128, 64, TW, TH, SPS, false, true>(a, grid, st);
-        } else launch_tile_ld<64, 64, TW, TH, 1, false, true>(a, grid, st);
-    } else if constexpr (TH == 8 && SPS == 1) {
-        static int pf = -1;
-        if (pf < 0) { const char* e = pa_getenv("PA_CONV3_PF"); pf = e ? atoi(e) : 1; }
-        if (pf) {
-            if (a.Cin == 128) { if (bigN) launch_tile_ld<128, 128, TW, TH, 1, true>(a, grid, st); else launch_tile_ld<128, 64, TW, TH, 1, true>(a, grid, st); }
-            else { if (bigN) launch_tile_ld<64, 128, TW, TH, 1, true>(a, grid, st); else launch_tile_ld<64, 64, TW, TH, 1, true, true>(a, grid, st); }
-        } else {
-            if (a.Cin == 128) { if (bigN) launch_tile_ld<128, 128, TW, TH, 1, false>(a, grid, st); else launch_tile_ld<128, 64, TW, TH, 1, false>(a, grid, st); }
-            else { if (bigN) launch_tile_ld<64, 128, TW, TH, 1, false>(a, grid, st); else launch_tile_ld<64, 64, TW, TH, 1, false>(a, grid, st); }
-        }
-    } else {
-        if (a.Cin == 128) {
-            if constexpr (SPS == 2) {
-                // 512 threads when the launch is at most one workgroup per CU (the 16 x 16 maps in 64-channel halves: 192 workgroups, 12.0 -> 8.6 us);
-                // with two workgroups per CU (32 x 32) the 256-thread workgroups already overlap each other and 512 measured slower (16.1 vs 18.2)
-                static int nt = -1, cus = 0;
-                if (nt < 0) {
-                    int dev = 0;
-                    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-                    const char* e = pa_getenv("PA_CONV3_NT16"); nt = e ? atoi(e) : 512;
-                }
-                if (nt == 512 && (int)(grid.x * grid.y) <= cus) { if (bigN) launch_tile_ld<128, 128, TW, TH, SPS, false, true, 512>(a, grid, st); else launch_tile_ld<128, 64, TW, TH, SPS, false, true, 512>(a, grid, st); return; }
-            }
-            if (bigN) launch_tile_ld<128, 128, TW, TH, SPS, false, (SPS == 2)>(a, grid, st); else launch_tile_ld<128, 64, TW, TH, SPS, false, (SPS == 2)>(a, grid, st);
-        }
-        else { if (bigN) launch_tile_ld<64, 128, TW, TH, 1, false>(a, grid, st); else launch_tile_ld<64, 64, TW, TH, 1, false>(a, grid, st); }
-    }
+// The three tilings.  SPS: slices per K-loop step of the latency-bound variants (128 input channels): a whole tap for the 8x8 / 4x4 maps,
+// half a tap for the 16 x 4 tiles; 1 everywhere else (the 16 x 8 tiles of the big maps are throughput-bound and need their LDS for 2
+// workgroups per CU, and run the software-pipelined K loop).
+// 8 x 8 / 4 x 4 tiles: always 64-channel halves, 512 threads for 128 input channels
+template <int T>
+static void launch_small(const PaConvArgs& a, dim3 grid, hipStream_t st) {
+    if (a.Cin == 128) launch_tile_ld<128, 64, T, T, 4, false, true, 512>(a, grid, st);
+    else launch_tile_ld<64, 64, T, T, 1, false, true>(a, grid, st);
+}
+// 16 x 8 tiles
+static void launch_16x8(const PaConvArgs& a, dim3 grid, bool bigN, hipStream_t st) {
+    if (a.Cin == 128) { if (bigN) launch_tile_ld<128, 128, 16, 8, 1, true>(a, grid, st); else launch_tile_ld<128, 64, 16, 8, 1, true>(a, grid, st); }
+    else { if (bigN) launch_tile_ld<64, 128, 16, 8, 1, true>(a, grid, st); else launch_tile_ld<64, 64, 16, 8, 1, true, true>(a, grid, st); }
+}
+// 16 x 4 tiles (128 input channels, 64-channel halves): 512 threads when the launch is at most one workgroup per CU (the 16 x 16 maps: 192
+// workgroups, 12.0 -> 8.6 us); with two workgroups per CU (32 x 32) the 256-thread workgroups already overlap each other and 512 measured
+// slower (16.1 vs 18.2)
+static void launch_16x4(const PaConvArgs& a, dim3 grid, hipStream_t st) {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+        return n;
+    }();
+    if ((int)(grid.x * grid.y) <= cus) launch_tile_ld<128, 64, 16, 4, 2, false, true, 512>(a, grid, st);
+    else launch_tile_ld<128, 64, 16, 4, 2, false, true>(a, grid, st);
 }
 
 // does the instance the launcher below picks for this shape exist with the finalize prologue?  (pa_conv_takes_fin)
 bool pa_conv3x3_tile_takes_fin(const PaConvArgs& a) {
     if (!pa_conv3x3_tile_supported(a)) return false;
-    if (pa_getenv("PA_CONV3_SPS") || pa_getenv("PA_CONV3_PF") || pa_getenv("PA_CONV3_BM64") || pa_getenv("PA_CONV3_BN64")) return false;      // (tuning switches select other instances)
     const bool small = !(a.H % 8 == 0 && a.W % 16 == 0);
     if (small) return true;                                                    // 8 x 8 / 4 x 4 maps: <128 | 64, 64, .., SPS 4 | 1>
     const int tiles128 = a.B * (a.H / 8) * (a.W / 16);
@@ -505,11 +465,9 @@ static int small_tile(const PaConvArgs& a) { return (a.H % 8 == 0 && a.W % 8 == 
 static bool small_map(const PaConvArgs& a) { return small_tile(a) != 0; }
 
 bool pa_conv3x3_tile_supported(const PaConvArgs& a) {
-    static int nosmall = -1;
-    if (nosmall < 0) nosmall = pa_getenv("PA_CONV3_NOSMALL") ? 1 : 0;
     if (a.taps != 9 || (a.Cin != 64 && a.Cin != 128) || a.Cout % 64 != 0) return false;
     if ((size_t)a.B * a.H * a.W * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;      // 32-bit element offsets in the epilogue
-    return (a.H % 8 == 0 && a.W % 16 == 0) || (!nosmall && small_map(a));
+    return (a.H % 8 == 0 && a.W % 16 == 0) || (!pa_tuning().conv3_nosmall && small_map(a));
 }
 
 int pa_launch_conv3x3_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) {
@@ -519,58 +477,23 @@ int pa_launch_conv3x3_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) 
     const int img = small ? 128 / (st_ * st_) : 1;                  // sub-tiles per workgroup
     // 16 x 4 pixel tiles (3 workgroups per CU) where 16 x 8 tiles would leave CUs idle: measured 64x64 maps (768 tiles)
     // 39.8 vs 42.8 us in favour of 16 x 8, 32x32 maps (192 tiles) 17.6 vs 14.6 us in favour of 16 x 4
-    static int bm64 = -1;
-    if (bm64 < 0) { const char* e = pa_getenv("PA_CONV3_BM64"); bm64 = e ? atoi(e) : -2; }
     const int tiles128 = small ? 0 : a.B * (a.H / 8) * (a.W / 16);
-    const bool half = !small && a.Cin == 128 && (bm64 == -2 ? tiles128 < 512 : bm64 != 0);
+    const bool half = !small && a.Cin == 128 && tiles128 < 512;
     const int tiles = small ? (a.B * ((a.H + st_ - 1) / st_) * ((a.W + st_ - 1) / st_) + img - 1) / img : a.B * (a.H / (half ? 4 : 8)) * (a.W / 16);
     if (stat_rows) *stat_rows = tiles;
     if (a.ep.rows_out) *a.ep.rows_out = tiles;
-    static int n64 = -1;
-    if (n64 < 0) n64 = pa_getenv("PA_CONV3_BN64") ? 1 : 0;          // experiment: 64-channel halves
     // the low-resolution levels have 3..12 pixel tiles: 64-channel halves double the number of workgroups
     // ... and so do the 16 x 4 tiles (32 x 32 / 16 x 16 maps): 64-channel blocks halve the serial chain of a workgroup (weight pieces, MFMAs,
-    // epilogue) -- 32 x 32: 16.5 -> 16.1 / 19.3 -> 17.8 us (forward / data gradient), 16 x 16: see launch_tile_shape
-    static int h64 = -1;
-    if (h64 < 0) { const char* e = pa_getenv("PA_CONV3_HALF64"); h64 = e ? atoi(e) : 1; }
-    const bool bigN = a.Cout % 128 == 0 && !n64 && !small && !(half && h64);
+    // epilogue) -- 32 x 32: 16.5 -> 16.1 / 19.3 -> 17.8 us (forward / data gradient), 16 x 16: see launch_16x4
+    const bool bigN = a.Cout % 128 == 0 && !small && !half;
     dim3 grid(tiles, a.Cout / (bigN ? 128 : 64));
-    static int xcd = -1;
-    if (xcd < 0) xcd = pa_getenv("PA_CONV3_NOXCD") ? 0 : 1;          // +0.3 % on the step (halo re-reads served by the XCD's own L2)
     PaConvArgs b = a;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = pa_getenv("PA_CONV3_DBG"); dbg = e ? atoi(e) : 0; }      // tuning builds: phase ablation / tap rotation
-    b.dbg = dbg;
-    b.xcd = (a.xcd & 2) | ((xcd && !small && tiles % 8 == 0) ? 1 : 0);
-    static int sps = -1;
-    if (sps < 0) { const char* e = pa_getenv("PA_CONV3_SPS"); sps = e ? atoi(e) : 1; }      // 0: one slice per step everywhere (round 1)
-    // three 16 x 8 tiles per 512-thread workgroup (one shared weight ring) when that is exactly one round of workgroups on the chip:
-    // the 64 x 64 maps of the hourglass at batch 24 (768 tiles = 256 workgroups)
-#ifdef PA_CONV3_TRI_BUILD          // (measured a wash, DESIGN.md round 4: compiled only on request -- PA_EXTRA=-DPA_CONV3_TRI_BUILD)
-    static int tri = -1, cus = 0;
-    if (tri < 0) {
-        const char* e = pa_getenv("PA_CONV3_TRI"); tri = e ? atoi(e) : 0;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-    }
-    const int wg3 = tiles128 / 3;
-    if (tri && a.fin.rows <= 0 && !small && !half && a.Cin == 128 && bigN && tiles128 % 3 == 0 && wg3 % 8 == 0 && wg3 <= cus && 2 * wg3 > cus &&
-        (a.ep.mode != PA_OUT_BWD || pa_bwd_epilogue_lds_ok(a))) {
-        if (stat_rows) *stat_rows = wg3;
-        if (a.ep.rows_out) *a.ep.rows_out = wg3;
-        b.xcd = (a.xcd & 2) | (xcd ? 1 : 0);
-        dim3 g3(wg3, a.Cout / 128);
-        switch (a.in.mode) {
-            case PA_LD_PLAIN: hipLaunchKernelGGL((conv3x3_tile_kernel<128, 128, PA_LD_PLAIN, 16, 8, 1, true, 512>), g3, dim3(512), 0, st, b); break;
-            case PA_LD_BNRELU: hipLaunchKernelGGL((conv3x3_tile_kernel<128, 128, PA_LD_BNRELU, 16, 8, 1, true, 512>), g3, dim3(512), 0, st, b); break;
-            default: hipLaunchKernelGGL((conv3x3_tile_kernel<128, 128, PA_LD_LIN2, 16, 8, 1, true, 512>), g3, dim3(512), 0, st, b); break;
-        }
-        return (int)hipGetLastError();
-    }
-#endif
-    if (half) { if (sps) launch_tile_shape<16, 4, 2>(b, grid, bigN, st); else launch_tile_shape<16, 4, 1>(b, grid, bigN, st); }
-    else if (!small) launch_tile_shape<16, 8, 1>(b, grid, bigN, st);
-    else if (st_ == 8) { if (sps) launch_tile_shape<8, 8, 4>(b, grid, bigN, st); else launch_tile_shape<8, 8, 1>(b, grid, bigN, st); }
-    else { if (sps) launch_tile_shape<4, 4, 4>(b, grid, bigN, st); else launch_tile_shape<4, 4, 1>(b, grid, bigN, st); }
+    b.dbg = pa_tuning().conv3_dbg;                                  // tuning builds: phase ablation / tap rotation
+    // one contiguous range of tiles per XCD: +0.3 % on the step (halo re-reads served by the XCD's own L2)
+    b.xcd = (a.xcd & 2) | ((!pa_tuning().conv3_noxcd && !small && tiles % 8 == 0) ? 1 : 0);
+    if (half) launch_16x4(b, grid, st);
+    else if (!small) launch_16x8(b, grid, bigN, st);
+    else if (st_ == 8) launch_small<8>(b, grid, st);
+    else launch_small<4>(b, grid, st);
     return (int)hipGetLastError();
 }

@@ -333,9 +333,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_oneshot_kernel(PaConvArgs a) {
 template <int NK>
 static void launch_oneshot(const PaConvArgs& a0, dim3 grid, hipStream_t st) {
     PaConvArgs a = a0;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = pa_getenv("PA_CONV1_DBG"); dbg = e ? atoi(e) : 0; }      // tuning builds: cycle stamps
-    a.dbg = dbg;
+    a.dbg = pa_tuning().conv1_dbg;      // tuning builds: cycle stamps
     if (a.fin.rows > 0) {
         if (a.in.mode == PA_LD_BNRELU) hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_BNRELU, true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_LIN2, true>), grid, dim3(256), 0, st, a);
@@ -388,9 +386,8 @@ int pa_launch_stem_conv(const PaConvArgs& a, hipStream_t st, int* stat_rows) {
 bool pa_conv_takes_fin(const PaConvArgs& a) {
     if (a.in.mode != PA_LD_BNRELU && a.in.mode != PA_LD_LIN2) return false;
     if (a.Cin > 256) return false;
-    const bool old3 = pa_getenv("PA_CONV3_OLD") != nullptr, old1 = pa_getenv("PA_CONV1_OLD") != nullptr;
-    if (!old3 && pa_conv3x3_tile_supported(a)) return pa_conv3x3_tile_takes_fin(a);
-    if (!old1 && pa_conv1x1_tile_supported(a)) return false;
+    if (!pa_tuning().conv3_old && pa_conv3x3_tile_supported(a)) return pa_conv3x3_tile_takes_fin(a);
+    if (!pa_tuning().conv1_old && pa_conv1x1_tile_supported(a)) return false;
     // generic kernel: only its 64 x 64-tile instance carries the prologue (the dispatch below: small M, or 64-channel outputs)
     const int M = a.B * a.H * a.W;
     const bool bigM = M >= 128 * 256, bigN = a.Cout % 128 == 0;
@@ -398,10 +395,8 @@ bool pa_conv_takes_fin(const PaConvArgs& a) {
 }
 
 int pa_launch_conv(const PaConvArgs& a0, hipStream_t st, int* stat_rows) {
-    static int bwd_direct = -1;
-    if (bwd_direct < 0) bwd_direct = pa_getenv("PA_EPI_BWD_DIRECT") ? 2 : 0;      // A/B: direct BatchNorm-backward epilogue
     PaConvArgs a = a0;
-    a.xcd = bwd_direct;
+    a.xcd = pa_tuning().epi_bwd_direct ? 2 : 0;      // A/B: direct BatchNorm-backward epilogue
     if ((a.taps != 1 && a.taps != 9) || a.Cin % 64 != 0 || a.Cout % 64 != 0 || a.Cin > 512) {
         pa_set_error_msg("pa_launch_conv: channel counts must be multiples of 64 and taps 1 or 9");
         return 1;
@@ -410,12 +405,8 @@ int pa_launch_conv(const PaConvArgs& a0, hipStream_t st, int* stat_rows) {
         pa_set_error_msg("pa_launch_conv: tensors of 2^31 elements or more are not supported (split the batch)");
         return 1;
     }
-    static int old3 = -1;
-    if (old3 < 0) old3 = pa_getenv("PA_CONV3_OLD") ? 1 : 0;          // experiments: force the generic kernel
-    if (!old3 && pa_conv3x3_tile_supported(a)) return pa_launch_conv3x3_tile(a, st, stat_rows);
-    static int old1 = -1;
-    if (old1 < 0) old1 = pa_getenv("PA_CONV1_OLD") ? 1 : 0;
-    if (!old1 && pa_conv1x1_tile_supported(a)) {
+    if (!pa_tuning().conv3_old && pa_conv3x3_tile_supported(a)) return pa_launch_conv3x3_tile(a, st, stat_rows);
+    if (!pa_tuning().conv1_old && pa_conv1x1_tile_supported(a)) {
         if (a.fin.rows > 0) { pa_set_error_msg("pa_launch_conv: a pending finalize was handed to the row-tile 1x1 kernel (pa_conv_takes_fin)"); return 1; }
         return pa_launch_conv1x1_tile(a, st, stat_rows);
     }
@@ -431,8 +422,7 @@ int pa_launch_conv(const PaConvArgs& a0, hipStream_t st, int* stat_rows) {
     else if (bigN && M >= 64 * 256) launch_taps<64, 128>(a, dim3((M + 63) / 64, a.Cout / 128), st);
     else {
         // 64 x 64 tiles: the 1x1 layers with 128 / 256 input channels take the one-shot kernel (PA_IGEMM_ONESHOT=0: the K-stepping one)
-        static int oneshot = -1;
-        if (oneshot < 0) { const char* e = pa_getenv("PA_IGEMM_ONESHOT"); oneshot = e ? atoi(e) : 1; }
+        const bool oneshot = pa_tuning().igemm_oneshot != 0;
         const dim3 grid((M + 63) / 64, a.Cout / 64);
         if (oneshot && a.taps == 1 && a.Cin == 256) launch_oneshot<4>(a, grid, st);
         else if (oneshot && a.taps == 1 && a.Cin == 128) launch_oneshot<2>(a, grid, st);

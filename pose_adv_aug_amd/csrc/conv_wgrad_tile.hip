@@ -23,9 +23,6 @@
 #include <string.h>
 #include <hip/hip_ext.h>
 
-#define PA_WG_GROUP_DEFAULT 1
-#define PA_WGRAD_MINPER1_DEFAULT 1
-#define PA_WGRAD_MINPER9_DEFAULT 1
 // operand loads / slab stores of the weight gradients: PA_WG_NT = 1 marks them non-temporal (streamed once: do not keep them in L2 / the
 // Infinity Cache, where the main chain's freshly produced tensors live)
 #ifndef PA_WG_NT
@@ -494,7 +491,6 @@ __global__ __launch_bounds__(256, PIPE ? OCC : 2) void wgrad_tile_kernel(PaWgrad
 // Plain (two workgroups per CU, <= 244 registers) rather than pipelined bodies: 6.27 vs 6.31 ms per step -- a pipelined workgroup owns its
 // CU's registers, and the main chain's kernels then find no room beside the group.
 #define PA_WG_MAXJOBS 8
-#define PA_WG_RED_WGS_DEFAULT 256
 enum { PA_WGK_9_44 = 0, PA_WGK_9_44L, PA_WGK_1_44, PA_WGK_1_42, PA_WGK_1_24, PA_WGK_1_22, PA_WGK_N };      // 3x3 64 x 64 (n x c) with a plain / BatchNorm-backward dy operand (fixed modes: the 144-accumulator body has no registers to spare for both) | 1x1 128 x 128 | 128 x 64 | 64 x 128 | 64 x 64
 struct PaWgradGroup {
     PaWgradArgs a[PA_WG_MAXJOBS];
@@ -539,13 +535,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_group_kernel(PaWgradGroup g) {
 struct WgTileCfg { int nb, cb, ntiles, splits; };
 
 static bool wg_tile_cfg(int B, int H, int W, int Cin, int Cout, int taps, WgTileCfg& c) {
-    static int off = -1, target1 = 0, target9 = 0;
-    if (off < 0) {
-        off = pa_getenv("PA_WGRAD_OLD") ? 1 : 0;
-        const char* e = pa_getenv("PA_WGRAD_WGS1"); target1 = e ? atoi(e) : 256;
-        e = pa_getenv("PA_WGRAD_WGS9"); target9 = e ? atoi(e) : 256;
-    }
-    if (off || H <= 0 || W <= 0) return false;
+    const PaTuning& t = pa_tuning();
+    if (t.wgrad_old || H <= 0 || W <= 0) return false;
     const int M = B * H * W;
     if (taps == 9) {
         if (Cin % 64 || Cout % 64 || H % 8 || W % 16) return false;
@@ -554,27 +545,13 @@ static bool wg_tile_cfg(int B, int H, int W, int Cin, int Cout, int taps, WgTile
     } else if (taps == 1) {
         if (Cin % 64 || Cout % 64) return false;
         c.nb = Cout % 128 == 0 ? 128 : 64; c.cb = Cin % 128 == 0 ? 128 : 64; c.ntiles = (M + 127) / 128;
-        static int min1 = -1;
-        if (min1 < 0) min1 = pa_getenv("PA_WGRAD_MIN1") ? atoi(pa_getenv("PA_WGRAD_MIN1")) : 3;      // also the 16x16 ... 4x4 levels: 6.90 vs 6.97 ms (96)
-        if (c.ntiles < min1) return false;
+        if (c.ntiles < t.wgrad_min1) return false;      // (3: also the 16x16 ... 4x4 levels: 6.90 vs 6.97 ms (96))
     } else return false;
     const int types = (Cout / c.nb) * (Cin / c.cb);
-    int s = (taps == 9 ? target9 : target1) / types;
+    int s = (taps == 9 ? t.wgrad_wgs9 : t.wgrad_wgs1) / types;
     if (s < 1) s = 1;
     if (s > c.ntiles) s = c.ntiles;
-    int per = (c.ntiles + s - 1) / s;                // tiles per workgroup
-    // fewer, longer splits: a pipelined workgroup (PIPE above) runs at its MFMA / per-CU load rate from the second tile on, so a launch
-    // of few workgroups with many tiles each takes about as long as one that spreads the same tiles over every CU -- on a fraction of
-    // the CUs and with that fraction of the fp32 slabs (at 32x32 and below the slabs were 3 - 9 x the operand bytes)
-    static int minper1 = -1, minper9 = -1;
-    if (minper1 < 0) {
-        const char* e = pa_getenv("PA_WGRAD_MINPER"); const int both = e ? atoi(e) : 0;
-        e = pa_getenv("PA_WGRAD_MINPER1"); minper1 = e ? atoi(e) : (both ? both : PA_WGRAD_MINPER1_DEFAULT);
-        e = pa_getenv("PA_WGRAD_MINPER9"); minper9 = e ? atoi(e) : (both ? both : PA_WGRAD_MINPER9_DEFAULT);
-    }
-    const int minper = taps == 9 ? minper9 : minper1;
-    if (per < minper) per = minper;
-    if (per > c.ntiles) per = c.ntiles;
+    const int per = (c.ntiles + s - 1) / s;          // tiles per workgroup
     c.splits = (c.ntiles + per - 1) / per;           // balanced
     return true;
 }
@@ -591,7 +568,7 @@ int pa_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout, int taps) {
 static thread_local unsigned g_wt_launch_flags = 0;
 void pa_wgrad_set_launch_flags(unsigned flags) { g_wt_launch_flags = flags; }
 
-template <int TAPS, int NF, int CF, int WNW, bool PIPE, int OCC = 1>
+template <int TAPS, int NF, int CF, int WNW, bool PIPE>
 static void launch_wt_modes2(const PaWgradArgs& a, dim3 grid, int ntiles, hipStream_t st) {
     const bool lin2 = a.dy.mode == PA_LD_LIN2, bnrelu = a.x.mode == PA_LD_BNRELU;
     constexpr bool DB = TAPS == 1;          // bias gradients: only convs without a BatchNorm behind them (all 1x1 here)
@@ -600,41 +577,28 @@ static void launch_wt_modes2(const PaWgradArgs& a, dim3 grid, int ntiles, hipStr
         if (fl) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, st, nullptr, nullptr, fl, a, ntiles);
         else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, a, ntiles);
     };
-    if (lin2 && bnrelu) go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_LIN2, PA_LD_BNRELU, DB, PIPE, OCC>);
-    else if (lin2) go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_LIN2, PA_LD_PLAIN, DB, PIPE, OCC>);
-    else if (bnrelu) go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_PLAIN, PA_LD_BNRELU, DB, PIPE, OCC>);
-    else go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_PLAIN, PA_LD_PLAIN, DB, PIPE, OCC>);
+    if (lin2 && bnrelu) go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_LIN2, PA_LD_BNRELU, DB, PIPE>);
+    else if (lin2) go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_LIN2, PA_LD_PLAIN, DB, PIPE>);
+    else if (bnrelu) go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_PLAIN, PA_LD_BNRELU, DB, PIPE>);
+    else go(wgrad_tile_kernel<TAPS, NF, CF, WNW, PA_LD_PLAIN, PA_LD_PLAIN, DB, PIPE>);
 }
 
 // the pipelined form wherever a workgroup walks over at least two tiles (one tile: nothing to prefetch, and the plain form's two
 // workgroups per CU are the better shape for launches with more workgroups than CUs)
 template <int TAPS, int NF, int CF, int WNW>
 static void launch_wt_modes(const PaWgradArgs& a, dim3 grid, int ntiles, hipStream_t st) {
-    static int nopipe = -1, occ = 1;
-    if (nopipe < 0) { nopipe = pa_getenv("PA_WGRAD_NOPIPE") ? 1 : 0; const char* e = pa_getenv("PA_WGRAD_PIPE_OCC"); occ = e ? atoi(e) : 1; }
-    if (!nopipe && ntiles >= 2 * (int)grid.x) {
-        if (occ == 2 && TAPS == 1) launch_wt_modes2<TAPS, NF, CF, WNW, true, TAPS == 1 ? 2 : 1>(a, grid, ntiles, st);      // (the 3x3 form spills at 256 registers)
-        else launch_wt_modes2<TAPS, NF, CF, WNW, true, 1>(a, grid, ntiles, st);
-    } else launch_wt_modes2<TAPS, NF, CF, WNW, false>(a, grid, ntiles, st);
+    if (!pa_tuning().wgrad_nopipe && ntiles >= 2 * (int)grid.x) launch_wt_modes2<TAPS, NF, CF, WNW, true>(a, grid, ntiles, st);
+    else launch_wt_modes2<TAPS, NF, CF, WNW, false>(a, grid, ntiles, st);
 }
 
 // 7x7/2 stem weight gradient on the tile kernel: NB = 64 output channels x CB = 256 patch elements per workgroup, dy read once
 int pa_launch_stem_wgrad_tile(const PaWgradArgs& a, hipStream_t st) {
-    static int off = -1;
-    if (off < 0) off = (pa_getenv("PA_WGRAD_OLD") || pa_getenv("PA_STEM_WGRAD_OLD")) ? 1 : 0;
+    const bool off = pa_tuning().wgrad_old || pa_tuning().stem_wgrad_old;
     const int M = a.B * a.H * a.W, ntiles = (M + 127) / 128;
     if (off || a.Cin != 256 || a.Cout != 64 || a.splits > ntiles) return -1;
     dim3 grid(a.splits, 1, 1);
-    // the pipelined form needs the CU to itself (297 registers): with the stem's 512 splits that is two rounds of workgroups, 95 us
-    // against 45 us for the plain form at two workgroups per CU (measured in the step, where this launch is the tail everything waits
-    // for); it pays at <= 256 splits only
-    static int pipe = -1;
-    if (pipe < 0) { const char* e = pa_getenv("PA_STEM_PIPE"); pipe = e ? atoi(e) : 0; if (pa_getenv("PA_WGRAD_NOPIPE")) pipe = 0; }
-    if (pipe && ntiles >= 2 * a.splits) {
-        if (a.dy.mode == PA_LD_LIN2) hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_LIN2, PA_WG_STEM, false, true>), grid, dim3(256), 0, st, a, ntiles);
-        else hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_PLAIN, PA_WG_STEM, false, true>), grid, dim3(256), 0, st, a, ntiles);
-        return (int)hipGetLastError();
-    }
+    // the plain form at two workgroups per CU: a pipelined one needs the CU to itself (297 registers) -- with the stem's 512 splits that is
+    // two rounds of workgroups, 95 us against 45 us (measured in the step, where this launch is the tail everything waits for)
     if (a.dy.mode == PA_LD_LIN2) hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_LIN2, PA_WG_STEM, false>), grid, dim3(256), 0, st, a, ntiles);
     else hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_PLAIN, PA_WG_STEM, false>), grid, dim3(256), 0, st, a, ntiles);
     return (int)hipGetLastError();
@@ -656,11 +620,7 @@ int pa_launch_wgrad_tile(const PaWgradArgs& a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------ grouped launch
-static int wg_group_on() {
-    static int on = -1;
-    if (on < 0) { const char* e = pa_getenv("PA_WG_GROUP"); on = e ? atoi(e) : PA_WG_GROUP_DEFAULT; }
-    return on;
-}
+static int wg_group_on() { return pa_tuning().wg_group; }
 
 static int wg_kind(const WgTileCfg& c, int taps, int pmode = PA_LD_PLAIN) {
     if (taps == 9) return (c.nb == 64 && c.cb == 64) ? (pmode == PA_LD_LIN2 ? PA_WGK_9_44L : PA_WGK_9_44) : -1;
@@ -678,16 +638,10 @@ int pa_wgrad_group_splits(int B, int H, int W, int Cin, int Cout, int taps) {
     if (!wg_group_on() || H <= 0 || W <= 0) return 0;
     WgTileCfg c;
     if (!wg_tile_cfg(B, H, W, Cin, Cout, taps, c) || wg_kind(c, taps) < 0) return 0;
-    static int wg9 = -1, wg1 = -1, mp9 = -1, mp1 = -1;
-    if (wg9 < 0) {
-        const char* e = pa_getenv("PA_WG_GROUP_WGS9"); wg9 = e ? atoi(e) : 64;
-        e = pa_getenv("PA_WG_GROUP_WGS1"); wg1 = e ? atoi(e) : 64;
-        e = pa_getenv("PA_WG_GROUP_MINPER9"); mp9 = e ? atoi(e) : 4;
-        e = pa_getenv("PA_WG_GROUP_MINPER1"); mp1 = e ? atoi(e) : 2;
-    }
+    const PaTuning& t = pa_tuning();
     const int types = (Cout / c.nb) * (Cin / c.cb);
-    int s = (taps == 9 ? wg9 : wg1) / types;
-    const int minper = taps == 9 ? mp9 : mp1;
+    int s = (taps == 9 ? t.wg_group_wgs9 : t.wg_group_wgs1) / types;
+    const int minper = taps == 9 ? t.wg_group_minper9 : t.wg_group_minper1;
     if (s * minper > c.ntiles) s = c.ntiles / minper;
     if (s < 1) s = 1;
     const int per = (c.ntiles + s - 1) / s;
@@ -736,8 +690,7 @@ int pa_launch_wgrad_group(const PaWgradArgs* const* as, int n, hipStream_t st, b
     }
     g.begin[n] = begin; g.njobs = n;
     if (red_n > 0) {
-        static int rw = -1;
-        if (rw < 0) { const char* e = pa_getenv("PA_WG_RED_WGS"); rw = e ? atoi(e) : PA_WG_RED_WGS_DEFAULT; if (rw < 1) rw = 1; }
+        const int rw = pa_tuning().wg_red_wgs < 1 ? 1 : pa_tuning().wg_red_wgs;
         g.red_jobs = red_jobs; g.red_n = red_n; g.red_wgs = rw;
         for (int i = 0; i < PA_RED_LIST_MAX; ++i) g.red.idx[i] = red_idx[i < red_n ? i : 0];
         begin += rw;

@@ -15,7 +15,7 @@
 #include <hip/hip_ext.h>
 // TIMING EXPERIMENT (tuning builds, PA_FIN_ANYORDER=1; results may be WRONG): the finalize launches without the completion / cache round trip
 // behind their producer (hipExtAnyOrderLaunch) -- what a tagged-row hand-off from the producers to the finalize kernel could return at most
-static unsigned fin_launch_flags() { static int v = -1; if (v < 0) { const char* e = pa_getenv("PA_FIN_ANYORDER"); v = e ? atoi(e) : 0; } return v ? hipExtAnyOrderLaunch : 0u; }
+static unsigned fin_launch_flags() { return pa_tuning().fin_anyorder ? hipExtAnyOrderLaunch : 0u; }
 
 // ------------------------------------------------------------------------------------------------
 // BatchNorm bookkeeping (reference semantics: torch.nn.BatchNorm2d, eps 1e-5, momentum 0.1,
@@ -24,17 +24,13 @@ static unsigned fin_launch_flags() { static int v = -1; if (v < 0) { const char*
 // FC channels x (FT / FC) row slices, float2 loads, LDS tree over the slices.  Result in LDS sums[FC][2].
 // FC = 8: 16-32 workgroups per BatchNorm (the kernel is pure latency: launch + row loads in batches + tree; 32 channels per workgroup
 // took 6 us; FC = 4 -- every common row count in ONE batch of loads, twice the workgroups -- measured 0.03 ms per step slower, round 4).
-// workgroup shape of the finalize launches: FT threads = FC channels x FT / FC row slices (tuning builds: PA_FIN_THREADS, PA_FIN_FC)
+// workgroup shape of the finalize launches: FT threads = FC channels x FT / FC row slices
 template <class F>
 static void fin_dispatch(F f) {
     // 512 threads (8 channels x 64 row slices): measured 6.44 - 6.49 ms per step against 6.50 - 6.54 with 1024-thread workgroups (three
     // interleaved pairs; 256 threads, or 4 channels per workgroup: the same as 512 / 8) -- a 1024-thread workgroup has to find a whole CU's
     // worth of wave slots next to the other queues' kernels, and the launch is all these kernels are
-    static int ft = -1;
-    if (ft < 0) { const char* e = pa_getenv("PA_FIN_THREADS"); ft = e ? atoi(e) : 512; }
-    if (ft == 256) f(std::integral_constant<int, 256>{}, std::integral_constant<int, 8>{});
-    else if (ft == 1024) f(std::integral_constant<int, 1024>{}, std::integral_constant<int, 8>{});
-    else f(std::integral_constant<int, 512>{}, std::integral_constant<int, 8>{});
+    f(std::integral_constant<int, 512>{}, std::integral_constant<int, 8>{});
 }
 template <int FT, int FC>
 __device__ __forceinline__ void reduce_partial_rows(const float* part, int rows, int C, int c0, float (*sums)[2]) {
@@ -445,8 +441,7 @@ __global__ __launch_bounds__(256) void pool_up_fwd_s_kernel(PaOperand a, PaOpera
 // returns false when the configuration is not covered (caller uses the generic kernel)
 template <int OP>
 static bool launch_pool_up_fwd_s(const PaOperand& a, const PaOperand& b, bf16* out, int B, int H, int W, int C, hipStream_t st) {
-    static int old = -1;
-    if (old < 0) old = pa_getenv("PA_ELTWISE_OLD") ? 1 : 0;
+    const bool old = pa_tuning().eltwise_old != 0;
     const int threads = 256;
     const size_t row_items = (size_t)(W / 2) * (C / 8);
     const bool ma = a.mode == PA_LD_PLAIN || a.mode == PA_LD_BNRELU, mb = OP == 0 || b.mode == PA_LD_PLAIN || b.mode == PA_LD_BNRELU;
@@ -479,12 +474,10 @@ int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, i
 // them still keep enough loads in flight (256-thread ones, measured ALONE, left HBM half idle: 3.3 TB/s vs 6+ TB/s for a plain copy of the
 // same size).
 static inline void stream_launch_dims(size_t total, int& blocks, int& threads) {
-    static int big = -1;
     // 512 threads for the big tensors (1024 until round 4: 6.465 vs 6.434 ms per step over three interleaved pairs -- a 1024-thread
     // workgroup needs a whole CU's wave slots at once next to the other queues' kernels; 512 workgroups x 512 threads x 9 loads of 16 bytes are
     // still 38 MB in flight)
-    if (big < 0) { const char* e = pa_getenv("PA_STREAM_THREADS"); big = e ? atoi(e) : 512; }
-    threads = total >= (size_t)512 * 1024 ? big : 256;
+    threads = total >= (size_t)512 * 1024 ? 512 : 256;
     blocks = (int)((total + threads - 1) / threads);
     if (blocks > 512) blocks = 512;          // one partial-statistics row per workgroup
     if (blocks < 1) blocks = 1;
@@ -643,8 +636,7 @@ int pa_launch_maxpool_bwd(const bf16* dout, const PaOperand& in, const PaOperand
     if (stat_rows) *stat_rows = blocks;
     if (ep.rows_out) *ep.rows_out = blocks;
     {
-        static int old = -1;
-        if (old < 0) old = pa_getenv("PA_ELTWISE_OLD") ? 1 : 0;
+        const bool old = pa_tuning().eltwise_old != 0;
         const size_t row_items = (size_t)(W / 2) * (C / 8);
         const bool in_ok = in.mode == PA_LD_PLAIN || in.mode == PA_LD_BNRELU;
         const bool add_ok = add.mode == PA_LD_NONE || add.mode == PA_LD_PLAIN;
@@ -812,7 +804,7 @@ bool pa_upadd_bwd_splits(const PaEpilogue& ep_low, const PaEpilogue& ep_skip, in
     stream_launch_dims(total, blocks, threads);
     fit_threads_to_rows(threads, W, C);
     const size_t row_items = (size_t)(W / 2) * (C / 8);
-    return !pa_getenv("PA_ELTWISE_OLD") && ep_low.mode == PA_OUT_BWD && ep_skip.mode == PA_OUT_BWD && threads % (C / 8) == 0 &&
+    return !pa_tuning().eltwise_old && ep_low.mode == PA_OUT_BWD && ep_skip.mode == PA_OUT_BWD && threads % (C / 8) == 0 &&
            (row_items % threads == 0 || threads % row_items == 0) && (size_t)B * H * W * C < ((size_t)1 << 31);
 }
 
@@ -832,8 +824,7 @@ int pa_launch_upadd_bwd(const bf16* dout, const PaEpilogue& ep_low, bf16* dlow, 
         else hipLaunchKernelGGL((upadd_bwd_bb_kernel<false, true>), dim3(blocks), dim3(threads), lds, st, dout, ep_low, dlow, ep_skip, dskip, B * (H / 2), W, C);
         return (int)hipGetLastError();
     }
-    static int old = -1;
-    if (old < 0) old = pa_getenv("PA_ELTWISE_OLD") ? 1 : 0;
+    const bool old = pa_tuning().eltwise_old != 0;
     const size_t row_items = (size_t)(W / 2) * (C / 8);
     if (!old && ep_low.mode == PA_OUT_BWD && ep_skip.mode == PA_OUT_BWD && threads % (C / 8) == 0 &&
         (row_items % threads == 0 || threads % row_items == 0) && (size_t)B * H * W * C < ((size_t)1 << 31)) {

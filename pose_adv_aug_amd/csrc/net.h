@@ -106,8 +106,7 @@ struct Residual {
     const Act* low_of_in = nullptr;
     bool low_fused = false;
     int b3_rows_scale = 1;   // partial-row capacity of bn3's backward reductions in units of this block's own map (4: the rows may come from a launch over the 2x larger map)
-    int bwd_a(Net& n, const Act& in, const PaOperand* extra = nullptr);    // everything except the input gradient (extra: known already -- lets the adapter's data gradient start early)
-    bool ad_forked = false;                                            // the adapter's data gradient of this backward pass runs on the side stream
+    int bwd_a(Net& n, const Act& in);                                  // everything except the input gradient
     int bwd_b(Net& n, const Act& in, const PaOperand& extra);           // input gradient (needs `extra`)
 };
 
@@ -148,57 +147,37 @@ struct Net {
     // device job tables
     PaPrepJob* prep_jobs = nullptr; int n_prep = 0, prep_max = 0;
     PaWgradReduceJob* red_jobs = nullptr; int n_red = 0, red_max = 0;
-    // ONE slab buffer shared by all layers: each weight-gradient launch is reduced right away, while its slabs are
-    // still in the 256 MB Infinity Cache, and the next layer overwrites the same lines
-    float* shared_part = nullptr; float* shared_db = nullptr; size_t shared_part_floats = 0, shared_db_floats = 0;
-    bool immediate_reduce = false;     // measured on MI355X: +0.55 ms/step (100 extra launches) vs one deferred reduce, so off
     PaBnEvalJob* bneval_jobs = nullptr; int n_bneval = 0;
     // run state
     hipStream_t st = nullptr;
-    // side streams: the skip branch of hourglass level k runs on side[k] next to the low-resolution path
-    // (tiny, latency-bound kernels that leave most CUs idle); fork/join by events, joined before the call returns
-    hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};
+    // side stream: the skip branch of every hourglass level runs on `side` next to the low-resolution path (tiny, latency-bound kernels
+    // that leave most CUs idle); fork / join by one event pair per level, joined before the call returns.  ONE stream for all four skip
+    // branches: main + side + weight-gradient stream = 3 hardware queues (the runtime has 4)
+    hipStream_t side = nullptr;
     hipEvent_t ev_fork[4], ev_join[4];
-    bool streams_ready = false, multi_stream = true;
-    // distinct side streams (PA_SIDE_STREAMS); level k uses side[k % n_side].  ONE stream for all four skip branches measured
-    // best (3128 vs 3090 img/s with four): main + side + weight-gradient stream = 3 hardware queues (the runtime has 4)
-    int n_side = 1;
-    int fork_mask = 0xF;                       // bit k: hourglass level k forks its skip block (PA_FORK_LEVELS)
-    bool forks(int k) const { return multi_stream && ((fork_mask >> k) & 1); }
-    // adapter convolutions of residual1 / residual3 on the side stream beside the block's main path (only outside a side branch, with the
-    // streams on).  Measured round 5: 5.917 vs 5.892 ms with them on the main chain (three interleaved pairs) -- the two event pairs per
-    // block cost more than the 38 + 78 us of hidden kernels return beside the weight-gradient queue; OFF, switch in tuning builds
-    bool adapter_parallel() const {
-        static int on = -1;
-        if (on < 0) { const char* e = pa_getenv("PA_ADAPTER_PAR"); on = e ? atoi(e) : 0; }
-        return on && multi_stream && side[0] != nullptr && !on_side;
-    }
-    // weight-gradient launches only feed the slab reducer at the end of the backward pass: they run on their own
-    // stream behind an event recorded where their operands are final, off the dgrad / BatchNorm critical chain
+    bool streams_ready = false, multi_stream = !pa_tuning().single_stream;
+    // weight-gradient launches only feed the slab reducer: they run on their own stream behind an event recorded where their operands
+    // are final, off the dgrad / BatchNorm critical chain
     hipStream_t wstream = nullptr;
-    hipStream_t wstreams[4] = {nullptr, nullptr, nullptr, nullptr}; int n_w = 1, w_rr = 0;   // wstream == wstreams[0]; groups go round robin
-    hipEvent_t ev_wdone_x[4];
+    bool wgrads_aside() const { return multi_stream && wstream != nullptr; }      // the weight gradients run on wstream
     hipEvent_t ev_w[16]; int ev_w_next = 0;
     hipEvent_t ev_wdone;
     // weight-gradient launches are collected and flushed in groups: ONE event record on the producing stream per group
     // (an event record between two kernels of a queue costs a 15-20 us bubble on it: ~100 records per step were 1.5 ms)
     struct PendingWgrad { PaWgradArgs a; int cls; double bytes, flops; bool stem; ConvLayer* c; };
-    // the slabs of a group are summed right behind it on the weight-gradient stream (part of them still in the 256 MB
-    // Infinity Cache) instead of by one 280 us reduction on the main stream at the end of the step: +1.1 % (PA_WREDUCE_LATE = old)
-    bool reduce_early = true;
+    // with a weight-gradient stream, the slabs of a group are summed right behind it on that stream (part of them still in the 256 MB
+    // Infinity Cache) instead of by one 280 us reduction on the main stream at the end of the step
     std::vector<PendingWgrad> pending_wgrads;
-    int flush_every = 1, flush_ctr = 0; bool on_side = false;   // main-stream blocks flush every flush_every-th time (PA_WFLUSH_EVERY)
+    bool on_side = false;                      // the launches being enqueued belong to a side branch (StreamScope)
     int flush_wgrads();                        // record on `st`, make wstream wait, launch the collected weight gradients
+    int launch_pending_wgrads();               // its body; flush_wgrads() empties the list (and on an error the stash) behind it
     std::vector<int> red_stash; int red_stash_mx = 0, red_stash_flushes = 0;      // reduce-table indices of flushed layers whose slabs are not summed yet
     int flush_red_stash(hipStream_t ws);       // one reduction launch for the stash
-    // hold the weight gradients of an hourglass' high-resolution levels back until its backward pass reaches level `hold_level`
-    // (the low-resolution stretch, where the main chain leaves the GPU almost empty): 0 = off
-    int hold_level = 0; bool hold = false;
-    int release_held(int k);
+    void drop_wgrads();                        // error exits: forget the collected launches and the stash
     int ensure_streams();
     void release_streams();                    // destroys the side streams / events (pa_net_destroy)
-    int fork_to(int k);                        // side[k] waits for everything enqueued on st so far
-    int record_join(int k);                    // mark the end of the work enqueued on side[k]
+    int fork_to(int k);                        // level k's branch on the side stream waits for everything enqueued on st so far
+    int record_join(int k);                    // mark the end of that branch
     int wait_join(int k);                      // st waits for that mark
     Prof prof;
     // bytes this design moves (pa_net_design_bytes): operands of every launch since begin_step(), counted once per launch
@@ -250,7 +229,6 @@ struct Net {
     void declare_bn(BNLayer& b, const std::string& name, int C);
     void layout_conv(ConvLayer& c, Arena& a, int M, int H = 0, int W = 0);
     void layout_bn(BNLayer& b, Arena& a, int M);
-    void layout_shared(Arena& a);                  // call last in every layout pass
     Act new_act(Arena& a, int B, int H, int W, int C, BNLayer* bn, bool need_grad);
 
     void declare_pose();
@@ -273,8 +251,8 @@ struct Net {
                    const Act* low = nullptr, bool* low_done = nullptr);      // low: also emit the upsample-add backward's low-resolution output (Residual::low_of_in)
     // BatchNorm finalize in the consumer's prologue for launches with at most this many partial rows (the 16 x 16 and smaller levels;
     // 0 = always a launch of its own).  Same bits either way (bn_fin.h)
-    int fin_rows_max = PA_FIN_SMALL_ROWS;
-    int fin_mask = 7;       // which finalizes may ride in a consumer: 1 forward x1 / x2, 2 backward x2, 4 backward x3 (PA_FIN_MASK in tuning builds)
+    int fin_rows_max = pa_tuning().fin_prologue > PA_FIN_SMALL_ROWS ? PA_FIN_SMALL_ROWS : pa_tuning().fin_prologue;
+    int fin_mask = pa_tuning().fin_mask;       // which finalizes may ride in a consumer: 1 forward x1 / x2, 2 backward x2, 4 backward x3
     bool fin_consumer_ok(const ConvLayer& c, int B, int H, int W, bool dgrad) const;
     PaBnFin fin_fwd(const BNLayer& b, int M) const;
     PaBnFin fin_bwd(const BNLayer& b, int M) const;

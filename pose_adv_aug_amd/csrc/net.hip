@@ -5,22 +5,13 @@
 #include <stdio.h>
 #include <string.h>
 
-// (the round-1 timing experiment that removed cross-stream waits -- wrong results by design -- is gone from the library)
-static const int g_nosync = 0;
-static bool nosync() { return false; }
 // PA_ABLATE=<mask> (tuning builds only; results are WRONG, timing bounds only): 1 no slab reductions, 2 no weight-gradient
 // launches, 4 no BatchNorm finalize launches, 8 no 3x3 convolutions, 16 no 1x1 data gradients; 1024 no upsample-add backward, 2048 no
 // pooling backward, 4096 no pooling / upsample-add forward (bounds of what fusing them into their neighbours can return)
-static int ablate() { static int v = -1; if (v < 0) { const char* e = pa_getenv("PA_ABLATE"); v = e ? atoi(e) : 0; } return v; }
+static int ablate() { return pa_tuning().ablate; }
 // bits 128 / 256 / 512: forward convolutions + finalize / data gradients + backward finalize / weight gradients of maps up to
 // PA_ABLATE_H (default 8) pixels high are skipped: what the low-resolution stretch costs the step at most (wrong results)
-static int ablate_h() { static int v = -1; if (v < 0) { const char* e = pa_getenv("PA_ABLATE_H"); v = e ? atoi(e) : 8; } return v; }
-#define PA_STEM_ON_MAIN_DEFAULT 1
-#define PA_WG_GROUP_CAP_DEFAULT 256
-#define PA_WREDUCE_LAG_DEFAULT 2
-#define PA_UPADD_SPLIT_DEFAULT 1
-#define PA_UPADD_FUSE_DEFAULT 1
-#define PA_WG_RED_IN_GROUP_DEFAULT 1
+static int ablate_h() { return pa_tuning().ablate_h; }
 #define TRY(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 PaOperand pa_plain(const bf16* p) { PaOperand o; o.p = p; o.q = nullptr; o.k0 = o.k1 = o.k2 = nullptr; o.mode = PA_LD_PLAIN; return o; }
@@ -129,26 +120,13 @@ void Net::layout_conv(ConvLayer& c, Arena& a, int M, int H, int W) {
         if (gs > 0) c.splits = gs;
     }
     if (c.k == 7) {                              // stem: 64 KB slabs, so two workgroups per CU (their load / MFMA phases overlap)
-        static int ss = -1;
-        if (ss < 0) { const char* e = pa_getenv("PA_STEM_SPLITS"); ss = e ? atoi(e) : 512; }       // 6.96 vs 7.00 ms (256)
+        const int ss = pa_tuning().stem_splits;       // 512: 6.96 vs 7.00 ms (256)
         if (ss > 0 && ss <= (M + 127) / 128) c.splits = ss;
     }
     c.part_floats = (size_t)c.splits * wn;
     c.db_floats = c.has_bn_after ? 0 : (size_t)c.splits * c.pcout;
-    if (immediate_reduce) {                   // shared slab: remember the largest request, bind after the layout pass
-        if (c.part_floats > shared_part_floats) shared_part_floats = c.part_floats;
-        if (c.db_floats > shared_db_floats) shared_db_floats = c.db_floats;
-        c.part = nullptr; c.dbpart = nullptr;
-    } else {
-        c.part = a.get<float>(c.part_floats);
-        c.dbpart = c.db_floats ? a.get<float>(c.db_floats) : nullptr;
-    }
-}
-
-void Net::layout_shared(Arena& a) {
-    if (!immediate_reduce) return;
-    shared_part = a.get<float>(shared_part_floats);
-    shared_db = a.get<float>(shared_db_floats > 0 ? shared_db_floats : 1);
+    c.part = a.get<float>(c.part_floats);
+    c.dbpart = c.db_floats ? a.get<float>(c.db_floats) : nullptr;
 }
 
 void Net::layout_bn(BNLayer& b, Arena& a, int M) {
@@ -247,7 +225,6 @@ size_t Net::layout_all(char* base) {
         if (i == 0) xin[0] = res3.x3;
         if (i + 1 < stacks) xin[i + 1] = new_act(a, B, H4, H4, chan, nullptr, true);
     }
-    layout_shared(a);
     a.take(0);
     return a.off;
 }
@@ -256,7 +233,6 @@ int Net::upload_tables() {
     std::vector<PaPrepJob> pj; std::vector<PaWgradReduceJob> rj; std::vector<PaBnEvalJob> bj;
     prep_max = 0; red_max = 0;
     for (ConvLayer* c : convs) {
-        if (immediate_reduce) { c->part = shared_part; c->dbpart = c->db_floats ? shared_db : nullptr; }
         PaPrepJob p; p.w = params + c->p_w; p.wf = c->wf; p.wb = c->wb; p.Cout = c->Cout; p.Cin = c->Cin;
         p.taps = c->k == 7 ? 49 : c->taps(); p.pad_cout = c->pcout; p.pad_cin = c->pcin;
         pj.push_back(p);
@@ -447,18 +423,15 @@ int Net::conv_dgrad(ConvLayer& c, const PaOperand& dy, int B_, int H, int W, con
     a.B = B_; a.H = H; a.W = W; a.Cin = c.pcout; a.Cout = c.pcin; a.taps = c.taps();
     if (dz_done) *dz_done = false;
     if (dz_out && dy.mode == PA_LD_LIN2) {         // only the 1x1 row-tile kernel stores its transformed input
-        static int off = -1;
-        if (off < 0) off = (pa_getenv("PA_CONV1_OLD") || pa_getenv("PA_NO_DZ3")) ? 1 : 0;
-        static int off3 = -1;
-        if (off3 < 0) off3 = (pa_getenv("PA_CONV3_OLD") || pa_getenv("PA_NO_DZ2")) ? 1 : 0;
+        const PaTuning& t = pa_tuning();
+        const bool off = t.conv1_old || t.no_dz3, off3 = t.conv3_old || t.no_dz2;
         if ((!off && a.taps == 1 && pa_conv1x1_tile_supported(a)) || (!off3 && a.taps == 9 && pa_conv3x3_tile_supported(a))) { a.dz_out = dz_out; if (dz_done) *dz_done = true; }
     }
     double wb, wf; conv_work(B_ * H * W, c.Cin, c.Cout, c.taps(), false, wb, wf);
     ProfEntry* pe = prof.begin((long)B_ * H * W < PA_PROF_LOW_M ? PA_PROF_LOW_DGRAD : (c.k == 3 ? PA_PROF_DGRAD3 : PA_PROF_DGRAD1), wb, wf, st);
     if ((c.k == 3 && (ablate() & 8)) || (c.k == 1 && (ablate() & 16)) || ((ablate() & 256) && H <= ablate_h())) { if (a.ep.rows_out) *a.ep.rows_out = 1; prof.end(pe, st); return 0; }
-    // the low-resolution half of the upsample-add backward in this launch's epilogue (round 6)
-    static int up_fuse = -1;
-    if (up_fuse < 0) { const char* e = pa_getenv("PA_UPADD_FUSE"); up_fuse = e ? atoi(e) : PA_UPADD_FUSE_DEFAULT; }
+    // the low-resolution half of the upsample-add backward in this launch's epilogue (round 6): an instance of the row-tile 1x1 kernel
+    const bool up_fuse = pa_tuning().upadd_fuse && !pa_tuning().conv1_old;
     bool up = false;
     if (low && up_fuse && low->bn && !drop_mask && !(ablate() & 1024)) {
         a.out2 = low->grad; a.ep2 = final_ep(*low);
@@ -487,15 +460,14 @@ int Net::conv_wgrad(ConvLayer& c, const PaOperand& dy, const PaOperand& x, int B
     if ((ablate() & 512) && H <= ablate_h()) return 0;
     { const double M = (double)B_ * H * W, slab = 4.0 * (double)c.splits * a.Cout * a.taps * a.Cin;      // slabs written, read back by the reducer, gradient written
       cnt((c.k == 7 ? 2.0 * B_ * 4.0 * H * W * 4 : opb(x, M * a.Cin)) + opb(dy, M * a.Cout) + slab, slab + 4.0 * a.Cout * a.taps * a.Cin); }
-    static int stem_main = -1;
-    if (stem_main < 0) { const char* e = pa_getenv("PA_STEM_ON_MAIN"); stem_main = e ? atoi(e) : PA_STEM_ON_MAIN_DEFAULT; }
-    // (the stem's weight gradient is the last launch of the step: on the main stream, idle by then, it runs beside the weight-gradient
-    // queue's last reduction instead of behind it)
-    // single-stream mode (bench.py's roofline leg, debugging): the launches the grouped kernel takes are collected too and leave as the
-    // same group launches on the caller's stream -- per-class event times and the bitwise comparison of the stream modes then see the
-    // kernels of the real step
-    const bool defer_single = !(multi_stream && wstream) && !immediate_reduce && c.k != 7 && pa_wgrad_group_takes(a);
-    if (defer_single || (multi_stream && wstream && !(c.k == 7 && stem_main && reduce_early && !immediate_reduce))) {        // deferred: flush_wgrads() launches it (on the weight-gradient stream)
+    // With a weight-gradient stream every launch is collected and leaves in flush_wgrads() on that stream -- except the stem's, the last
+    // launch of the step: on the main stream, idle by then, it runs beside the weight-gradient queue's last reduction instead of behind it.
+    // Without one (single-stream mode: bench.py's roofline leg, debugging) the launches the grouped kernel takes are collected too and
+    // leave as the same group launches on the caller's stream -- per-class event times and the bitwise comparison of the stream modes
+    // then see the kernels of the real step; the others are launched here and summed by reduce_grads().
+    const bool aside = wgrads_aside();
+    const bool stem_now = c.k == 7 && aside && pa_tuning().stem_on_main;
+    if (aside ? !stem_now : (c.k != 7 && pa_wgrad_group_takes(a))) {
         PendingWgrad p; p.a = a; p.cls = cls; p.bytes = wb; p.flops = wf; p.stem = c.k == 7; p.c = &c;
         pending_wgrads.push_back(p);
         return 0;
@@ -504,29 +476,8 @@ int Net::conv_wgrad(ConvLayer& c, const PaOperand& dy, const PaOperand& x, int B
     int rc = (c.k == 7) ? pa_launch_stem_wgrad(a, st) : pa_launch_wgrad(a, st);
     prof.end(pe, st);
     if (rc) return rc;
-    if (c.k == 7 && multi_stream && wstream && stem_main && reduce_early && !immediate_reduce) {
-        TRY(pa_launch_stem_wgrad_reduce(c.part, c.splits, grads + c.p_w, st, grads + c.p_b));
-        return 0;
-    }
-    if (immediate_reduce) {
-        if (c.k == 7) {
-            TRY(pa_launch_stem_wgrad_reduce(c.part, c.splits, grads + c.p_w, st, grads + c.p_b));
-        } else {
-            TRY(pa_launch_wgrad_reduce(red_jobs + c.red_index, 1, c.Cout * c.Cin * c.taps() + c.Cout, st));
-        }
-    }
+    if (stem_now) TRY(pa_launch_stem_wgrad_reduce(c.part, c.splits, grads + c.p_w, st, grads + c.p_b));
     return 0;
-}
-
-// Operands of the collected launches are final on `st` at this point (their producers were enqueued before).  The
-// gradient buffers they read are written once per step, so deferring a launch is always safe.
-int Net::release_held(int k) {
-    if (!hold) return 0;
-    hold = false;
-    hipStream_t ws = wstreams[w_rr];
-    for (int kk = 0; kk < k && kk < 4; ++kk)          // the held groups of the skip branches: their operands are final at ev_join[kk]
-        if (forks(kk)) PA_CHECK(hipStreamWaitEvent(ws, ev_join[kk], 0));
-    return flush_wgrads();
 }
 
 int Net::flush_red_stash(hipStream_t ws) {
@@ -537,107 +488,103 @@ int Net::flush_red_stash(hipStream_t ws) {
     return rc;
 }
 
+void Net::drop_wgrads() {
+    pending_wgrads.clear();
+    red_stash.clear(); red_stash_mx = 0; red_stash_flushes = 0;
+}
+
+// Operands of the collected launches are final on `st` at this point (their producers were enqueued before).  The
+// gradient buffers they read are written once per step, so deferring a launch is always safe.
 int Net::flush_wgrads() {
-    if (pending_wgrads.empty() || hold) return 0;
-    const bool ms = multi_stream && wstream;
-    hipStream_t ws = ms ? wstreams[w_rr] : st;
-    if (ms) w_rr = (w_rr + 1) % n_w;
-    if (ms && !(nosync() && (g_nosync & 4))) {
+    if (pending_wgrads.empty()) return 0;
+    const int rc = launch_pending_wgrads();
+    if (rc) drop_wgrads(); else pending_wgrads.clear();
+    return rc;
+}
+
+int Net::launch_pending_wgrads() {
+    const PaTuning& t = pa_tuning();
+    const bool aside = wgrads_aside();
+    hipStream_t ws = aside ? wstream : st;
+    if (aside) {
         hipEvent_t ev = ev_w[ev_w_next]; ev_w_next = (ev_w_next + 1) & 15;
         PA_CHECK(hipEventRecord(ev, st));
         PA_CHECK(hipStreamWaitEvent(ws, ev, 0));
     }
-    // the launches of a group share no data: from the second on they need no completion / cache round trip behind their predecessor
-    // (hipExtAnyOrderLaunch, conv_wgrad_tile.hip; not with the per-launch event timing, not with one slab shared by all layers, and not
-    // inside a stream capture -- the engine's own or a caller's around pa_hg_backward: an extension launch cannot be captured)
-    static int any_order = -1;
-    if (any_order < 0) { const char* e = pa_getenv("PA_WGRAD_ANYORDER"); any_order = e ? atoi(e) : 1; }
-    bool in_capture = capturing;
-    if (!in_capture) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(ws, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) in_capture = true;
-    }
+    // slabs are summed on the weight-gradient stream as the step goes: the layers of a flush join the stash, and the stash is summed by a
+    // few more workgroups of a LATER group launch of this stream (in_group) or by a launch of its own
+    const bool stash = aside && !(ablate() & 1), in_group = t.wg_red_in_group != 0;
     bool first = true;
     // every launch of the list the grouped kernel takes goes into group launches of up to 8 jobs (also while the per-launch event timing
     // runs: a group launch counts for the class of its largest job); the others -- the stem, shapes of the generic kernel -- are launched
     // one by one behind them
     std::vector<char> grouped(pending_wgrads.size(), 0);
-    if (!immediate_reduce) {
-        const PaWgradArgs* jobs[8]; int jidx[8]; int nj = 0;
-        auto fire = [&]() -> int {
-            if (nj == 0) return 0;
-            // (event timing: the launch counts for the class of its largest job, with the bytes / flops of all of them)
-            int big = 0; double bytes = 0.0, flops = 0.0;
-            for (int j = 0; j < nj; ++j) {
-                const PendingWgrad& q = pending_wgrads[jidx[j]];
-                bytes += q.bytes; flops += q.flops;
-                if (q.flops > pending_wgrads[jidx[big]].flops) big = j;
-            }
-            ProfEntry* pe = prof.begin(pending_wgrads[jidx[big]].cls, bytes, flops, ws);
-            // the slabs of EARLIER flushes (the stash) are summed by a few more workgroups of this launch instead of by a launch of their own
-            static int red_in_group = -1;
-            if (red_in_group < 0) { const char* e = pa_getenv("PA_WG_RED_IN_GROUP"); red_in_group = e ? atoi(e) : PA_WG_RED_IN_GROUP_DEFAULT; }
-            const bool carry = red_in_group && ms && n_w == 1 && reduce_early && !(ablate() & 1) && !red_stash.empty();      // (one weight-gradient stream: the stash's slabs were written on THIS stream)
-            const int rc = (nj == 1 && !carry) ? pa_launch_wgrad(*jobs[0], ws)
-                                               : pa_launch_wgrad_group(jobs, nj, ws, false, red_jobs, carry ? red_stash.data() : nullptr, carry ? (int)red_stash.size() : 0);
-            if (carry && !rc) { red_stash.clear(); red_stash_mx = 0; red_stash_flushes = 0; }
-            prof.end(pe, ws);
-            nj = 0; first = false;
-            return rc;
-        };
-        // a group launch is capped at `cap` workgroups: its workgroups live for tens of microseconds with 242 registers each, two of them
-        // close a CU to every other queue -- a launch of <= 256 leaves room for a workgroup of the main chain beside it on every CU
-        static int cap = -1;
-        if (cap < 0) { const char* e = pa_getenv("PA_WG_GROUP_CAP"); cap = e ? atoi(e) : PA_WG_GROUP_CAP_DEFAULT; }
-        int wgs = 0;
-        for (size_t pi = 0; pi < pending_wgrads.size(); ++pi) {
-            PendingWgrad& p = pending_wgrads[pi];
-            if (p.stem || !pa_wgrad_group_takes(p.a)) continue;
-            const int w = pa_wgrad_job_workgroups(p.a);
-            if (nj > 0 && (nj == 8 || wgs + w > cap)) { const int rc = fire(); if (rc) { pending_wgrads.clear(); return rc; } wgs = 0; }
-            grouped[pi] = 1;
-            jidx[nj] = (int)pi;
-            jobs[nj++] = &p.a;
-            wgs += w;
+    const PaWgradArgs* jobs[8]; int jidx[8]; int nj = 0;
+    auto fire = [&]() -> int {
+        if (nj == 0) return 0;
+        // (event timing: the launch counts for the class of its largest job, with the bytes / flops of all of them)
+        int big = 0; double bytes = 0.0, flops = 0.0;
+        for (int j = 0; j < nj; ++j) {
+            const PendingWgrad& q = pending_wgrads[jidx[j]];
+            bytes += q.bytes; flops += q.flops;
+            if (q.flops > pending_wgrads[jidx[big]].flops) big = j;
         }
-        { const int rc = fire(); if (rc) { pending_wgrads.clear(); return rc; } }
+        ProfEntry* pe = prof.begin(pending_wgrads[jidx[big]].cls, bytes, flops, ws);
+        const bool carry = stash && in_group && !red_stash.empty();      // the slabs of EARLIER flushes ride in this launch
+        const int rc = (nj == 1 && !carry) ? pa_launch_wgrad(*jobs[0], ws)
+                                           : pa_launch_wgrad_group(jobs, nj, ws, false, red_jobs, carry ? red_stash.data() : nullptr, carry ? (int)red_stash.size() : 0);
+        if (carry && !rc) { red_stash.clear(); red_stash_mx = 0; red_stash_flushes = 0; }
+        prof.end(pe, ws);
+        nj = 0; first = false;
+        return rc;
+    };
+    // a group launch is capped at `cap` workgroups: its workgroups live for tens of microseconds with 242 registers each, two of them
+    // close a CU to every other queue -- a launch of <= 256 leaves room for a workgroup of the main chain beside it on every CU
+    const int cap = t.wg_group_cap;
+    int wgs = 0;
+    for (size_t pi = 0; pi < pending_wgrads.size(); ++pi) {
+        PendingWgrad& p = pending_wgrads[pi];
+        if (p.stem || !pa_wgrad_group_takes(p.a)) continue;
+        const int w = pa_wgrad_job_workgroups(p.a);
+        if (nj > 0 && (nj == 8 || wgs + w > cap)) { TRY(fire()); wgs = 0; }
+        grouped[pi] = 1;
+        jidx[nj] = (int)pi;
+        jobs[nj++] = &p.a;
+        wgs += w;
+    }
+    TRY(fire());
+    // the ungrouped launches share no data: from the second on they need no completion / cache round trip behind their predecessor
+    // (hipExtAnyOrderLaunch, conv_wgrad_tile.hip; not with the per-launch event timing, and not inside a stream capture -- the engine's
+    // own or a caller's around pa_hg_backward: an extension launch cannot be captured)
+    bool in_capture = capturing;
+    if (!in_capture) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ws, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) in_capture = true;
     }
     for (size_t pi = 0; pi < pending_wgrads.size(); ++pi) {
         PendingWgrad& p = pending_wgrads[pi];
         if (grouped[pi]) continue;
         ProfEntry* pe = prof.begin(p.cls, p.bytes, p.flops, ws);
-        pa_wgrad_set_launch_flags((any_order && !first && !prof.on && !immediate_reduce && !in_capture) ? 1u : 0u);
+        pa_wgrad_set_launch_flags((t.wgrad_anyorder && !first && !prof.on && !in_capture) ? 1u : 0u);
         int rc = p.stem ? pa_launch_stem_wgrad(p.a, ws) : pa_launch_wgrad(p.a, ws);
         pa_wgrad_set_launch_flags(0u);
         first = false;
         prof.end(pe, ws);
-        if (rc) { pending_wgrads.clear(); return rc; }
-        if (immediate_reduce) {            // ONE slab shared by all layers: reduce before the next launch overwrites it
-            if (p.stem) {
-                TRY(pa_launch_stem_wgrad_reduce(p.c->part, p.c->splits, grads + p.c->p_w, ws, grads + p.c->p_b));
-            } else {
-                TRY(pa_launch_wgrad_reduce(red_jobs + p.c->red_index, 1, p.c->Cout * p.c->Cin * p.c->taps() + p.c->Cout, ws));
-            }
-        }
+        if (rc) return rc;
     }
-    if (ms && reduce_early && !immediate_reduce && !(ablate() & 1)) {
-        // the slabs of this flush join the stash; the stash is summed every `lag`-th flush (one launch for the layers of two or three
-        // blocks: 41 reduction launches per step were 0.3 - 0.6 ms of the weight-gradient queue), part of them still in the Infinity Cache
-        static int lag = -1;
-        if (lag < 0) { const char* e = pa_getenv("PA_WREDUCE_LAG"); lag = e ? atoi(e) : PA_WREDUCE_LAG_DEFAULT; if (lag < 1) lag = 1; }
-        for (PendingWgrad& p : pending_wgrads) {
-            if (p.stem) { TRY(pa_launch_stem_wgrad_reduce(p.c->part, p.c->splits, grads + p.c->p_w, ws, grads + p.c->p_b)); continue; }
-            const int el = p.c->Cout * p.c->Cin * p.c->taps() + p.c->Cout;
-            if ((int)red_stash.size() == PA_RED_LIST_MAX) TRY(flush_red_stash(ws));
-            red_stash.push_back(p.c->red_index);
-            red_stash_mx = el > red_stash_mx ? el : red_stash_mx;
-        }
-        // (in-group reductions: the stash waits for the next group launch of this stream; a launch of its own only when none came for `lag` + 2 flushes)
-        static int rig = -1;
-        if (rig < 0) { const char* e = pa_getenv("PA_WG_RED_IN_GROUP"); rig = e ? atoi(e) : PA_WG_RED_IN_GROUP_DEFAULT; }
-        if (++red_stash_flushes >= (rig && n_w == 1 ? lag + 2 : lag) || n_w > 1) TRY(flush_red_stash(ws));          // (several weight-gradient streams, tuning builds: no lag across streams)
+    if (!stash) return 0;            // (no weight-gradient stream: reduce_grads() sums every slab at the end of the step)
+    // the stash is summed every `lag`-th flush (one launch for the layers of two or three blocks: 41 reduction launches per step were
+    // 0.3 - 0.6 ms of the weight-gradient queue), part of it still in the Infinity Cache; with in-group reductions it waits for the next
+    // group launch, and gets a launch of its own only when none came for `lag` + 2 flushes
+    const int lag = t.wreduce_lag < 1 ? 1 : t.wreduce_lag;
+    for (PendingWgrad& p : pending_wgrads) {
+        if (p.stem) { TRY(pa_launch_stem_wgrad_reduce(p.c->part, p.c->splits, grads + p.c->p_w, ws, grads + p.c->p_b)); continue; }
+        const int el = p.c->Cout * p.c->Cin * p.c->taps() + p.c->Cout;
+        if ((int)red_stash.size() == PA_RED_LIST_MAX) TRY(flush_red_stash(ws));
+        red_stash.push_back(p.c->red_index);
+        red_stash_mx = el > red_stash_mx ? el : red_stash_mx;
     }
-    pending_wgrads.clear();
+    if (++red_stash_flushes >= (in_group ? lag + 2 : lag)) TRY(flush_red_stash(ws));
     return 0;
 }
 
@@ -688,19 +635,10 @@ int Residual::fwd(Net& n, const Act& in) {
     const int B = in.B, H = in.H, W = in.W;
     // x1 / x2 have ONE reader each (conv2 / conv3): at the low-resolution levels their BatchNorm finalize runs in that reader's prologue
     const bool d1 = (n.fin_mask & 1) && n.fin_consumer_ok(c2, B, H, W, false), d2 = (n.fin_mask & 1) && n.fin_consumer_ok(c3, B, H, W, false);
-    // the adapter (residual1, residual3: in front of the hourglasses, the side stream is idle) depends on the block input only: it runs
-    // on the side stream beside conv1 / conv2 instead of between conv2 and conv3 on the main chain
-    const bool ad_par = has_adapter && n.adapter_parallel() ;
-    if (ad_par) {
-        TRY(n.fork_to(0));
-        { StreamScope sc(n, n.side[0]); TRY(n.conv_fwd(ad, n.op(in), B, H, W, pa_none(), pa_none(), adout, nullptr)); }
-        TRY(n.record_join(0));
-    }
     TRY(n.conv_fwd(c1, n.op(in), B, H, W, pa_none(), pa_none(), x1.raw, &b1, nullptr, d1));
     TRY(n.conv_fwd(c2, n.op(x1), B, H, W, pa_none(), pa_none(), x2.raw, &b2, &b1, d2));
     if (has_adapter) {
-        if (ad_par) TRY(n.wait_join(0));
-        else TRY(n.conv_fwd(ad, n.op(in), B, H, W, pa_none(), pa_none(), adout, nullptr));
+        TRY(n.conv_fwd(ad, n.op(in), B, H, W, pa_none(), pa_none(), adout, nullptr));
         TRY(n.conv_fwd(c3, n.op(x2), B, H, W, pa_plain(adout), pa_none(), x3.raw, &b3, &b2));
     } else {
         TRY(n.conv_fwd(c3, n.op(x2), B, H, W, n.op(in), pa_none(), x3.raw, &b3, &b2));
@@ -711,7 +649,7 @@ int Residual::fwd(Net& n, const Act& in) {
 // precondition: x3.grad holds the finished masked gradient and finish_grad(x3) has run.
 // bwd = bwd_a (parameter gradients and the inner data gradients) + bwd_b (gradient of the block input, the only
 // part that needs `extra`, the gradient arriving at the input from its other consumers)
-int Residual::bwd_a(Net& n, const Act& in, const PaOperand* extra) {
+int Residual::bwd_a(Net& n, const Act& in) {
     const int B = in.B, H = in.H, W = in.W;
     low_fused = false;
     // conv3's data gradient goes first: its kernel also stores dz3 = BatchNorm-backward(x3.grad, x3.raw), and the weight
@@ -721,15 +659,6 @@ int Residual::bwd_a(Net& n, const Act& in, const PaOperand* extra) {
     dz3_valid = false;
     TRY(n.conv_dgrad(c3, g3, B, H, W, pa_none(), pa_none(), n.final_ep(x2), x2.grad, dz3, &dz3_valid, x3.bn));
     if (dz3_valid) g3 = pa_plain(dz3);
-    // the adapter's data gradient needs g3 and the gradient reaching the block input from elsewhere (`extra`) only: beside conv2's data
-    // gradient on the side stream when both are known here (residual1 / residual3: no other consumer of the input)
-    ad_forked = false;
-    if (has_adapter && extra && n.adapter_parallel()) {
-        TRY(n.fork_to(0));
-        { StreamScope sc(n, n.side[0]); TRY(n.conv_dgrad(ad, g3, B, H, W, *extra, pa_none(), ep_plain(), adgrad)); }
-        TRY(n.record_join(0));
-        ad_forked = true;
-    }
     TRY(n.conv_wgrad(c3, g3, n.op(x2), B, H, W));
     // (x2's BatchNorm-backward constants are first read by conv2's data gradient, which can compute them in its prologue; conv2's
     // weight gradient, on the weight-gradient stream, is launched behind it)
@@ -745,7 +674,6 @@ int Residual::bwd_a(Net& n, const Act& in, const PaOperand* extra) {
     const PaOperand g1 = n.gradop(x1);
     TRY(n.conv_wgrad(c1, g1, n.op(in), B, H, W));
     if (has_adapter) TRY(n.conv_wgrad(ad, g3, n.op(in), B, H, W));
-    if (!n.on_side && (++n.flush_ctr % n.flush_every) != 0) return 0;
     return n.flush_wgrads();                   // one event for the block's 3-4 weight gradients
 }
 
@@ -753,8 +681,7 @@ int Residual::bwd_b(Net& n, const Act& in, const PaOperand& extra) {
     const int B = in.B, H = in.H, W = in.W;
     const PaOperand g3 = dz3_valid ? pa_plain(dz3) : n.gradop(x3), g1 = n.gradop(x1);
     if (has_adapter) {
-        if (ad_forked) { TRY(n.wait_join(0)); ad_forked = false; }
-        else TRY(n.conv_dgrad(ad, g3, B, H, W, extra, pa_none(), ep_plain(), adgrad));
+        TRY(n.conv_dgrad(ad, g3, B, H, W, extra, pa_none(), ep_plain(), adgrad));
         TRY(n.conv_dgrad(c1, g1, B, H, W, pa_plain(adgrad), pa_none(), n.final_ep(in), in.grad));
     } else {
         TRY(n.conv_dgrad(c1, g1, B, H, W, g3, extra, n.final_ep(in), in.grad, nullptr, nullptr, nullptr, low_of_in, &low_fused));
@@ -763,14 +690,14 @@ int Residual::bwd_b(Net& n, const Act& in, const PaOperand& extra) {
 }
 
 int Residual::bwd(Net& n, const Act& in, const PaOperand& extra, bool in_needs_grad) {
-    TRY(bwd_a(n, in, in_needs_grad ? &extra : nullptr));
+    TRY(bwd_a(n, in));
     return in_needs_grad ? bwd_b(n, in, extra) : 0;
 }
 
 // ------------------------------------------------------------------------------------------------
 // hourglass (reference :139-157 down path, :192-203 up path)
 // The skip branch of level k (a full-resolution residual block) does not depend on the low-resolution path
-// below it: it is enqueued on side stream k and joined where its result is consumed.
+// below it: it is enqueued on the side stream and joined where its result is consumed.
 
 int Hourglass::encode(Net& n, const Act& in) {
     const Act* cur = &in;
@@ -780,9 +707,9 @@ int Hourglass::encode(Net& n, const Act& in) {
             if (n.drop_mask) TRY(pa_launch_cell_mask(n.op(skip[k].x3), n.drop_mask, ep_plain(), skipm[k].raw, cur->B, cur->H, cur->W, cur->C, n.st));
             return 0;
         };
-        if (n.forks(k)) {
+        if (n.multi_stream) {
             TRY(n.fork_to(k));
-            { StreamScope sc(n, n.side[k]); TRY(skip_branch()); }
+            { StreamScope sc(n, n.side); TRY(skip_branch()); }
             TRY(n.record_join(k));
         } else {
             TRY(skip_branch());
@@ -804,7 +731,7 @@ int Hourglass::decode(Net& n) {
     for (int k = 3; k >= 0; --k) {
         TRY(up[k].fwd(n, *low));
         const Act& m = merged[k];
-        if (n.forks(k)) TRY(n.wait_join(k));
+        if (n.multi_stream) TRY(n.wait_join(k));
         TRY(c_upadd_fwd(n, n.op(up[k].x3), n.op(n.drop_mask ? skipm[k] : skip[k].x3), m.raw, m.B, m.H, m.W, m.C, n.st));
         low = &merged[k];
     }
@@ -820,20 +747,16 @@ bool Hourglass::low_fusable(const Net& n, int k) const {
 // precondition: merged[0].grad holds the finished (plain) gradient of the hourglass output.
 // extra0: gradient reaching the hourglass INPUT from consumers outside the hourglass.
 int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
-    if (n.hold_level > 0 && n.multi_stream && n.wstream) n.hold = true;
     for (int k = 0; k < 4; ++k) {
-        if (k == n.hold_level) TRY(n.release_held(k));
         const Act& m = merged[k];
         // the two outputs of the upsample-add backward as two launches: d low on the main chain (the low-resolution path waits for it), d skip
         // on the side stream in front of the skip block's backward pass, its only reader -- the main chain waits for 75 MB instead of 175
-        static int split_env = -1;
-        if (split_env < 0) { const char* e = pa_getenv("PA_UPADD_SPLIT"); split_env = e ? atoi(e) : PA_UPADD_SPLIT_DEFAULT; }
-        if (split_env && !n.drop_mask && n.forks(k) && pa_upadd_bwd_splits(n.final_ep(up[k].x3), n.final_ep(skip[k].x3), m.B, m.H, m.W, m.C)) {
+        if (pa_tuning().upadd_split && !n.drop_mask && n.multi_stream && pa_upadd_bwd_splits(n.final_ep(up[k].x3), n.final_ep(skip[k].x3), m.B, m.H, m.W, m.C)) {
             const Act& upin_ = (k == 3) ? neck.x3 : merged[k + 1];
             const Act& x = (k == 0) ? in : down[k - 1].x3;
             TRY(n.fork_to(k));
             {
-                StreamScope sc(n, n.side[k]);
+                StreamScope sc(n, n.side);
                 TRY(c_upadd_bwd(n, m.grad, n.final_ep(up[k].x3), up[k].x3.grad, n.final_ep(skip[k].x3), skip[k].x3.grad, m.B, m.H, m.W, m.C, n.st, nullptr, 2));
                 TRY(n.finish_grad_or_defer(skip[k].x3, n.x3_fin_ok(skip[k], x)));
                 TRY(skip[k].bwd_a(n, x));
@@ -860,10 +783,10 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
             const Act& skin_ = (k == 0) ? in : down[k - 1].x3;
             TRY(n.finish_grad2_or_defer(up[k].x3, n.x3_fin_ok(up[k], upin_), skip[k].x3, n.x3_fin_ok(skip[k], skin_)));
         }
-        if (n.forks(k)) {          // parameter / inner gradients of the skip block next to the deeper levels
+        if (n.multi_stream) {          // parameter / inner gradients of the skip block next to the deeper levels
             const Act& x = (k == 0) ? in : down[k - 1].x3;
             TRY(n.fork_to(k));
-            { StreamScope sc(n, n.side[k]); TRY(skip[k].bwd_a(n, x)); }
+            { StreamScope sc(n, n.side); TRY(skip[k].bwd_a(n, x)); }
             TRY(n.record_join(k));
         }
         const Act& upin = (k == 3) ? (n.drop_mask ? neckm : neck.x3) : merged[k + 1];
@@ -875,7 +798,6 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
         const Act& x = neck.x3;
         TRY(pa_launch_cell_mask(pa_plain(neckm.grad), n.drop_mask, n.final_ep(x), x.grad, x.B, x.H, x.W, x.C, n.st));
     }
-    TRY(n.release_held(4));
     TRY(n.finish_grad_or_defer(neck.x3, n.x3_fin_ok(neck, down[3].x3)));
     TRY(neck.bwd(n, down[3].x3, pa_none(), true));
     TRY(n.finish_grad_or_defer(down[3].x3, n.x3_fin_ok(down[3], pooled[3])));
@@ -884,7 +806,7 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
         const Act& x = (k == 0) ? in : down[k - 1].x3;
         TRY(c_maxpool_bwd(n, pooled[k].grad, n.op(x), (k == 0) ? extra0 : pa_none(), ep_plain(), poolgrad[k],
                                   x.B, x.H, x.W, x.C, n.st));
-        if (n.forks(k)) {
+        if (n.multi_stream) {
             TRY(n.wait_join(k));
             TRY(skip[k].bwd_b(n, x, pa_plain(poolgrad[k])));
         } else {
@@ -896,40 +818,16 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
     return 0;
 }
 
-// A/B (tuning builds): a stream restricted to `n` of the 256 CUs, spread evenly (PA_WSTREAM_CUS / PA_SIDE_CUS)
-// ... or with a queue priority (PA_WSTREAM_PRIO / PA_SIDE_PRIO: the runtime's numeric priority, lower = more urgent)
-static hipError_t create_stream_cus(hipStream_t* s, const char* env, const char* prio_env) {
-    const char* e = pa_getenv(env);
-    const int n = e ? atoi(e) : 0;
-    if (const char* p = pa_getenv(prio_env)) return hipStreamCreateWithPriority(s, hipStreamNonBlocking, atoi(p));
-    if (n <= 0 || n >= 256) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < n; ++i) { const int cu = (int)((long)i * 256 / n); mask[cu >> 5] |= 1u << (cu & 31); }
-    return hipExtStreamCreateWithCUMask(s, 8, mask);
-}
-
 int Net::ensure_streams() {
     if (streams_ready) return 0;
-    if (const char* e = pa_getenv("PA_FIN_MASK")) fin_mask = atoi(e);
-    if (const char* e = pa_getenv("PA_FIN_PROLOGUE")) fin_rows_max = atoi(e) > PA_FIN_SMALL_ROWS ? PA_FIN_SMALL_ROWS : atoi(e);
-    if (pa_getenv("PA_SINGLE_STREAM")) { multi_stream = false; streams_ready = true; return 0; }
-    if (const char* e = pa_getenv("PA_FORK_LEVELS")) fork_mask = atoi(e);
-    if (const char* e = pa_getenv("PA_SIDE_STREAMS")) n_side = atoi(e) < 1 ? 1 : (atoi(e) > 4 ? 4 : atoi(e));
-    reduce_early = pa_getenv("PA_WREDUCE_LATE") == nullptr;
-    if (const char* e = pa_getenv("PA_WFLUSH_EVERY")) flush_every = atoi(e) > 0 ? atoi(e) : 1;
-    if (const char* e = pa_getenv("PA_WHOLD")) hold_level = atoi(e);
+    if (pa_tuning().single_stream) { streams_ready = true; return 0; }      // (multi_stream is false from the start then)
+    PA_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
     for (int k = 0; k < 4; ++k) {
-        if (k < n_side) PA_CHECK(create_stream_cus(&side[k], "PA_SIDE_CUS", "PA_SIDE_PRIO"));
-        else side[k] = side[k % n_side];            // levels share streams (in-order per stream: fork/join events keep it correct)
         PA_CHECK(hipEventCreateWithFlags(&ev_fork[k], hipEventDisableTiming));
         PA_CHECK(hipEventCreateWithFlags(&ev_join[k], hipEventDisableTiming));
     }
-    if (!pa_getenv("PA_NO_WSTREAM")) {
-        PA_CHECK(create_stream_cus(&wstream, "PA_WSTREAM_CUS", "PA_WSTREAM_PRIO"));
-        wstreams[0] = wstream;
-        if (const char* e = pa_getenv("PA_WSTREAMS")) n_w = atoi(e) < 1 ? 1 : (atoi(e) > 4 ? 4 : atoi(e));
-        for (int i = 1; i < n_w; ++i) PA_CHECK(hipStreamCreateWithFlags(&wstreams[i], hipStreamNonBlocking));
-        for (int i = 0; i < n_w; ++i) PA_CHECK(hipEventCreateWithFlags(&ev_wdone_x[i], hipEventDisableTiming));
+    if (!pa_tuning().no_wstream) {
+        PA_CHECK(hipStreamCreateWithFlags(&wstream, hipStreamNonBlocking));
         for (int i = 0; i < 16; ++i) PA_CHECK(hipEventCreateWithFlags(&ev_w[i], hipEventDisableTiming));
         PA_CHECK(hipEventCreateWithFlags(&ev_wdone, hipEventDisableTiming));
     }
@@ -940,16 +838,12 @@ void Net::release_streams() {
     release_graph();
     if (bucket_events) { for (int i = 0; i < 16; ++i) (void)hipEventDestroy(ev_bucket[i]); (void)hipEventDestroy(ev_bucket_main); bucket_events = false; }
     if (mstream) { (void)hipStreamSynchronize(mstream); (void)hipStreamDestroy(mstream); (void)hipEventDestroy(ev_mfork); (void)hipEventDestroy(ev_meter); mstream = nullptr; meter_pending = false; }
-    for (int k = 0; k < 4; ++k) {
-        if (side[k]) {
-            if (k < n_side) { (void)hipStreamSynchronize(side[k]); (void)hipStreamDestroy(side[k]); }
-            (void)hipEventDestroy(ev_fork[k]); (void)hipEventDestroy(ev_join[k]); side[k] = nullptr;
-        }
+    if (side) {
+        (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); side = nullptr;
+        for (int k = 0; k < 4; ++k) { (void)hipEventDestroy(ev_fork[k]); (void)hipEventDestroy(ev_join[k]); }
     }
     if (wstream) {
-        for (int i = 1; i < n_w; ++i) { (void)hipStreamSynchronize(wstreams[i]); (void)hipStreamDestroy(wstreams[i]); wstreams[i] = nullptr; }
-        for (int i = 0; i < n_w; ++i) (void)hipEventDestroy(ev_wdone_x[i]);
-        (void)hipStreamSynchronize(wstream); (void)hipStreamDestroy(wstream); wstream = nullptr; wstreams[0] = nullptr;
+        (void)hipStreamSynchronize(wstream); (void)hipStreamDestroy(wstream); wstream = nullptr;
         for (int i = 0; i < 16; ++i) (void)hipEventDestroy(ev_w[i]);
         (void)hipEventDestroy(ev_wdone);
     }
@@ -957,9 +851,9 @@ void Net::release_streams() {
     prof.entries.clear(); prof.used = 0;
     streams_ready = false;
 }
-int Net::fork_to(int k) { if (nosync() && (g_nosync & 1)) return 0; PA_CHECK(hipEventRecord(ev_fork[k], st)); PA_CHECK(hipStreamWaitEvent(side[k], ev_fork[k], 0)); return 0; }
-int Net::record_join(int k) { if (nosync() && (g_nosync & 2)) return 0; PA_CHECK(hipEventRecord(ev_join[k], side[k])); return 0; }
-int Net::wait_join(int k) { if (nosync() && (g_nosync & 2)) return 0; PA_CHECK(hipStreamWaitEvent(st, ev_join[k], 0)); return 0; }
+int Net::fork_to(int k) { PA_CHECK(hipEventRecord(ev_fork[k], st)); PA_CHECK(hipStreamWaitEvent(side, ev_fork[k], 0)); return 0; }
+int Net::record_join(int k) { PA_CHECK(hipEventRecord(ev_join[k], side)); return 0; }
+int Net::wait_join(int k) { PA_CHECK(hipStreamWaitEvent(st, ev_join[k], 0)); return 0; }
 
 // ------------------------------------------------------------------------------------------------
 int Net::prepare_weights() { return pa_launch_weight_prep(prep_jobs, n_prep, prep_max, st); }
@@ -1114,18 +1008,12 @@ int Net::mark_bucket(int stack) {
         bucket_events = true;
     }
     TRY(flush_wgrads());
-    if (multi_stream && wstream) TRY(flush_red_stash(wstreams[(w_rr + n_w - 1) % n_w]));
-    if (multi_stream && wstream && (reduce_early || immediate_reduce)) {
-        PA_CHECK(hipEventRecord(ev_bucket_main, st));
-        for (int i = 0; i < n_w; ++i) PA_CHECK(hipStreamWaitEvent(wstreams[i], ev_bucket_main, 0));
-        for (int i = 1; i < n_w; ++i) {         // (more than one weight-gradient stream: fold them into the first)
-            PA_CHECK(hipEventRecord(ev_wdone_x[i], wstreams[i]));
-            PA_CHECK(hipStreamWaitEvent(wstreams[0], ev_wdone_x[i], 0));
-        }
-        PA_CHECK(hipEventRecord(ev_bucket[stack], wstreams[0]));
-        return 0;
-    }
-    return -1;            // slabs are only reduced at the very end in this mode: no early bucket
+    if (!wgrads_aside()) return -1;            // slabs are only reduced at the very end in this mode: no early bucket
+    TRY(flush_red_stash(wstream));
+    PA_CHECK(hipEventRecord(ev_bucket_main, st));
+    PA_CHECK(hipStreamWaitEvent(wstream, ev_bucket_main, 0));
+    PA_CHECK(hipEventRecord(ev_bucket[stack], wstream));
+    return 0;
 }
 
 // One training step (forward, loss, backward) as a HIP graph.  Inputs live in the engine's own buffers (img4, pts_dev:
@@ -1177,17 +1065,12 @@ void Net::release_graph() {
 
 int Net::reduce_grads() {
     TRY(flush_wgrads());
-    if (multi_stream && wstream) TRY(flush_red_stash(wstreams[(w_rr + n_w - 1) % n_w]));
-    if (multi_stream && wstream) {              // all weight-gradient slabs are complete
-        if (!(nosync() && (g_nosync & 8))) {
-            for (int i = 0; i < n_w; ++i) {
-                PA_CHECK(hipEventRecord(ev_wdone_x[i], wstreams[i]));
-                PA_CHECK(hipStreamWaitEvent(st, ev_wdone_x[i], 0));
-            }
-        }
-        if (reduce_early || immediate_reduce) return 0;
+    if (wgrads_aside()) {                       // every slab is summed on the weight-gradient stream: the main stream waits for it
+        TRY(flush_red_stash(wstream));
+        PA_CHECK(hipEventRecord(ev_wdone, wstream));
+        PA_CHECK(hipStreamWaitEvent(st, ev_wdone, 0));
+        return 0;
     }
-    if (immediate_reduce) return 0;             // every layer was reduced right after its weight-gradient launch
     TRY(pa_launch_wgrad_reduce(red_jobs, n_red, red_max, st));
     if (!is_agent) {
         TRY(pa_launch_stem_wgrad_reduce(stem_conv.part, stem_conv.splits, grads + stem_conv.p_w, st, grads + stem_conv.p_b));

@@ -5,10 +5,10 @@ unfinished agent forwards (tests/exact_history.py) -- recomputed in float64 from
   * the 12 residual blocks (in0..4 = residual_skip1-4 / residual_neck, merge0..3 = merge1-4, deep0..2 = deep_merge.0-2) with the per-block
     checks of tests/conv_exact.py (Checker.block) and the per-BatchNorm checks of tests/bn_exact.py (check_bn_site): one definition of
     every bound.  The five input blocks read the pose net's hg0.skip1-4 / hg0.neck in place: their conv1 operand is rnd(view 0) of the
-    POSE net's tensor (its eval-mode constants), they give no input gradient (Residual::bwd with need_dx = false, asn.hip:337-339) and
+    POSE net's tensor (its eval-mode constants), they give no input gradient (Residual::bwd with need_dx = false, asn.hip:336-338) and
     the pose net's flat_grads must stay zero;
   * pool+add forward (pooladd_fwd_kernel asn.hip:26-38: one fp32 max chain, one add, one rounding) bit for bit, and its backward
-    (asn.hip:333-336): the plain gradient of pa<k> through the ReLU mask of in<k+1> (pa_launch_ep_apply) and routed to the first maximum
+    (asn.hip:332-335): the plain gradient of pa<k> through the ReLU mask of in<k+1> (pa_launch_ep_apply) and routed to the first maximum
     of hi under hi's ReLU mask (pa_launch_maxpool_bwd with a BatchNorm-backward epilogue, no addend), both bit for bit
     (bn_exact.check_pool_bwd).  The sums these launches feed to the BatchNorm backward of lo / hi are the BatchNorm checks' (sum_depth
     models the streaming kernels);
@@ -59,7 +59,7 @@ POSE_FEATS = ['hg0.skip1', 'hg0.skip2', 'hg0.skip3', 'hg0.skip4', 'hg0.neck']
 
 def block_sites():
     """(parameter prefix, hook name of the output, input in the pose net?, hook name of the input) of the agent's 12 residual blocks, wired
-    as Net::asn_forward_trunk (asn.hip:244-263)."""
+    as Net::asn_forward_trunk (asn.hip:243-262)."""
     s = [(IN_PREFIX[k], 'in%d' % k, True, POSE_FEATS[k]) for k in range(5)]
     s += [('merge%d.' % (k + 1), 'merge%d' % k, False, 'pa%d' % k) for k in range(4)]
     s += [('deep_merge.%d.' % k, 'deep%d' % k, False, 'merge3' if k == 0 else 'deep%d' % (k - 1)) for k in range(3)]

@@ -19,19 +19,19 @@ one addition at 2u -- the ISA does not specify the internal order or rounding, s
 charged 2u.
 
 Depth D: the most additions any product passes through.  The release kernels keep one accumulator per output element and chain the
-MFMAs over the reduction (conv_igemm.hip:194/323, conv1x1_tile.hip:197, conv3x3_tile.hip:356/401, conv_wgrad.hip:195,
-conv_wgrad_tile.hip:160/174, pose_ops.hip:137): no split of the reduction across waves.
+MFMAs over the reduction (conv_igemm.hip:194/323, conv1x1_tile.hip:195, conv3x3_tile.hip:334/379, conv_wgrad.hip:195,
+conv_wgrad_tile.hip:157/171, pose_ops.hip:137): no split of the reduction across waves.
   * forward and data gradient: D = 32 + ceil(K / 32) + A, where K = Cin * taps (Cout * taps for the data gradient) over the padded
     channel counts (multiples of 64; 256 for the stem's 7 x 7 x 4 patch) and A the epilogue adds (bias, add1, add2).
   * weight gradient: a split owns a contiguous (conv_wgrad.hip: steps of 64 / 128 pixels) or strided (conv_wgrad_tile.hip: tiles of
     128 pixels) share of the ceil(M / P) tiles of P <= 128 pixels, at most M / S + 2 P pixels, one MFMA per 32 of them; the slabs of the S
-    splits are then chained in split order (wgrad_reduce.h; the stem's reducer: four slices of S / 4 plus three adds, conv_wgrad.hip:344):
+    splits are then chained in split order (wgrad_reduce.h; the stem's reducer: four slices of S / 4 plus three adds, conv_wgrad.hip:340):
     D = 32 + ceil((M / S + 256) / 32) + S.
   * bias gradient (convs without a BatchNorm behind them): any tree over the <= M / S + 256 values of a split (per-thread column sums
-    and their LDS sum, conv_wgrad_tile.hip:469, conv_wgrad.hip:222), then the chain over S: D = M / S + 256 + S.
-  S is the split count Net::layout_conv (net.hip:117-135) gives the layer: pa_wgrad_splits (conv_wgrad.hip:241-260, with the tile
-  kernels' count wg_tile_cfg conv_wgrad_tile.hip:541-580), replaced by pa_wgrad_group_splits (conv_wgrad_tile.hip:677-695) where the
-  grouped kernel takes the layer, and 512 for the stem (net.hip:129-133).  They are not exported: wgrad_splits() mirrors them for the
+    and their LDS sum, conv_wgrad_tile.hip:466, conv_wgrad.hip:222), then the chain over S: D = M / S + 256 + S.
+  S is the split count Net::layout_conv (net.hip:108-125) gives the layer: pa_wgrad_splits (conv_wgrad.hip:238-256, with the tile
+  kernels' count wg_tile_cfg conv_wgrad_tile.hip:537-557), replaced by pa_wgrad_group_splits (conv_wgrad_tile.hip:637-649) where the
+  grouped kernel takes the layer, and 512 for the stem (net.hip:120-123).  They are not exported: wgrad_splits() mirrors them for the
   release build, which reads no tuning variable (common.h pa_getenv); tests/test_gpu_conv_exact.py checks the mirror against the
   workspace sizes the library reports.  A shape no kernel takes raises instead of getting a default.
 
@@ -126,7 +126,7 @@ def pad64(c):
 
 # ---- split counts of the release build (not exported; see the module docstring for the source lines)
 def _tile_cfg(B, H, W, Cin, Cout, taps):
-    """wg_tile_cfg (conv_wgrad_tile.hip:541-580): (n block, c block, tiles, splits) or None."""
+    """wg_tile_cfg (conv_wgrad_tile.hip:537-557): (n block, c block, tiles, splits) or None."""
     if H <= 0 or W <= 0:
         return None
     if taps == 9:
@@ -147,12 +147,12 @@ def _tile_cfg(B, H, W, Cin, Cout, taps):
         return None
     types = (Cout // nb) * (Cin // cb)
     s = min(max(256 // types, 1), nt)
-    per = min(max(-(-nt // s), 1), nt)                      # PA_WGRAD_MINPER1 / 9 default 1
+    per = min(max(-(-nt // s), 1), nt)                      # tiles per workgroup (at least 1, at most all)
     return nb, cb, nt, -(-nt // per)
 
 
 def wgrad_splits(M, H, W, Cin, Cout, taps):
-    """pa_wgrad_splits (conv_wgrad.hip:241-260)."""
+    """pa_wgrad_splits (conv_wgrad.hip:238-256)."""
     if taps not in (1, 9) or Cin % 64 or Cout % 64:
         raise ValueError('no weight-gradient kernel for Cin %d Cout %d taps %d' % (Cin, Cout, taps))
     if H > 0 and W > 0 and M % (H * W) == 0:
@@ -167,7 +167,7 @@ def wgrad_splits(M, H, W, Cin, Cout, taps):
 
 
 def group_splits(B, H, W, Cin, Cout, taps):
-    """pa_wgrad_group_splits (conv_wgrad_tile.hip:677-695); 0: the grouped kernel does not take the shape."""
+    """pa_wgrad_group_splits (conv_wgrad_tile.hip:637-649); 0: the grouped kernel does not take the shape."""
     c = _tile_cfg(B, H, W, Cin, Cout, taps)
     if not c:
         return 0
@@ -183,7 +183,7 @@ def group_splits(B, H, W, Cin, Cout, taps):
 
 
 def layer_splits(B, H, W, Cin, Cout, k):
-    """S of a layer of the net (Net::layout_conv, net.hip:117-135); Cin / Cout real, padded here."""
+    """S of a layer of the net (Net::layout_conv, net.hip:108-125); Cin / Cout real, padded here."""
     M = B * H * W
     if k == 7:
         s = wgrad_splits(M, 0, 0, 256, pad64(Cout), 1)
@@ -302,7 +302,7 @@ def bgrad_check(got, dy, S):
 # the net (GPU legs)
 def block_sites(stacks):
     """(parameter prefix of the residual block, debug-hook name of its output, hook name of its input, has adapter), every block of the
-    pose net, wired as Net::forward_pose_body / Hourglass::encode / decode (net.hip:776-815, 1018-1048)."""
+    pose net, wired as Net::forward_pose_body / Hourglass::encode / decode (net.hip:703-742, 912-942)."""
     s = [('residual1.', 'res1', 'stem', True), ('residual2.', 'res2', 'pool0', False), ('residual3.', 'res3', 'res2', True)]
     for i in range(stacks):
         for k in (1, 2, 3, 4):
@@ -378,7 +378,7 @@ class Checker(object):
                 self.fails.append(('zero bias gradient', conv, float(z.abs().max())))
 
     def block(self, p, out, Po, Pi, inp, input_grad=True, ad=False, add2=None, in_masked=True):
-        """One residual block (Residual::fwd / bwd_a / bwd_b, net.hip:691-763): forward of conv1 / conv2 / conv3 (+ adapter), the inner data
+        """One residual block (Residual::fwd / bwd_a / bwd_b, net.hip:638-690): forward of conv1 / conv2 / conv3 (+ adapter), the inner data
         gradients, the weight gradients at the layer's split count, zero bias gradients, and -- input_grad -- the data gradient of the
         block's input.  p: parameter prefix; out: hook name of the output in probe Po; inp: hook name of the input in probe Pi;
         ad: the block has an adapter; add2: a second addend of the input's data gradient (the pool's routed gradient); in_masked: the
@@ -424,7 +424,7 @@ class Checker(object):
             wg(p + 'adapter', x_in, g3, 1, H)
         if not input_grad:
             return
-        # d in = mask * (conv1^T(g1) + add1 [+ add2]) (Residual::bwd_b, net.hip:750-763)
+        # d in = mask * (conv1^T(g1) + add1 [+ add2]) (Residual::bwd_b, net.hip:678-690)
         if ad:      # add1 = adgrad = rnd(adapter^T(g3)), not exposed; residual1 / residual3 have no other reader of their input
             adds = (rounded(dgrad_term(g3, W(p + 'adapter'), pad64(g3.shape[1])), dtype),)
         else:       # add1: the x3 gradient as conv1's epilogue loads it, dz3 (view 4) or the LIN2 value in fp32 (view 3)
@@ -457,7 +457,7 @@ def loss_check(got, heat, target):
 
 def heat_grad_check(got, heat, target, gscale, add, dtype):
     """d heat (storage type) against 2 (heat - target) gscale (+ add): heat_grad_kernel pose_ops.hip:198-200 -- a subtraction, the exact
-    doubling, the product with the fp32 gscale = grad_scale / (B * 16 * H * H) (itself one rounded division, net.hip:1055), the add of
+    doubling, the product with the fp32 gscale = grad_scale / (B * 16 * H * H) (itself one rounded division, net.hip:949), the add of
     in_conv's data gradient: three or four roundings, fewer where the compiler contracts the product and the add into one fma (a
     first-order bound over the separate operations admits both); then the half ulp of the storage type."""
     from tests.bn_exact import E
@@ -496,10 +496,10 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
     note('conv forward', 'conv1', check16(P.get('stem', 2), a0, dtype), ('conv1',))
     wg('conv1', xs, grad_op('stem'), 7, res // 2, stride=2, pad=3)
     del a0
-    # ---- residual blocks (Residual::fwd / bwd_a, net.hip:691-760)
+    # ---- residual blocks (Residual::fwd / bwd_a, net.hip:638-687)
     # The input of skip block k of hourglass i (xin<i>, hg<i>.down<k-1>) also feeds max pool k: Hourglass::bwd routes the pool's
-    # gradient back (plus, k = 1, d xin<i+1> from the next stack's forth_conv addend) into poolgrad[k] (net.hip:881-885, stored in the
-    # storage type), and skip k's conv1 data gradient adds it as its SECOND addend (Residual::bwd_b, net.hip:760).  res1's output has
+    # gradient back (plus, k = 1, d xin<i+1> from the next stack's forth_conv addend) into poolgrad[k] (net.hip:803-807, stored in the
+    # storage type), and skip k's conv1 data gradient adds it as its SECOND addend (Residual::bwd_b, net.hip:687).  res1's output has
     # no conv reader (pool0 only): nothing to check here.  (That the pool routed correctly: tests/bn_exact.py 'pool backward'.)
     skip_k = dict([('xin%d' % i, (i, 1)) for i in range(stacks)] + [('hg%d.down%d' % (i, k), (i, k + 1)) for i in range(stacks) for k in (1, 2, 3)])
     # a pending BatchNorm (masked gradient): the stem and block outputs (xin0 is residual3's); not the pools, merges or xin<i>, i >= 1
@@ -508,7 +508,7 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
         add2 = P.get('hg%d.poolgrad%d' % skip_k[inp], 2) if inp in skip_k else None          # the pool's routed gradient
         ck.block(p, out, P, P, inp, True, ad, add2, has_bn(inp))
         del add2
-    # ---- head (Net::forward_pose_body / backward_stack, net.hip:1036-1083)
+    # ---- head (Net::forward_pose_body / backward_stack, net.hip:930-977)
     Hh = res // 4
     target = t(inputs.heatmaps_from_pts(pts_np, res=Hh)).cuda()
     loss_sum = None
@@ -538,7 +538,7 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
             fails.append(('heat gradient', 'heat%d padded channels' % i, float('inf')))
         ls, r = loss_check(S.losses[i], outs[i], target)
         note('loss', 'stack %d' % i, (r, 0.0))
-        loss_sum = ls if loss_sum is None else loss_sum + ls                # loss_out_kernel (elementwise.hip:1202-1208): s += v, from 0
+        loss_sum = ls if loss_sum is None else loss_sum + ls                # loss_out_kernel (elementwise.hip:1193-1199): s += v, from 0
         del dh64, inner_add
         if i + 1 < stacks:
             fc, ic = 'forth_conv.%d' % i, 'in_conv.%d' % i
@@ -556,7 +556,7 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
                 fails.append(('conv data gradient', ic + ' padded channels', float('inf')))
             wg(fc, lv, gx, 1, Hh, has_bias=True)
             wg(ic, h64, gx, 1, Hh, has_bias=True)
-        # d lin<i> = mask * (forth^T(d xin<i+1>) + lgrad_tmp), lgrad_tmp = rnd(out_conv^T(d heat)) (net.hip:1064-1072); the last stack:
+        # d lin<i> = mask * (forth^T(d xin<i+1>) + lgrad_tmp), lgrad_tmp = rnd(out_conv^T(d heat)) (net.hip:958-966); the last stack:
         # mask * out_conv^T(d heat)
         lm = (P.get('lin%d' % i, 0) > 0).double()
         oct_ = dgrad_term(dheat, W(oc), 64)

@@ -190,7 +190,7 @@ def test_an_element_whose_terms_are_all_zero_must_be_zero(dtype, floor):
 
 
 def test_split_mirror_knows_the_net_layers_and_refuses_unknown_shapes():
-    assert X.layer_splits(24, 128, 128, 3, 64, 7) == 512              # the stem at benchmark size (net.hip:129-133)
+    assert X.layer_splits(24, 128, 128, 3, 64, 7) == 512              # the stem at benchmark size (net.hip:120-123)
     assert X.layer_splits(2, 64, 64, 3, 64, 7) == 128                 # tiny maps: the generic count
     assert X.group_splits(24, 64, 64, 128, 128, 9) > 0                # the grouped kernel takes the 64 x 64 3 x 3 layers
     assert X.group_splits(2, 8, 8, 128, 128, 9) == 0
