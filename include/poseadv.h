@@ -94,8 +94,17 @@ int pa_transform_pts_sized(const float* pts, const double* params, const double*
  * (scipy.misc.pilutil over Pillow): source bytes = fp32 frame / 255, mirrored, times gain, clamped; for
  * scale * 200 / res >= 2 the antialiased whole-frame pre-downscale (:121-133); the int-truncated, rotation-padded,
  * zero-filled window (:136-164); PIL's bilinear rotate about the window centre (:166-170); PIL's bilinear (triangle
- * filter) resize to res x res (:175); uint8 / 255.  Byte-exact against the reference's crop over Pillow 12 for crops
- * that hold a black and a white pixel (scipy's per-image min/max stretching is not applied).
+ * filter) resize to res x res (:175); uint8 / 255.
+ * What each entry point is exact against: scipy's toimage() maps every non-uint8 array from its own [min, max] to [0, 255]
+ * (the whole fp32 frame in front of the pre-downscale, in fp32; the zero-padded window, in double).
+ *   pa_crop          (the default) scales by the full range instead: byte-exact against the reference's crop over Pillow 12
+ *                    only for crops whose window holds a pure black and a pure white pixel, and against the same pipeline
+ *                    without the stretch (oracle/crop.py, quirk=False) for every crop.
+ *   pa_crop_stretch  (opt-in) applies both stretches: byte-exact against the reference's crop over Pillow 12 for every crop
+ *                    (oracle/crop.py, quirk=True).  Same arguments and outputs; its workspace is
+ *                    pa_crop_stretch_workspace_bytes() bytes (larger; scratch, no initialisation needed).  It costs three more
+ *                    launches and one more read of every pre-downscaled sample's frame.  A window wholly outside the frame,
+ *                    where the reference raises, gives zeros from both.
  * src: uint8 [B][Hs][Ws][3]; sizes: int32 [B][2] = (width, height) of each sample's own frame inside the padded
  * buffer, or NULL (all Ws x Hs); params: [B][8] as for pa_affine_params (centre AFTER the mirror);
  * workspace: pa_crop_workspace_bytes() bytes (scratch, no initialisation needed);
@@ -106,6 +115,9 @@ size_t pa_crop_workspace_bytes(int B, int Hs, int Ws, int res);
 int pa_crop_design_bytes(int B, int Hs, int Ws, int res, double* out_host);
 int pa_crop(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const double* params, int B, int res, void* workspace,
             void* out4, float* outf, uint8_t* out8, void* stream);
+size_t pa_crop_stretch_workspace_bytes(int B, int Hs, int Ws, int res);
+int pa_crop_stretch(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const double* params, int B, int res, void* workspace,
+                    void* out4, float* outf, uint8_t* out8, void* stream);
 
 /* JPEG decode split between host and device (the reference decodes on the host inside its DataLoader workers: utils/imutils.py:38-41
  * over data/mpii_for_mpii.py:97): the serial Huffman stage runs on the host, everything after the coefficients (dequantisation,

@@ -79,6 +79,8 @@ _PROTOS = {
     'pa_crop_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'pa_crop_design_bytes': (_i, [_i, _i, _i, _i, C.POINTER(C.c_double)]),
     'pa_crop': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'pa_crop_stretch_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'pa_crop_stretch': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'pa_jpeg_info_host': (_i, [_vp, _sz, _vp]),
     'pa_jpeg_entropy_host': (_i, [_vp, _sz, _vp, _sz, _vp]),
     'pa_jpeg_workspace_bytes': (_sz, [_i, _i, _i]),

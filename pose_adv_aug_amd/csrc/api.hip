@@ -90,6 +90,12 @@ int pa_crop(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const doub
     if (!src || !params || !workspace || B <= 0 || res <= 0) { pa_set_error_msg("pa_crop: bad arguments"); return 1; }
     TRY(pa_launch_crop(src, Hs, Ws, sizes, params, B, res, workspace, reinterpret_cast<bf16*>(out4), outf, out8, ST(s))); return 0;
 }
+size_t pa_crop_stretch_workspace_bytes(int B, int Hs, int Ws, int res) { return pa_crop_stretch_workspace_size(B, Hs, Ws, res); }
+int pa_crop_stretch(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const double* params, int B, int res, void* workspace,
+                    void* out4, float* outf, uint8_t* out8, void* s) {
+    if (!src || !params || !workspace || B <= 0 || res <= 0) { pa_set_error_msg("pa_crop_stretch: bad arguments"); return 1; }
+    TRY(pa_launch_crop_stretch(src, Hs, Ws, sizes, params, B, res, workspace, reinterpret_cast<bf16*>(out4), outf, out8, ST(s))); return 0;
+}
 int pa_flip_lr_nhwc4(const void* src, void* dst, int B, int H, int W, void* s) {
     TRY(pa_launch_flip_lr_nhwc4(reinterpret_cast<const bf16*>(src), reinterpret_cast<bf16*>(dst), B, H, W, ST(s))); return 0;
 }

@@ -32,3 +32,6 @@ size_t pa_crop_workspace_size(int B, int Hs, int Ws, int res);
 void pa_crop_bytes_bound(int B, int Hs, int Ws, int res, double* rd, double* wr);
 int pa_launch_crop(const unsigned char* src, int Hs, int Ws, const int* sizes, const double* params, int B, int res, void* workspace,
                    bf16* out4, float* outf, unsigned char* out8, hipStream_t st);
+size_t pa_crop_stretch_workspace_size(int B, int Hs, int Ws, int res);
+int pa_launch_crop_stretch(const unsigned char* src, int Hs, int Ws, const int* sizes, const double* params, int B, int res, void* workspace,
+                           bf16* out4, float* outf, unsigned char* out8, hipStream_t st);

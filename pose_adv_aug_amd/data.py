@@ -98,15 +98,18 @@ def dataset_size(batches):
 
 
 class Augmenter(object):
-    """Draw augmentation parameters by the reference's laws and produce the network input + targets."""
+    """Draw augmentation parameters by the reference's laws and produce the network input + targets.
+    stretch: crop with scipy's min/max byte stretch (HumanAug.crop_batch(stretch=True)) in every law; off by default."""
 
-    def __init__(self, seed=0, inp_res=256, out_res=64):
+    def __init__(self, seed=0, inp_res=256, out_res=64, stretch=False):
         self.seed, self.inp_res, self.out_res = int(seed), inp_res, out_res
+        self.stretch = bool(stretch)
         self.step = 0
 
     def _finish(self, batch, want_nchw=False):
         t_out, _ = HumanAug.affine_params(batch.params, self.inp_res, self.out_res)
-        img4, imgf, _ = HumanAug.crop_batch(batch.frames, batch.params, res=self.inp_res, want_nchw=want_nchw, sizes=batch.sizes)
+        img4, imgf, _ = HumanAug.crop_batch(batch.frames, batch.params, res=self.inp_res, want_nchw=want_nchw, sizes=batch.sizes,
+                                              stretch=self.stretch)
         pts_heat, pts_img = HumanAug.transform_pts_batch(batch.joints, batch.params, t_out, batch.Ws, sizes=batch.sizes)
         # fp32 c, s, r for the metric calls from ONE launch of the library (three framework elementwise kernels per step before round 6)
         B = batch.B

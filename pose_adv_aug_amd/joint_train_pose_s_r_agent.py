@@ -207,7 +207,7 @@ def main(argv=None):
     broadcast_parameters(hg)
     broadcast_parameters(agent_sr)
 
-    augmenter = Augmenter(seed=4242 + rank)
+    augmenter = Augmenter(seed=4242 + rank, stretch=bool(opt.crop_stretch))
     train_feed, val_feed = make_feeds(opt, rank, world, log)                                  # :117-133
     if not opt.is_train:                                                                      # :137-144
         _, _, predictions = validate(val_feed, hg, augmenter, train_history_pose.epoch[-1]['epoch'], opt, log=log)

@@ -28,6 +28,9 @@ class BaseOptions(object):
         p.add_argument('--use_html', type=_bool, default=False, help='use html to store images')
         p.add_argument('--display_winsize', type=int, default=256, help='display window size')
         p.add_argument('--dataset', type=str, default='mpii', help='dataset type')
+        # (not a flag of the reference) 1: crops reproduce scipy's toimage() min/max byte stretch, as the reference's host pipeline
+        # does for training and validation alike; 0 (default): the frame is scaled by its full range
+        p.add_argument('--crop_stretch', type=int, default=0, help='1: reproduce scipy toimage() min/max byte stretching in the crop')
         self.initialized = True
 
     @staticmethod

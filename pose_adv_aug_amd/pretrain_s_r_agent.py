@@ -159,7 +159,7 @@ def main(argv=None):
         ckpt.load_prefix = sr_dir + '/' + opt.load_prefix_sr[0:-1]
         ckpt.load_checkpoint(agent, optimizer, history)
     ckpt.save_prefix = sr_dir + '/'
-    aug = Augmenter(seed=4321)
+    aug = Augmenter(seed=4321, stretch=bool(opt.crop_stretch))
     # the feeds are STREAMED every pass (an MPII split resident in HBM would be 60-130 GB of padded frames): the collection
     # pass walks each split once in dataset order (row i of a text file = person i, collect-scale-ditri.py:123-255), the
     # training passes look a person's distribution up by its dataset index (data/pretrain_s_r_agent.py:127-128)

@@ -73,13 +73,14 @@ def transform_pts_batch(pts, params, t, width, sizes=None):
 _CROP_WS = {}
 
 
-def _crop_workspace(B, Hs, Ws, res):
-    """scratch of pa_crop (intermediate images of the staged crop): ONE grow-only buffer per (device, stream it is used
+def _crop_workspace(B, Hs, Ws, res, stretch=False):
+    """scratch of pa_crop / pa_crop_stretch (intermediate images of the staged crop), sized for the mode in use (the stretch
+    mode's is the same layout plus its accumulators and tables): ONE grow-only buffer per (device, stream it is used
     on), re-allocated only when pa_crop_workspace_bytes asks for more than it holds -- the MPII feed pads every batch to its
     own (Hs, Ws), a cache per shape would grow by ~90 MB per new shape.  Keyed by the stream so that the crop enqueued one step
     ahead on the augmentation stream (data.AugmentAhead) and a crop on the main stream (validate) never share scratch; a
     buffer that is outgrown is released through torch's stream-ordered allocator on the stream that used it."""
-    need = int(lib().pa_crop_workspace_bytes(B, Hs, Ws, res))
+    need = int((lib().pa_crop_stretch_workspace_bytes if stretch else lib().pa_crop_workspace_bytes)(B, Hs, Ws, res))
     key = (str(dev()), int(getattr(stream(), 'value', stream()) or 0))
     ws = _CROP_WS.get(key)
     if ws is None or ws.numel() < need:
@@ -87,17 +88,22 @@ def _crop_workspace(B, Hs, Ws, res):
     return ws
 
 
-def crop_batch(frames, params, res=256, want_nchw=False, want_nhwc4=True, want_u8=False, sizes=None):
+def crop_batch(frames, params, res=256, want_nchw=False, want_nhwc4=True, want_u8=False, sizes=None, stretch=False):
     """device: uint8 frames [B][Hs][Ws][3] + params [B][8] -> network input (bf16 NHWC4) and/or fp32 NCHW and/or the uint8
     crop [B][res][res][3].  crop (pylib/HumanAug.py:117-176: pre-downscale, int-truncated window, PIL rotate, PIL resize)
-    behind flip + colour gain (data/mpii_for_mpii.py:126-135), byte-exact against the reference over Pillow."""
+    behind flip + colour gain (data/mpii_for_mpii.py:126-135).  stretch=False (the default, pa_crop): the frame is scaled by
+    its full range -- byte-exact against the reference over Pillow only for crops that hold a pure black and a pure white
+    pixel.  stretch=True (pa_crop_stretch): scipy's toimage() min/max byte stretch of the frame (pre-downscale case) and of
+    the window is reproduced -- byte-exact against the reference for every crop, for three more launches and one more read of
+    every pre-downscaled frame."""
     f = frames if (isinstance(frames, torch.Tensor) and frames.device == dev()) else to_dev(frames, torch.uint8)
     B, Hs, Ws, _ = f.shape
     out4 = torch.empty((B, res, res, 4), dtype=_lib.act_dtype(), device=dev()) if want_nhwc4 else None
     outf = torch.empty((B, 3, res, res), dtype=torch.float32, device=dev()) if want_nchw else None
     out8 = torch.empty((B, res, res, 3), dtype=torch.uint8, device=dev()) if want_u8 else None
-    check(lib().pa_crop(ptr(f), Hs, Ws, ptr(sizes), ptr(params), B, res, ptr(_crop_workspace(B, Hs, Ws, res)), ptr(out4), ptr(outf),
-                        ptr(out8), stream()), 'pa_crop')
+    fn, name = (lib().pa_crop_stretch, 'pa_crop_stretch') if stretch else (lib().pa_crop, 'pa_crop')
+    check(fn(ptr(f), Hs, Ws, ptr(sizes), ptr(params), B, res, ptr(_crop_workspace(B, Hs, Ws, res, stretch)), ptr(out4), ptr(outf),
+             ptr(out8), stream()), name)
     return out4, outf, out8
 
 
@@ -117,16 +123,19 @@ def warp_batch(frames, tinv, params, res=256, want_nchw=False, want_nhwc4=True, 
     return out4, outf
 
 
-def crop(img, center, scale, rot, res, size):
+def crop(img, center, scale, rot, res, size, stretch=False):
     """Reference signature (pylib/HumanAug.py:117): H x W x 3 image (float [0,1] or uint8) -> res x res x 3 uint8, with the
-    reference's pixels (its PIL arithmetic restated on the device) except scipy's per-image min/max byte stretching."""
+    reference's pixels (its PIL arithmetic restated on the device).  stretch=False: without scipy's per-image min/max byte
+    stretching.  stretch=True: with it -- exact for float images whose values are k / 255 (k = 0..255, what a loaded uint8
+    image divided by 255 holds: the image is taken back to those bytes and the device works from them); other float values
+    are rounded to the nearest k / 255 first, and the result is then not the reference's."""
     if size != 200:
         raise ValueError('the reference always uses size == 200')
     a = np.asarray(img)
     if a.dtype != np.uint8:
         a = (np.clip(a.astype(np.float64) * 255.0, 0, 255) + 0.5).astype(np.uint8)      # toimage() with the full range
     p = make_params(np.asarray(center, dtype=np.float64).reshape(1, 2), [_scalar(scale)], [_scalar(rot)])
-    _, _, out8 = crop_batch(np.ascontiguousarray(a)[None], p, res=int(res), want_nhwc4=False, want_u8=True)
+    _, _, out8 = crop_batch(np.ascontiguousarray(a)[None], p, res=int(res), want_nhwc4=False, want_u8=True, stretch=stretch)
     return out8[0].cpu().numpy()
 
 

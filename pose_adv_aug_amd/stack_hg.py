@@ -200,7 +200,7 @@ def main(argv=None):
     else:
         ckpt.save_prefix = exp_dir + '/'
     broadcast_parameters(net)
-    augmenter = Augmenter(seed=1234 + rank)
+    augmenter = Augmenter(seed=1234 + rank, stretch=bool(opt.crop_stretch))     # (training and validation: the reference stretches both)
     vis = Visualizer(opt, log_path=os.path.join(exp_dir, 'train-log.txt' if opt.is_train else 'val-log.txt') if rank == 0 else None)
     log = (lambda m: (print(m), vis.write_log(m))) if rank == 0 else (lambda m: None)
     batches, val_batches = make_feeds(opt, rank, world, log)
