@@ -1179,11 +1179,26 @@ __global__ __launch_bounds__(1024) void cell_mask_kernel(PaOperand x, const floa
 int pa_launch_cell_mask(const PaOperand& x, const float* mask, const PaEpilogue& ep, bf16* out, int B, int H, int W, int C,
                         hipStream_t st) {
     if (H % 4 != 0 || W % 4 != 0 || C % 8 != 0) { pa_set_error_msg("pa_launch_cell_mask: the map must be a multiple of the 4x4 cell grid"); return 1; }
-    size_t total = (size_t)B * H * W * (C / 8);
+    const int CG = C / 8;
+    // flush_stats reduces the lanes of a wave that share a channel group by xor shuffles: a power of two, at most one wave wide
+    if (ep.mode != PA_OUT_PLAIN && (CG > 64 || (CG & (CG - 1)) != 0)) {
+        pa_set_error_msg("pa_launch_cell_mask: a statistics epilogue needs C / 8 a power of two <= 64"); return 1;
+    }
+    if (CG > 1024) { pa_set_error_msg("pa_launch_cell_mask: C / 8 exceeds the workgroup size"); return 1; }
+    size_t total = (size_t)B * H * W * CG;
     int blocks, threads;
     stream_launch_dims(total, blocks, threads);
+    // a thread keeps the channel group threadIdx.x % CG over its whole grid-stride walk: the workgroup size (and with it the stride)
+    // must be a multiple of CG.  256 / 512 are for every power of two; otherwise the largest multiple below (C = 24: 255, 384: 240)
+    if (threads % CG != 0) {
+        threads = CG > threads ? CG : threads / CG * CG;
+        blocks = (int)((total + threads - 1) / threads);
+        if (blocks > 512) blocks = 512;
+    }
     if (ep.rows_out) *ep.rows_out = blocks;
-    hipLaunchKernelGGL(cell_mask_kernel, dim3(blocks), dim3(threads), (threads / 64) * 2 * C * sizeof(float), st, x, mask, ep, out, B, H, W, C);
+    // flush_stats' LDS: one row of 2 * C floats per wave (a plain epilogue never reaches it)
+    const size_t lds = ep.mode != PA_OUT_PLAIN ? (size_t)((threads + 63) / 64) * 2 * C * sizeof(float) : 0;
+    hipLaunchKernelGGL(cell_mask_kernel, dim3(blocks), dim3(threads), lds, st, x, mask, ep, out, B, H, W, C);
     return (int)hipGetLastError();
 }
 

@@ -300,15 +300,17 @@ def bgrad_check(got, dy, S):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the net (GPU legs)
-def block_sites(stacks):
+def block_sites(stacks, masked=False):
     """(parameter prefix of the residual block, debug-hook name of its output, hook name of its input, has adapter), every block of the
-    pose net, wired as Net::forward_pose_body / Hourglass::encode / decode (net.hip:703-742, 912-942)."""
+    pose net, wired as Net::forward_pose_body / Hourglass::encode / decode (net.hip:703-742, 912-942).  masked: the step ran with
+    occlusion masks -- up4 reads maskedneck, the neck's output times the cell mask (a plain tensor); no other block's input changes
+    (the skip blocks read xin / down, up3..1 and post read merges, which then hold the masked skip tensors)."""
     s = [('residual1.', 'res1', 'stem', True), ('residual2.', 'res2', 'pool0', False), ('residual3.', 'res3', 'res2', True)]
     for i in range(stacks):
         for k in (1, 2, 3, 4):
             s.append(('hg.%d.skip%d.0.' % (i, k), 'hg%d.skip%d' % (i, k), 'xin%d' % i if k == 1 else 'hg%d.down%d' % (i, k - 1), False))
             s.append(('hg.%d.down%d.0.' % (i, k), 'hg%d.down%d' % (i, k), 'hg%d.pool%d' % (i, k), False))
-            s.append(('hg.%d.up%d.0.' % (i, k), 'hg%d.up%d' % (i, k), 'hg%d.neck' % i if k == 4 else 'hg%d.merge%d' % (i, k + 1), False))
+            s.append(('hg.%d.up%d.0.' % (i, k), 'hg%d.up%d' % (i, k), ('hg%d.maskedneck' if masked else 'hg%d.neck') % i if k == 4 else 'hg%d.merge%d' % (i, k + 1), False))
         s.append(('hg.%d.neck.0.' % i, 'hg%d.neck' % i, 'hg%d.down4' % i, False))
         s.append(('post_res.%d.0.' % i, 'post%d' % i, 'hg%d.merge1' % i, False))
     return s
@@ -469,16 +471,18 @@ def heat_grad_check(got, heat, target, gscale, add, dtype):
     return check16(got, Term(g.v, g.e, mag), dtype)
 
 
-def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
+def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh', masks=None):
     """One training step (loss_and_backward, default multi-stream mode) behind `history` (tests/exact_history.py: 'fresh' = the first
     step after the bind), then every check.  Returns {kind: worst error / bound} and the failures.  expect: weight-gradient split
-    kinds this leg must meet ('group': a layer whose split count is the grouped kernel's)."""
+    kinds this leg must meet ('group': a layer whose split count is the grouped kernel's).  masks (a seed): the checked step runs with
+    occlusion masks (tests/exact_history.py)."""
     from pose_adv_aug_amd._lib import act_dtype, grad_scale
     from tests import exact_history, inputs
     from tests.bn_exact import Probe
     from tests.test_gpu_net import t
+    assert stacks <= 9, 'stack indexes are read as one character (w[3] - \'0\' in pa_hg_debug_tensor)'
     dtype = act_dtype()
-    S = exact_history.pose_step(stacks, chan, B, res, seed, history)
+    S = exact_history.pose_step(stacks, chan, B, res, seed, history, masks=masks)
     net, sd0, img, pts_np, outs, loss_total, grads = S.net, S.sd0, S.img, S.pts_np, S.outs, S.loss_total, S.grads
     names = conv_names(stacks)
     assert sorted(names) == sorted(k[:-len('.weight')] for k in sd0 if k.endswith('.weight') and sd0[k].dim() == 4), \
@@ -502,9 +506,10 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
     # storage type), and skip k's conv1 data gradient adds it as its SECOND addend (Residual::bwd_b, net.hip:687).  res1's output has
     # no conv reader (pool0 only): nothing to check here.  (That the pool routed correctly: tests/bn_exact.py 'pool backward'.)
     skip_k = dict([('xin%d' % i, (i, 1)) for i in range(stacks)] + [('hg%d.down%d' % (i, k), (i, k + 1)) for i in range(stacks) for k in (1, 2, 3)])
-    # a pending BatchNorm (masked gradient): the stem and block outputs (xin0 is residual3's); not the pools, merges or xin<i>, i >= 1
-    has_bn = lambda n: not ('pool' in n or 'merge' in n or (n.startswith('xin') and n != 'xin0'))
-    for p, out, inp, ad in block_sites(stacks):
+    # a pending BatchNorm (masked gradient): the stem and block outputs (xin0 is residual3's); not the pools, merges, xin<i>, i >= 1, or
+    # the occlusion branch's maskedneck (d maskedneck = conv1^T + dz3 of up4 through a plain epilogue: no ReLU mask)
+    has_bn = lambda n: not ('pool' in n or 'merge' in n or 'masked' in n or (n.startswith('xin') and n != 'xin0'))
+    for p, out, inp, ad in block_sites(stacks, masked=S.masks is not None):
         add2 = P.get('hg%d.poolgrad%d' % skip_k[inp], 2) if inp in skip_k else None          # the pool's routed gradient
         ck.block(p, out, P, P, inp, True, ad, add2, has_bn(inp))
         del add2
@@ -578,7 +583,7 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh'):
             fails.append(('coverage', 'no layer of this leg has a shape of the %s weight-gradient split' % kind, 0))
     if os.environ.get('POSEADV_TEST_VERBOSE'):
         log('conv_exact %s %s stacks %d chan %d B %d res %d: worst error / bound: %s; %d convs, %d with grouped splits'
-            % ('fp16' if dtype == torch.float16 else 'bf16', history, stacks, chan, B, res,
+            % ('fp16' if dtype == torch.float16 else 'bf16', history + (' masked' if S.masks is not None else ''), stacks, chan, B, res,
                ', '.join('%s %.3g' % (k, worst[k]) for k in KINDS), len(set(c for c, _ in checked)), met['group']))
     return worst, fails
 

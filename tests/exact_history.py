@@ -24,13 +24,20 @@ the two meters of train_step), two batches in alternation so that no step sees t
               tables, the heat-peak cache, the training statistics of a forward nobody finished;
   after_half  one train_step; the agent's half-hourglass forward on the pose net in train mode (pa_hg_forward_half, train = 1) and an
               agent backward with seeded targets; the checked FULL step.  The agent needs res >= 256.
+  after_masked  one loss_and_backward(dropout_masks=...) and an optimizer step, then the checked step WITHOUT masks: what a masked step
+              leaves behind (Net::drop_mask, Hourglass::low_done / Residual::low_of_in, the gradients of the masked copies) while the
+              fused upsample-add paths and the consumer-prologue finalizes come back on.  The mask needs a 4 x 4 neck: res 256.
+masks (a seed): the checked step is the occlusion agent's training step, loss_and_backward(dropout_masks=M), M [B][1][4][4] of 0 / 1 with
+two zero cells per sample (drop_masks); the steps of 'warm' in front of it are masked too, each with another draw (loss_and_backward
+and the optimizer called as train_step calls them: train_step takes no masks).  Only with 'fresh' and 'warm': a captured graph and the
+phased backward pass do not run with masks.
 For the agent (agent_history): 'warm' is two pose train_step calls and two agent steps (forward, backward or backward_masks,
 an RMSprop step of the agent's own optimizer); 'after_eval' one agent step and the same eval / train-forward interleaving on the
 agent.  Before the agent steps the pose net's running estimates are set to the statistics of a crop batch (calibrate)."""
 import numpy as np
 import torch
 
-POSE_HISTORIES = ('fresh', 'warm', 'graph', 'phased', 'after_eval', 'after_half')
+POSE_HISTORIES = ('fresh', 'warm', 'graph', 'phased', 'after_eval', 'after_half', 'after_masked')
 AGENT_HISTORIES = ('fresh', 'warm', 'after_eval')
 LR = 2.5e-4
 
@@ -75,34 +82,67 @@ def _snapshot(module):
 
 class Step(object):
     """the checked pose step: net; sd0 / before (all entries / the running estimates, cloned immediately before it); img (NCHW fp32, as
-    the engine read it); pts (device) and pts_np; grads, outs, loss_total and losses (the per-stack values) after it"""
+    the engine read it); pts (device) and pts_np; grads, outs, loss_total and losses (the per-stack values) after it; masks: the
+    [B][1][4][4] occlusion masks of the checked step (device, fp32) or None"""
 
 
-def pose_step(stacks, chan, B, res, seed, history='fresh'):
+FORCED_CELLS = ((0, 15), (5, 6))        # sample 0: two corners of the map; sample 1: interior and adjacent
+
+
+def drop_masks(seed, B, draw=0):
+    """[B][1][4][4] fp32 of 0 / 1, two distinct zero cells per sample (what pa_sample_dropout_masks draws).  Draw 0, the checked step's:
+    samples 0 and 1 take FORCED_CELLS, so that every leg has cells on the map border and a pair sharing an edge."""
+    from tests import inputs
+    g = inputs.rng(seed, 77, draw)
+    M = torch.ones(B, 1, 4, 4)
+    for b in range(B):
+        cells = g.choice(16, 2, replace=False)
+        if draw == 0 and b < len(FORCED_CELLS):
+            cells = FORCED_CELLS[b]
+        for cell in cells:
+            M[b, 0, int(cell) // 4, int(cell) % 4] = 0
+    assert bool((M.view(B, 16).sum(1) == 14).all())
+    return M
+
+
+def _masked_train_step(net, opt, data, M):
+    """stack_hg.train_step with masks: the same two calls"""
+    net.loss_and_backward(img4=data['img4'], pts=data['pts'], dropout_masks=M, after_forward=_meters(net, data))
+    opt.step()
+
+
+def pose_step(stacks, chan, B, res, seed, history='fresh', masks=None):
     from pose_adv_aug_amd.stack_hg import train_step
     from pose_adv_aug_amd.utils.optim import RMSprop
     from tests import inputs
     from tests.test_gpu_net import t, _hg_pair
     assert history in POSE_HISTORIES, history
+    assert masks is None or history in ('fresh', 'warm'), 'no masked step behind %s' % history
     torch.cuda.set_device(0)
     ref, net = _hg_pair(stacks, chan, B, res, seed=seed)
     del ref
     S = Step()
     S.net, S.history = net, history
+    S.masks = None if masks is None else drop_masks(masks, B).cuda()
     net.train()
     if history == 'fresh':
         S.sd0, S.before = _snapshot(net)
         S.img = t(inputs.images(seed + 100, B, res)).cuda()
         S.pts_np = inputs.heat_pts(seed + 101, B, res=res // 4)
         S.pts = t(S.pts_np).cuda()
-        loss, S.outs = net.loss_and_backward(S.img, S.pts, want_outputs=True)
+        loss, S.outs = net.loss_and_backward(S.img, S.pts, want_outputs=True, dropout_masks=S.masks)
     else:
         feed = Feed(B, res, seed)
         opt = RMSprop(net, lr=LR, overlap=(history == 'phased'))
         if history == 'graph':
             net.use_graph = True
-        for _ in range({'warm': 3, 'graph': 3, 'phased': 2, 'after_eval': 1, 'after_half': 1}[history]):
-            train_step(net, opt, feed.aug, feed.next_batch())
+        for k in range({'warm': 3, 'graph': 3, 'phased': 2, 'after_eval': 1, 'after_half': 1, 'after_masked': 0}[history]):
+            if masks is None:
+                train_step(net, opt, feed.aug, feed.next_batch())
+            else:
+                _masked_train_step(net, opt, feed.next_data(), drop_masks(masks, B, draw=k + 1).cuda())
+        if history == 'after_masked':
+            _masked_train_step(net, opt, feed.next_data(), drop_masks(seed, B).cuda())
         if history == 'after_eval':
             other = feed.next_data(want_nchw=True)
             net.eval()
@@ -128,7 +168,8 @@ def pose_step(stacks, chan, B, res, seed, history='fresh'):
         if history == 'graph':
             loss, S.outs = net.loss_and_backward(img4=data['img4'], pts=data['pts'], want_outputs=True)
         else:
-            loss, S.outs = net.loss_and_backward(img4=data['img4'], pts=data['pts'], want_outputs=True, after_forward=_meters(net, data))
+            loss, S.outs = net.loss_and_backward(img4=data['img4'], pts=data['pts'], want_outputs=True, dropout_masks=S.masks,
+                                                 after_forward=_meters(net, data))
         S.data = data
     S.loss_total = loss.clone()
     S.losses = net._last_losses

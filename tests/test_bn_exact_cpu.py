@@ -184,3 +184,71 @@ def test_bit_exact_checks_catch_one_ulp_and_another_summation_order(dtype, B, H,
     differs = int((other != dup).sum())
     assert differs > 0
     assert X.check_merge_bwd(dm, vu, vs, other, dsk, dtype) == differs
+
+
+# ---- the occlusion branch: masked copies of the skip / neck tensors (check_mask_fwd, check_merge_bwd_masked, check_mask_bwd)
+def _masks(B):
+    """two zero cells per sample: the map corners, then an interior pair sharing an edge (tests/exact_history.FORCED_CELLS)"""
+    M = torch.ones(B, 1, 4, 4)
+    for b, cells in enumerate(((0, 15), (5, 6))[:B]):
+        for c in cells:
+            M[b, 0, c // 4, c % 4] = 0
+    return M
+
+
+def _emulate_masked(vs, vu, dm, M, dtype, shift=None, fwd_only=False, mask_up=False, no_relu=False):
+    """Hourglass::encode / decode / bwd under Net::drop_mask on storage-type tensors: the masked copy of the skip tensor, the merge
+    over it, and the two gradients.  shift: (dim, cells) the engine's mask is displaced by; fwd_only: the backward launch forgets the
+    mask; mask_up: the mask lands on the upsampled tensor, not on the skip; no_relu: d skip without the ReLU factor of skip."""
+    H = vs.shape[2]
+    m = X.up4(M if shift is None else torch.roll(M, shift[1], dims=shift[0]), H)
+    if mask_up:
+        masked = X.rnd(vs, dtype)
+        merged = X.rnd(X.up2(vu) * m + masked, dtype)
+    else:
+        masked = X.rnd(vs, dtype) * m
+        merged = X.rnd(X.up2(vu) + masked, dtype)
+    dup = X.rnd(X.sum2x2(dm), dtype) * (vu > 0).float()
+    dmasked = dm.clone()
+    dsk = dmasked * (torch.ones_like(m) if (fwd_only or mask_up) else m) * (torch.ones_like(vs) if no_relu else (vs > 0).float())
+    return dict(masked=masked, merged=merged, dup=dup, dmasked=dmasked, dsk=dsk)
+
+
+def _masked_checks(vs, vu, dm, M, dtype, e):
+    return {'mask forward': X.check_mask_fwd(vs, M, e['masked'], dtype),
+            'merge forward': X.check_merge_fwd(vu, e['masked'], e['merged'], dtype),
+            'merge backward': X.check_merge_bwd_masked(dm, vu, e['dup'], e['dmasked'], dtype),
+            'mask backward': X.check_mask_bwd(e['dmasked'], M, vs, e['dsk'])}
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('H', [64, 8, 4])
+def test_masked_merge_checks_pass_the_emulation_and_report_each_defect(dtype, H):
+    B, Cc = 2, 4
+    g = torch.Generator().manual_seed(H)
+    vs = torch.relu(torch.randn(B, Cc, H, H, generator=g))                   # BatchNorm+ReLU-applied fp32 values: zeros and positives everywhere
+    vu = torch.relu(torch.randn(B, Cc, H // 2, H // 2, generator=g))
+    dm = X.rnd(torch.randn(B, Cc, H, H, generator=g), dtype)
+    M = _masks(B)
+    ck = lambda **kw: _masked_checks(vs, vu, dm, M, dtype, _emulate_masked(vs, vu, dm, M, dtype, **kw))
+    assert ck() == {'mask forward': 0, 'merge forward': 0, 'merge backward': 0, 'mask backward': 0}
+    for dim in (2, 3):                                                        # the mask one cell off in y, in x
+        bad = ck(shift=(dim, 1))
+        assert bad['mask forward'] > 0 and bad['mask backward'] > 0, bad
+    bad = ck(fwd_only=True)
+    assert bad['mask backward'] > 0 and bad['mask forward'] == 0 and bad['merge forward'] == 0, bad
+    bad = ck(mask_up=True)
+    assert bad['mask forward'] > 0 and bad['merge forward'] > 0, bad
+    bad = ck(no_relu=True)
+    assert bad['mask backward'] > 0 and bad['mask forward'] == 0 and bad['merge backward'] == 0, bad
+    # one element one ulp off, in each tensor the masked step adds (a kept cell: the last pixel of sample 1 is cell 15, kept there)
+    e = _emulate_masked(vs, vu, dm, M, dtype)
+    for key, kind in (('masked', 'mask forward'), ('dmasked', 'merge backward'), ('dsk', 'mask backward')):
+        t = e[key].clone()
+        j = int((t.view(-1) != 0).nonzero()[-1])
+        t.view(-1)[j] = _next_ulp(float(t.view(-1)[j]), dtype)
+        r = _masked_checks(vs, vu, dm, M, dtype, dict(e, **{key: t}))
+        assert r[kind] == 1, (key, r)
+    # the gradient of the masked copy is d merged itself: a ReLU mask there is reported
+    r = _masked_checks(vs, vu, dm, M, dtype, dict(e, dmasked=e['dmasked'] * (vs > 0).float()))
+    assert r['merge backward'] > 0

@@ -198,3 +198,21 @@ def test_split_mirror_knows_the_net_layers_and_refuses_unknown_shapes():
         X.wgrad_splits(100, 10, 10, 96, 64, 1)
     with pytest.raises(ValueError):
         X.wgrad_splits(100, 10, 10, 64, 64, 4)
+
+
+def test_data_gradient_of_a_plain_input_catches_a_relu_mask():
+    """up4 in a step with occlusion masks reads maskedneck, a plain tensor (no pending BatchNorm): its gradient conv1^T(g1) + dz3 goes
+    through a plain epilogue and is checked without a mask (Checker.block(in_masked=False)).  A gradient that was masked by the ReLU of
+    the tensor's value -- which is zero inside the dropped cells and wherever the neck's ReLU cut -- is outside the bound."""
+    B, C, N, H = 2, 128, 64, 4
+    g, _, w, _ = _data(B, C, N, H, 1, seed=21)
+    dy = torch.randn(B, N, H, H, generator=g, dtype=torch.float64).to(BF).double()              # g1, the gradient of up4.x1
+    dz3 = torch.randn(B, C, H, H, generator=g, dtype=torch.float64).to(BF).double()             # the shortcut's addend
+    value = torch.relu(torch.randn(B, C, H, H, generator=g, dtype=torch.float64)).to(BF).double()
+    value[0, :, 0, 0] = 0                                                                       # a dropped cell
+    t = X.dgrad_term(dy, w, N, (dz3,))
+    dx = emulate_conv(dy, w.flip(2, 3).transpose(0, 1), add=(dz3,))
+    assert X.check16(dx, t, BF, None)[0] <= 1.0
+    assert X.check16(dx * (value > 0).double(), t, BF, None)[0] > 1.0
+    # (and the converse stays caught: a plain gradient where the check expects the mask)
+    assert X.check16(dx, t, BF, (value > 0).double())[0] > 1.0

@@ -6,7 +6,10 @@ statistics row, a wrong variance, a wrong summation order or a rounding error of
 Legs: BASELINE configs[1] at full size (the only leg that reaches the fused low-resolution half of the upsample-add backward in the 1 x 1
 data gradient's epilogue, the split upsample-add launches, 1536-row statistics and the consumer-prologue finalize at <= 128 rows); the
 configs[4] geometry (384 x 384: the 24 x 24 / 12 x 12 tiled 3 x 3 variants, the masked 6 x 6 neck) at a ragged batch; tiny maps (2 x 2 neck,
-8 values per channel: biased and unbiased variance differ by 14 %); and the IEEE-half build on the configs[4] geometry in a child process."""
+8 values per channel: biased and unbiased variance differ by 14 %); and the IEEE-half build on the configs[4] geometry in a child process.
+Then the tiny-maps size at 1, 3 and 8 stacks (no inner head; a middle stack -- a plain xin<i> with a nonzero gradient arriving from the
+next stack; the configs[4] depth), 3 stacks behind a phased / warm history and in the IEEE-half build, and the step with occlusion masks
+(loss_and_backward(dropout_masks=...), the occlusion agent's training path) at 256 x 256, the smallest size with a 4 x 4 neck."""
 import os
 import subprocess
 import sys
@@ -55,6 +58,41 @@ def test_every_bn_pool_and_merge_is_exact_after_a_history_at_256(history):
     _leg(2, 128, 2, 256, 36, history=history)
 
 
+# ---- stack counts other than two.  One stack: forth / inc / dheat_in / lgrad_tmp are empty.  Three: stack 1 is neither first nor last
+# (run_leg asserts that pool 1 of every middle stack met a nonzero addend over an input without a pending BatchNorm).  Eight: the depth
+# of BASELINE configs[4].
+@pytest.mark.parametrize('stacks', (1, 3, 8))
+def test_every_bn_pool_and_merge_is_exact_on_tiny_maps_at_other_stack_counts(stacks):
+    _leg(stacks, 128, 2, 128, 51, stored_expected=('.x2',))
+
+
+def test_every_bn_pool_and_merge_is_exact_with_a_middle_stack_in_the_phased_backward():
+    """3 stacks, tiny maps, RMSprop(overlap=True): four phases of pa_hg_backward_phase, phase 1 a middle stack."""
+    _leg(3, 128, 2, 128, 52, stored_expected=('.x2',), history='phased')
+
+
+def test_every_bn_pool_and_merge_is_exact_with_a_middle_stack_after_warm_steps_at_256():
+    _leg(3, 128, 2, 256, 53, history='warm')
+
+
+# ---- the step with occlusion masks: 2 stacks, chan 128, B 2, 256 x 256 as the history legs above.  Which blocks store dz2 / dz3 does not
+# change under masks: Net::drop_mask switches x3_fin_ok off, which only moves x3's backward FINALIZE out of conv3's data-gradient prologue
+# into a launch of its own; whether that data gradient stores dz3 (dz2) is Net::conv_dgrad's pa_conv1x1_tile_supported /
+# pa_conv3x3_tile_supported over the shape alone (net.hip:425-429), and the 64 x 64 maps of these legs are taken by both.  So both kinds stay expected.
+@pytest.mark.parametrize('history', ('fresh', 'warm'))
+def test_every_bn_pool_merge_and_cell_mask_is_exact_in_a_masked_step(history):
+    _leg(2, 128, 2, 256, 54, history=history, masks=540)
+
+
+def test_every_bn_pool_and_merge_is_exact_in_the_step_after_a_masked_one():
+    """'after_masked': a masked step and an optimizer step, then the checked step without masks."""
+    _leg(2, 128, 2, 256, 55, history='after_masked')
+
+
+def test_every_bn_pool_merge_and_cell_mask_is_exact_in_a_masked_step_with_a_middle_stack():
+    _leg(3, 128, 2, 256, 56, masks=560)
+
+
 def _fp16_child(args):
     env = dict(os.environ, POSEADV_DTYPE='fp16')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'bn_exact.py')] + args, env=env, capture_output=True, text=True, timeout=900)
@@ -66,6 +104,15 @@ def _fp16_child(args):
 def test_every_bn_pool_and_merge_is_exact_after_warm_steps_in_the_fp16_build():
     """The IEEE-half library, 'warm' at chan 128, B 2, 256 x 256, in a child process."""
     _fp16_child(['2', '128', '2', '256', '37', 'warm'])
+
+
+def test_every_bn_pool_and_merge_is_exact_with_a_middle_stack_in_the_fp16_build():
+    """The IEEE-half library, 3 stacks on the 96 / 48 / 24 / 12 / 6 geometry at chan 128, B 2."""
+    _fp16_child(['3', '128', '2', '384', '57'])
+
+
+def test_every_bn_pool_merge_and_cell_mask_is_exact_in_a_masked_step_in_the_fp16_build():
+    _fp16_child(['2', '128', '2', '256', '58', 'fresh', '580'])
 
 
 def test_every_bn_pool_and_merge_is_exact_in_the_fp16_build():

@@ -5,7 +5,7 @@ bias or addend or an 8-channel group with its neighbour's constants is a few per
 a failure.
 
 Legs (as tests/test_gpu_bn_exact.py): BASELINE configs[1] at full size; the configs[4] geometry (maps 96 / 48 / 24 / 12 / 6) at B 3; tiny
-maps; the IEEE-half build on the configs[4] geometry in a child process.  Then every shape of tests/test_gpu_conv.SHAPES through pa_conv2d
+maps; the IEEE-half build on the configs[4] geometry in a child process; 1, 3 and 8 stacks; the step with occlusion masks.  Then every shape of tests/test_gpu_conv.SHAPES through pa_conv2d
 in all three modes, and the split-count mirror against the library's workspace sizes.
 
 What a leg guards is geometric only: it has the map sizes that conv3x3_tile.hip's dispatch sends to the tiled 24 x 24 / 12 x 12 and masked
@@ -62,6 +62,52 @@ def test_every_conv_is_exact_after_a_history_at_256(history):
     takes the 3 x 3 layers there ('group', from the split mirror), beside the tile kernels.  'after_half' runs here: the agent accepts
     no res below 256."""
     _leg(2, 128, 2, 256, 46, expect=('group',), history=history)
+
+
+# ---- stack counts other than two (as tests/test_gpu_bn_exact.py): no inner head; a middle stack, whose xin<i> is written by
+# in_conv.<i-1> and read in the backward pass by forth_conv.<i> and in_conv.<i>; the configs[4] depth
+@pytest.mark.parametrize('stacks', (1, 3, 8))
+def test_every_conv_is_exact_on_tiny_maps_at_other_stack_counts(stacks):
+    _leg(stacks, 128, 2, 128, 61)
+
+
+def test_every_conv_is_exact_with_a_middle_stack_in_the_phased_backward():
+    _leg(3, 128, 2, 128, 62, history='phased')
+
+
+def test_every_conv_is_exact_with_a_middle_stack_after_warm_steps_at_256():
+    _leg(3, 128, 2, 256, 63, expect=('group',), history='warm')
+
+
+# ---- the step with occlusion masks (loss_and_backward(dropout_masks=...)): up4 reads maskedneck, the decoder's merges hold masked skips
+@pytest.mark.parametrize('history', ('fresh', 'warm'))
+def test_every_conv_is_exact_in_a_masked_step(history):
+    _leg(2, 128, 2, 256, 64, expect=('group',), history=history, masks=640)
+
+
+def test_every_conv_is_exact_in_the_step_after_a_masked_one():
+    _leg(2, 128, 2, 256, 65, expect=('group',), history='after_masked')
+
+
+def test_every_conv_is_exact_in_a_masked_step_with_a_middle_stack():
+    _leg(3, 128, 2, 256, 66, expect=('group',), masks=660)
+
+
+def _fp16_child(args):
+    env = dict(os.environ, POSEADV_DTYPE='fp16')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'conv_exact.py')] + args, env=env, capture_output=True, text=True, timeout=900)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print(r.stdout)
+    assert r.returncode == 0 and 'FP16 CONV EXACT PASSED' in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+def test_every_conv_is_exact_with_a_middle_stack_in_the_fp16_build():
+    """The IEEE-half library, 3 stacks on the 96 / 48 / 24 / 12 / 6 geometry at chan 128, B 2."""
+    _fp16_child(['3', '128', '2', '384', '67'])
+
+
+def test_every_conv_is_exact_in_a_masked_step_in_the_fp16_build():
+    _fp16_child(['2', '128', '2', '256', '68', 'fresh', '680'])
 
 
 def test_every_conv_is_exact_after_warm_steps_in_the_fp16_build():

@@ -32,10 +32,26 @@ def _up(masks, H):
     return torch.nn.functional.interpolate(masks, scale_factor=H // 4, mode='nearest') if H > 4 else masks
 
 
+def _cell_mask_into_nan(x, masks):
+    """pa_cell_mask as models.asn_stacked_hg.dropout calls it, but into an output filled with NaN: an element the kernel never wrote
+    cannot pass by what the allocator left there."""
+    from pose_adv_aug_amd._lib import lib, check, ptr, stream, act_dtype
+    B, Cc, H, W = x.shape
+    assert Cc % 8 == 0
+    xh = x.permute(0, 2, 3, 1).to(act_dtype()).contiguous()
+    out = torch.full_like(xh, float('nan'))
+    m = masks.to(x.device, torch.float32).reshape(B, 16).contiguous()
+    check(lib().pa_cell_mask(ptr(xh), ptr(m), ptr(out), B, H, W, Cc, stream()), 'pa_cell_mask')
+    return out.permute(0, 3, 1, 2).float()
+
+
 def test_cell_mask_operator_is_exact():
+    """The last four shapes have C / 8 = 3, 5, 48, 80 channel groups, no power of two: a thread's channel group (threadIdx.x % (C / 8))
+    agrees with its element only where the workgroup size and the grid stride are multiples of C / 8 (pa_launch_cell_mask).  (1, 40, 4)
+    is one workgroup without a stride, the other three are not."""
     from pose_adv_aug_amd.models.asn_stacked_hg import dropout
     g = inputs.rng(301)
-    for (B, Cc, H) in ((2, 8, 4), (3, 16, 16), (2, 256, 64)):
+    for (B, Cc, H) in ((2, 8, 4), (3, 16, 16), (2, 256, 64), (2, 24, 8), (1, 40, 4), (2, 384, 16), (3, 640, 8)):
         x = bf16r(t(g.standard_normal((B, Cc, H, H)).astype(np.float32)))
         masks = torch.ones(B, 1, 4, 4)
         for b in range(B):
@@ -44,6 +60,8 @@ def test_cell_mask_operator_is_exact():
         want = om.Hourglass.dropout(x, masks)
         got = dropout(x.cuda(), masks.cuda()).cpu()
         assert torch.equal(got, want), (B, Cc, H)
+        got = _cell_mask_into_nan(x.cuda(), masks.cuda()).cpu()
+        assert torch.equal(got, want), (B, Cc, H, 'NaN-filled output', int((got != want).sum()))
 
 
 def test_mask_sampler_law_and_replay():
