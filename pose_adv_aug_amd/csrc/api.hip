@@ -177,6 +177,8 @@ size_t pa_residual_workspace_bytes(int B, int H, int W, int C) {
 int pa_residual_fwd_bwd(const float* x, const float* dy, const float* params, float* y, float* dx, float* grads, float* buffers,
                         int B, int C, int H, int W, void* ws, void* s) {
     g_err[0] = 0;
+    // (before any launch: the block's gradient enters through pa_launch_ep_apply with a statistics epilogue)
+    if (!pa_stats_groups_ok(C)) { pa_set_error_msg("pa_residual_fwd_bwd: " PA_STATS_GROUPS_MSG); return 1; }
     ResidualOp op; Net& n = op.n;
     n.is_agent = true; n.B = B; n.st = ST(s);
     op.r.declare(n, "", C, C, false);
@@ -434,6 +436,7 @@ pa_net* pa_hg_create(int num_stacks, int num_classes, int chan, int B, int res) 
         pa_set_error_msg("pa_hg_create: need num_classes == 16, chan % 128 == 0, res % 64 == 0");
         return nullptr;
     }
+    if (!pa_stats_groups_ok(chan)) { pa_set_error_msg("pa_hg_create: " PA_STATS_GROUPS_MSG); return nullptr; }
     pa_net* p = new (std::nothrow) pa_net;
     if (!p) return nullptr;
     Net& n = p->n;
@@ -449,6 +452,7 @@ pa_net* pa_asn_create(int chan, int scale_num, int rotation_num, int B, int res)
         pa_set_error_msg("pa_asn_create: need chan % 128 == 0, res % 64 == 0, scale_num + rotation_num <= 64");
         return nullptr;
     }
+    if (!pa_stats_groups_ok(chan)) { pa_set_error_msg("pa_asn_create: " PA_STATS_GROUPS_MSG); return nullptr; }
     // the head is AvgPool2d(4) + view + Linear(chan, K) (reference :375, :430-436): the pool of the res / 64 top map must have exactly
     // one output (a map below 4 x 4 has none: the reference raises; from 8 x 8 on there are four and its Linear does not fit)
     if (res / 64 < 4 || res / 64 > 7) {
@@ -470,6 +474,7 @@ pa_net* pa_asn_create_dropout(int chan, int B, int res) {
         pa_set_error_msg("pa_asn_create_dropout: need chan % 128 == 0 and res == 256 (4x4 neck map)");
         return nullptr;
     }
+    if (!pa_stats_groups_ok(chan)) { pa_set_error_msg("pa_asn_create_dropout: " PA_STATS_GROUPS_MSG); return nullptr; }
     pa_net* p = new (std::nothrow) pa_net;
     if (!p) return nullptr;
     Net& n = p->n;

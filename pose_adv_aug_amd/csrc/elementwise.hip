@@ -16,6 +16,11 @@
 // TIMING EXPERIMENT (tuning builds, PA_FIN_ANYORDER=1; results may be WRONG): the finalize launches without the completion / cache round trip
 // behind their producer (hipExtAnyOrderLaunch) -- what a tagged-row hand-off from the producers to the finalize kernel could return at most
 static unsigned fin_launch_flags() { return pa_tuning().fin_anyorder ? hipExtAnyOrderLaunch : 0u; }
+template <class... P, class... A>
+static void fin_launch(void (*kernel)(P...), dim3 grid, int threads, hipStream_t st, A... args) {
+    if (fin_launch_flags()) hipExtLaunchKernelGGL(kernel, grid, dim3(threads), 0, st, nullptr, nullptr, fin_launch_flags(), static_cast<P>(args)...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, st, static_cast<P>(args)...);
+}
 
 // ------------------------------------------------------------------------------------------------
 // BatchNorm bookkeeping (reference semantics: torch.nn.BatchNorm2d, eps 1e-5, momentum 0.1,
@@ -145,12 +150,8 @@ int pa_launch_bn_finalize(const float* stats, int rows, const float* gamma, cons
     if (C & 1) { pa_set_error_msg("BatchNorm finalize: the statistics rows are read as 16-byte channel pairs -- C must be even (the networks pad to 64)"); return 1; }
     fin_dispatch([&](auto ft, auto fc) {
         constexpr int FT = decltype(ft)::value, FC = decltype(fc)::value;
-        if (fin_launch_flags())
-            hipExtLaunchKernelGGL((bn_finalize_kernel<FT, FC>), dim3((C + FC - 1) / FC), dim3(FT), 0, st, nullptr, nullptr, fin_launch_flags(), stats, rows, gamma, beta, rmean, rvar, scale,
-                                  shift, mean, invstd, C, count, momentum, eps, update_running);
-        else
-            hipLaunchKernelGGL((bn_finalize_kernel<FT, FC>), dim3((C + FC - 1) / FC), dim3(FT), 0, st, stats, rows, gamma, beta, rmean, rvar, scale,
-                               shift, mean, invstd, C, count, momentum, eps, update_running);
+        fin_launch(bn_finalize_kernel<FT, FC>, dim3((C + FC - 1) / FC), FT, st, stats, rows, gamma, beta, rmean, rvar, scale, shift, mean, invstd, C, count,
+                   momentum, eps, update_running);
     });
     return (int)hipGetLastError();
 }
@@ -225,8 +226,7 @@ int pa_launch_bn_bwd_finalize2(const float* bs0, int rows0, const float* sc0, co
     const int cm = C0 > C1 ? C0 : C1;
     fin_dispatch([&](auto ft, auto fc) {
         constexpr int FT = decltype(ft)::value, FC = decltype(fc)::value;
-        if (fin_launch_flags()) hipExtLaunchKernelGGL((bn_bwd_finalize2_kernel<FT, FC>), dim3((cm + FC - 1) / FC, 2), dim3(FT), 0, st, nullptr, nullptr, fin_launch_flags(), a0, a1);
-        else hipLaunchKernelGGL((bn_bwd_finalize2_kernel<FT, FC>), dim3((cm + FC - 1) / FC, 2), dim3(FT), 0, st, a0, a1);
+        fin_launch(bn_bwd_finalize2_kernel<FT, FC>, dim3((cm + FC - 1) / FC, 2), FT, st, a0, a1);
     });
     return (int)hipGetLastError();
 }
@@ -237,28 +237,12 @@ int pa_launch_bn_bwd_finalize(const float* bstats, int rows, const float* scale,
     if (C & 1) { pa_set_error_msg("BatchNorm finalize: the statistics rows are read as 16-byte channel pairs -- C must be even (the networks pad to 64)"); return 1; }
     fin_dispatch([&](auto ft, auto fc) {
         constexpr int FT = decltype(ft)::value, FC = decltype(fc)::value;
-        if (fin_launch_flags()) {
-            hipExtLaunchKernelGGL((bn_bwd_finalize_kernel<FT, FC>), dim3((C + FC - 1) / FC), dim3(FT), 0, st, nullptr, nullptr, fin_launch_flags(), bstats, rows, scale, mean, invstd, kA, kB,
-                           kC, dgamma, dbeta, C, count);
-        } else {
-            hipLaunchKernelGGL((bn_bwd_finalize_kernel<FT, FC>), dim3((C + FC - 1) / FC), dim3(FT), 0, st, bstats, rows, scale, mean, invstd, kA, kB,
-                           kC, dgamma, dbeta, C, count);
-        }
+        fin_launch(bn_bwd_finalize_kernel<FT, FC>, dim3((C + FC - 1) / FC), FT, st, bstats, rows, scale, mean, invstd, kA, kB, kC, dgamma, dbeta, C, count);
     });
     return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void load8_rt(const PaOperand& op, size_t idx, int c, float (&v)[8]) {
-    if (op.mode == PA_LD_PLAIN) pa_load8<PA_LD_PLAIN>(op, idx, c, v);
-    else if (op.mode == PA_LD_BNRELU) pa_load8<PA_LD_BNRELU>(op, idx, c, v);
-    else if (op.mode == PA_LD_LIN2) pa_load8<PA_LD_LIN2>(op, idx, c, v);
-    else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = 0.f;
-    }
-}
-
 // apply an epilogue to 8 channel values at element offset idx (channel c..c+7); s1/s2 accumulate the
 // per-channel reductions of the STATS / BWD modes
 __device__ __forceinline__ bf16x8 epilogue8(const PaEpilogue& ep, size_t idx, int c, const float (&v)[8],
@@ -354,13 +338,34 @@ __global__ void maxpool_fwd_kernel(PaOperand in, bf16* out, int B, int H, int W,
         for (int k = 0; k < 4; ++k) {
             size_t idx = (((size_t)b * H + 2 * yo + (k >> 1)) * W + 2 * xo + (k & 1)) * C + c;
             float v[8];
-            load8_rt(in, idx, c, v);
+            pa_read8(in, idx, c, v);
 #pragma unroll
             for (int j = 0; j < 8; ++j) m[j] = (k == 0) ? v[j] : fmaxf(m[j], v[j]);
         }
         bf16x8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (bf16)m[j];
+        *reinterpret_cast<bf16x8*>(out + p * C + c) = o;
+    }
+}
+
+// out = nearest_upsample_x2(low) + skip   (reference models/asn_stacked_hg.py:193-203)
+__global__ void upadd_fwd_kernel(PaOperand low, PaOperand skip, bf16* out, int B, int H, int W, int C) {
+    const int CG = C / 8, Hl = H / 2, Wl = W / 2;
+    const size_t total = (size_t)B * H * W * CG;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        int cg = (int)(t % CG);
+        size_t p = t / CG;
+        int x = (int)(p % W);
+        size_t q = p / W;
+        int y = (int)(q % H), b = (int)(q / H);
+        int c = cg * 8;
+        float a[8], s[8];
+        pa_read8(low, (((size_t)b * Hl + (y >> 1)) * Wl + (x >> 1)) * C + c, c, a);
+        pa_read8(skip, p * C + c, c, s);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (bf16)(a[j] + s[j]);
         *reinterpret_cast<bf16x8*>(out + p * C + c) = o;
     }
 }
@@ -438,49 +443,29 @@ __global__ __launch_bounds__(256) void pool_up_fwd_s_kernel(PaOperand a, PaOpera
     }
 }
 
-// returns false when the configuration is not covered (caller uses the generic kernel)
+// OP 0: max pool of `a`; OP 1: upsample(a) + b.  The streaming kernel where the plan and the operand modes admit it, else the generic one.
 template <int OP>
-static bool launch_pool_up_fwd_s(const PaOperand& a, const PaOperand& b, bf16* out, int B, int H, int W, int C, hipStream_t st) {
-    const bool old = pa_tuning().eltwise_old != 0;
-    const int threads = 256;
-    const size_t row_items = (size_t)(W / 2) * (C / 8);
+static int launch_pool_up_fwd(const PaOperand& a, const PaOperand& b, bf16* out, int B, int H, int W, int C, hipStream_t st) {
     const bool ma = a.mode == PA_LD_PLAIN || a.mode == PA_LD_BNRELU, mb = OP == 0 || b.mode == PA_LD_PLAIN || b.mode == PA_LD_BNRELU;
-    if (old || !ma || !mb || C % 8 || H % 2 || W % 2 || threads % (C / 8) != 0 || !(row_items % threads == 0 || threads % row_items == 0) ||
-        (size_t)B * H * W * C >= ((size_t)1 << 31)) return false;
     const int rows = B * (H / 2);
-    const size_t total = (size_t)rows * row_items;
-    int blocks = (int)((total + threads - 1) / threads);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
+    const size_t items = (size_t)rows * (W / 2) * (C / 8);
+    PaEltPlan p;
+    if (pa_elt_plan(p, PA_ELT_FWD, items, B, H, W, C, false, ma && mb)) return 1;
     const bool A = a.mode == PA_LD_BNRELU, Bm = OP == 1 && b.mode == PA_LD_BNRELU;
-    if (A && Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_BNRELU>), dim3(blocks), dim3(threads), 0, st, a, b, out, rows, W, C);
-    else if (A) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_PLAIN>), dim3(blocks), dim3(threads), 0, st, a, b, out, rows, W, C);
-    else if (Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_BNRELU>), dim3(blocks), dim3(threads), 0, st, a, b, out, rows, W, C);
-    else hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_PLAIN>), dim3(blocks), dim3(threads), 0, st, a, b, out, rows, W, C);
-    return true;
-}
-
-int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st) {
-    if (launch_pool_up_fwd_s<0>(in, in, out, B, H, W, C, st)) return (int)hipGetLastError();
-    size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(blocks), dim3(256), 0, st, in, out, B, H, W, C);
+    if (!p.streaming) {
+        // (the generic upsample-add walks the high-resolution pixels)
+        if (OP == 0) hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(p.blocks), dim3(p.threads), 0, st, a, out, B, H, W, C);
+        else hipLaunchKernelGGL(upadd_fwd_kernel, dim3(pa_grid_for((size_t)B * H * W * (C / 8), p.threads, 4096)), dim3(p.threads), 0, st, a, b, out, B, H, W, C);
+    }
+    else if (A && Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_BNRELU>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
+    else if (A) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_PLAIN>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
+    else if (Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_BNRELU>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
+    else hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_PLAIN>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
     return (int)hipGetLastError();
 }
 
-// Streaming kernels with one partial-statistics row per workgroup (<= 512 rows): big tensors get larger workgroups so that 512 of
-// them still keep enough loads in flight (256-thread ones, measured ALONE, left HBM half idle: 3.3 TB/s vs 6+ TB/s for a plain copy of the
-// same size).
-static inline void stream_launch_dims(size_t total, int& blocks, int& threads) {
-    // 512 threads for the big tensors (1024 until round 4: 6.465 vs 6.434 ms per step over three interleaved pairs -- a 1024-thread
-    // workgroup needs a whole CU's wave slots at once next to the other queues' kernels; 512 workgroups x 512 threads x 9 loads of 16 bytes are
-    // still 38 MB in flight)
-    threads = total >= (size_t)512 * 1024 ? 512 : 256;
-    blocks = (int)((total + threads - 1) / threads);
-    if (blocks > 512) blocks = 512;          // one partial-statistics row per workgroup
-    if (blocks < 1) blocks = 1;
+int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st) {
+    return launch_pool_up_fwd<0>(in, in, out, B, H, W, C, st);
 }
 
 // gradient of the max pool: routed to the first maximum in scan order (torch semantics), plus an
@@ -506,7 +491,7 @@ __global__ __launch_bounds__(1024) void maxpool_bwd_kernel(const bf16* dout, PaO
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             idx[k] = (((size_t)b * H + 2 * yo + (k >> 1)) * W + 2 * xo + (k & 1)) * C + c;
-            load8_rt(in, idx[k], c, v[k]);
+            pa_read8(in, idx[k], c, v[k]);
         }
         int arg[8];
 #pragma unroll
@@ -519,7 +504,7 @@ __global__ __launch_bounds__(1024) void maxpool_bwd_kernel(const bf16* dout, PaO
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float e[8], r[8];
-            load8_rt(add, idx[k], c, e);
+            pa_read8(add, idx[k], c, e);
 #pragma unroll
             for (int j = 0; j < 8; ++j) r[j] = (arg[j] == k ? (float)g[j] : 0.f) + e[j];
             *reinterpret_cast<bf16x8*>(din + idx[k]) = epilogue8(ep, idx[k], c, r, s1, s2);
@@ -609,87 +594,42 @@ __global__ __launch_bounds__(1024) void maxpool_bwd_s_kernel(const bf16* __restr
 
 template <int INMODE, bool HASADD>
 static void launch_maxpool_bwd_s(const bf16* dout, const PaOperand& in, const bf16* add, const PaEpilogue& ep, bf16* din, int rows, int W, int C,
-                                 int blocks, int threads, hipStream_t st) {
-    const size_t lds = (threads / 64) * 2 * C * sizeof(float) + C * sizeof(float4) + C * sizeof(float2);
+                                 const PaEltPlan& p, hipStream_t st) {
     if (ep.mode == PA_OUT_BWD)
-        hipLaunchKernelGGL((maxpool_bwd_s_kernel<INMODE, HASADD, PA_OUT_BWD>), dim3(blocks), dim3(threads), lds, st, dout, in, add, ep, din, rows, W, C);
+        hipLaunchKernelGGL((maxpool_bwd_s_kernel<INMODE, HASADD, PA_OUT_BWD>), dim3(p.blocks), dim3(p.threads), p.lds, st, dout, in, add, ep, din, rows, W, C);
     else
-        hipLaunchKernelGGL((maxpool_bwd_s_kernel<INMODE, HASADD, PA_OUT_PLAIN>), dim3(blocks), dim3(threads), lds, st, dout, in, add, ep, din, rows, W, C);
-}
-
-// the streaming variants need blockDim and the items of a map row (W/2 * C/8) to divide one another: pick 512 / 256 threads
-// where 1024 do not (96 x 96 maps of the 384 x 384 configuration: 1536 items per row)
-static inline void fit_threads_to_rows(int& threads, int W, int C) {
-    const size_t row_items = (size_t)(W / 2) * (C / 8);
-    auto fit = [&](int t) { return t % (C / 8) == 0 && (row_items % t == 0 || t % row_items == 0); };
-    if (fit(threads)) return;
-    // (384 / 192 / 128: the 24 x 24 and 12 x 12 maps of the 384 x 384 configuration -- 12 / 6 low-resolution pixels x 32 channel groups per row)
-    for (int t : {512, 256, 384, 192, 128}) if (fit(t)) { threads = t; return; }
+        hipLaunchKernelGGL((maxpool_bwd_s_kernel<INMODE, HASADD, PA_OUT_PLAIN>), dim3(p.blocks), dim3(p.threads), p.lds, st, dout, in, add, ep, din, rows, W, C);
 }
 
 int pa_launch_maxpool_bwd(const bf16* dout, const PaOperand& in, const PaOperand& add, const PaEpilogue& ep, bf16* din,
                           int B, int H, int W, int C, hipStream_t st, int* stat_rows) {
-    size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    int blocks, threads;
-    stream_launch_dims(total, blocks, threads);
-    fit_threads_to_rows(threads, W, C);
-    if (stat_rows) *stat_rows = blocks;
-    if (ep.rows_out) *ep.rows_out = blocks;
-    {
-        const bool old = pa_tuning().eltwise_old != 0;
-        const size_t row_items = (size_t)(W / 2) * (C / 8);
-        const bool in_ok = in.mode == PA_LD_PLAIN || in.mode == PA_LD_BNRELU;
-        const bool add_ok = add.mode == PA_LD_NONE || add.mode == PA_LD_PLAIN;
-        // BatchNorm-backward epilogue: only when it refers to the pooled tensor itself (its raw values are already in registers)
-        const bool ep_ok = ep.mode == PA_OUT_PLAIN || (ep.mode == PA_OUT_BWD && ep.xref == in.p);
-        if (!old && in_ok && add_ok && ep_ok && threads % (C / 8) == 0 && (row_items % threads == 0 || threads % row_items == 0) &&
-            (size_t)B * H * W * C < ((size_t)1 << 31)) {
-            const int rows = B * (H / 2);
-            const bool has_add = add.mode == PA_LD_PLAIN;
-            if (in.mode == PA_LD_BNRELU) {
-                if (has_add) launch_maxpool_bwd_s<PA_LD_BNRELU, true>(dout, in, add.p, ep, din, rows, W, C, blocks, threads, st);
-                else launch_maxpool_bwd_s<PA_LD_BNRELU, false>(dout, in, nullptr, ep, din, rows, W, C, blocks, threads, st);
-            } else {
-                if (has_add) launch_maxpool_bwd_s<PA_LD_PLAIN, true>(dout, in, add.p, ep, din, rows, W, C, blocks, threads, st);
-                else launch_maxpool_bwd_s<PA_LD_PLAIN, false>(dout, in, nullptr, ep, din, rows, W, C, blocks, threads, st);
-            }
-            return (int)hipGetLastError();
-        }
+    const bool in_ok = in.mode == PA_LD_PLAIN || in.mode == PA_LD_BNRELU;
+    const bool add_ok = add.mode == PA_LD_NONE || add.mode == PA_LD_PLAIN;
+    // BatchNorm-backward epilogue: only when it refers to the pooled tensor itself (its raw values are already in registers)
+    const bool ep_ok = ep.mode == PA_OUT_PLAIN || (ep.mode == PA_OUT_BWD && ep.xref == in.p);
+    PaEltPlan p;
+    if (pa_elt_plan(p, PA_ELT_POOL_BWD, (size_t)B * (H / 2) * (W / 2) * (C / 8), B, H, W, C, ep.mode != PA_OUT_PLAIN, in_ok && add_ok && ep_ok)) return 1;
+    if (stat_rows) *stat_rows = p.blocks;
+    if (ep.rows_out) *ep.rows_out = p.blocks;
+    if (!p.streaming) {
+        hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(p.blocks), dim3(p.threads), p.lds, st, dout, in, add, ep, din, B, H, W, C);
+        return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(blocks), dim3(threads), (threads / 64) * 2 * C * sizeof(float), st, dout, in, add, ep, din, B, H, W, C);
+    const int rows = B * (H / 2);
+    const bool has_add = add.mode == PA_LD_PLAIN;
+    if (in.mode == PA_LD_BNRELU) {
+        if (has_add) launch_maxpool_bwd_s<PA_LD_BNRELU, true>(dout, in, add.p, ep, din, rows, W, C, p, st);
+        else launch_maxpool_bwd_s<PA_LD_BNRELU, false>(dout, in, nullptr, ep, din, rows, W, C, p, st);
+    } else {
+        if (has_add) launch_maxpool_bwd_s<PA_LD_PLAIN, true>(dout, in, add.p, ep, din, rows, W, C, p, st);
+        else launch_maxpool_bwd_s<PA_LD_PLAIN, false>(dout, in, nullptr, ep, din, rows, W, C, p, st);
+    }
     return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
-// out = nearest_upsample_x2(low) + skip   (reference models/asn_stacked_hg.py:193-203)
-__global__ void upadd_fwd_kernel(PaOperand low, PaOperand skip, bf16* out, int B, int H, int W, int C) {
-    const int CG = C / 8, Hl = H / 2, Wl = W / 2;
-    const size_t total = (size_t)B * H * W * CG;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        int cg = (int)(t % CG);
-        size_t p = t / CG;
-        int x = (int)(p % W);
-        size_t q = p / W;
-        int y = (int)(q % H), b = (int)(q / H);
-        int c = cg * 8;
-        float a[8], s[8];
-        load8_rt(low, (((size_t)b * Hl + (y >> 1)) * Wl + (x >> 1)) * C + c, c, a);
-        load8_rt(skip, p * C + c, c, s);
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (bf16)(a[j] + s[j]);
-        *reinterpret_cast<bf16x8*>(out + p * C + c) = o;
-    }
-}
-
 int pa_launch_upadd_fwd(const PaOperand& low, const PaOperand& skip, bf16* out, int B, int H, int W, int C, hipStream_t st) {
-    if (launch_pool_up_fwd_s<1>(low, skip, out, B, H, W, C, st)) return (int)hipGetLastError();
-    size_t total = (size_t)B * H * W * (C / 8);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(upadd_fwd_kernel, dim3(blocks), dim3(256), 0, st, low, skip, out, B, H, W, C);
-    return (int)hipGetLastError();
+    return launch_pool_up_fwd<1>(low, skip, out, B, H, W, C, st);
 }
 
 // backward: dskip = epilogue_skip(dout), dlow = epilogue_low(sum of the 2x2 dout block)
@@ -798,42 +738,32 @@ __global__ __launch_bounds__(1024) void upadd_bwd_bb_kernel(const bf16* __restri
     if (SKIP) flush_stats(red, eps.stats, C, c, k1, k2);
 }
 
+// the one plan of an upsample-add backward: pa_upadd_bwd_splits and the launch read the same answer
+static int upadd_bwd_plan(PaEltPlan& p, const PaEpilogue& ep_low, const PaEpilogue& ep_skip, int B, int H, int W, int C) {
+    return pa_elt_plan(p, PA_ELT_UPADD_BWD, (size_t)B * (H / 2) * (W / 2) * (C / 8), B, H, W, C, ep_low.mode != PA_OUT_PLAIN || ep_skip.mode != PA_OUT_PLAIN,
+                       ep_low.mode == PA_OUT_BWD && ep_skip.mode == PA_OUT_BWD);
+}
+
 bool pa_upadd_bwd_splits(const PaEpilogue& ep_low, const PaEpilogue& ep_skip, int B, int H, int W, int C) {
-    size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    int blocks, threads;
-    stream_launch_dims(total, blocks, threads);
-    fit_threads_to_rows(threads, W, C);
-    const size_t row_items = (size_t)(W / 2) * (C / 8);
-    return !pa_tuning().eltwise_old && ep_low.mode == PA_OUT_BWD && ep_skip.mode == PA_OUT_BWD && threads % (C / 8) == 0 &&
-           (row_items % threads == 0 || threads % row_items == 0) && (size_t)B * H * W * C < ((size_t)1 << 31);
+    PaEltPlan p;
+    return upadd_bwd_plan(p, ep_low, ep_skip, B, H, W, C) == 0 && p.streaming;
 }
 
 int pa_launch_upadd_bwd(const bf16* dout, const PaEpilogue& ep_low, bf16* dlow, const PaEpilogue& ep_skip, bf16* dskip,
                         int B, int H, int W, int C, hipStream_t st, int* stat_rows, int part) {
-    size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    int blocks, threads;
-    stream_launch_dims(total, blocks, threads);
-    fit_threads_to_rows(threads, W, C);
-    if (stat_rows) *stat_rows = blocks;
-    if (ep_low.rows_out && (part & 1)) *ep_low.rows_out = blocks;
-    if (ep_skip.rows_out && (part & 2)) *ep_skip.rows_out = blocks;
-    if (part != 3) {           // one output only: the streaming kernel or nothing (callers ask pa_upadd_bwd_splits first)
-        if (!pa_upadd_bwd_splits(ep_low, ep_skip, B, H, W, C) || (part != 1 && part != 2)) { pa_set_error_msg("pa_launch_upadd_bwd: this launch cannot be split"); return 1; }
-        const size_t lds = (threads / 64) * 2 * C * sizeof(float) + 2 * C * sizeof(float4);
-        if (part == 1) hipLaunchKernelGGL((upadd_bwd_bb_kernel<true, false>), dim3(blocks), dim3(threads), lds, st, dout, ep_low, dlow, ep_skip, dskip, B * (H / 2), W, C);
-        else hipLaunchKernelGGL((upadd_bwd_bb_kernel<false, true>), dim3(blocks), dim3(threads), lds, st, dout, ep_low, dlow, ep_skip, dskip, B * (H / 2), W, C);
-        return (int)hipGetLastError();
-    }
-    const bool old = pa_tuning().eltwise_old != 0;
-    const size_t row_items = (size_t)(W / 2) * (C / 8);
-    if (!old && ep_low.mode == PA_OUT_BWD && ep_skip.mode == PA_OUT_BWD && threads % (C / 8) == 0 &&
-        (row_items % threads == 0 || threads % row_items == 0) && (size_t)B * H * W * C < ((size_t)1 << 31)) {
-        hipLaunchKernelGGL((upadd_bwd_bb_kernel<true, true>), dim3(blocks), dim3(threads), (threads / 64) * 2 * C * sizeof(float) + 2 * C * sizeof(float4), st,
-                           dout, ep_low, dlow, ep_skip, dskip, B * (H / 2), W, C);
-        return (int)hipGetLastError();
-    }
-    hipLaunchKernelGGL(upadd_bwd_kernel, dim3(blocks), dim3(threads), (threads / 64) * 2 * C * sizeof(float), st, dout, ep_low, dlow, ep_skip, dskip,
-                       B, H, W, C);
+    PaEltPlan p;
+    if (upadd_bwd_plan(p, ep_low, ep_skip, B, H, W, C)) return 1;
+    // one output only: the streaming kernel or nothing (callers ask pa_upadd_bwd_splits first)
+    if (part != 3 && (!p.streaming || (part != 1 && part != 2))) { pa_set_error_msg("pa_launch_upadd_bwd: this launch cannot be split"); return 1; }
+    if (stat_rows) *stat_rows = p.blocks;
+    if (ep_low.rows_out && (part & 1)) *ep_low.rows_out = p.blocks;
+    if (ep_skip.rows_out && (part & 2)) *ep_skip.rows_out = p.blocks;
+    const dim3 grid(p.blocks), block(p.threads);
+    const int rows = B * (H / 2);
+    if (!p.streaming) hipLaunchKernelGGL(upadd_bwd_kernel, grid, block, p.lds, st, dout, ep_low, dlow, ep_skip, dskip, B, H, W, C);
+    else if (part == 1) hipLaunchKernelGGL((upadd_bwd_bb_kernel<true, false>), grid, block, p.lds, st, dout, ep_low, dlow, ep_skip, dskip, rows, W, C);
+    else if (part == 2) hipLaunchKernelGGL((upadd_bwd_bb_kernel<false, true>), grid, block, p.lds, st, dout, ep_low, dlow, ep_skip, dskip, rows, W, C);
+    else hipLaunchKernelGGL((upadd_bwd_bb_kernel<true, true>), grid, block, p.lds, st, dout, ep_low, dlow, ep_skip, dskip, rows, W, C);
     return (int)hipGetLastError();
 }
 
@@ -841,6 +771,9 @@ int pa_launch_upadd_bwd(const bf16* dout, const PaEpilogue& ep_low, bf16* dlow, 
 // RMSprop exactly as torch.optim.RMSprop(alpha, eps, momentum=0, weight_decay=0, centered=False)
 // (reference stack-hg.py:51-52): v = alpha v + (1-alpha) g^2 ; p -= lr g / (sqrt(v) + eps).
 // gscale multiplies the gradient first (1/world_size after a sum all-reduce).
+// the update, once for the vector body and the tail of both kernels: v' = alpha v + (1 - alpha) g^2, then p' = p - lr g / (sqrt(v') + eps)
+__device__ __forceinline__ float rmsprop_v(float v, float gr, float alpha) { return alpha * v + (1.f - alpha) * gr * gr; }
+__device__ __forceinline__ float rmsprop_p(float p, float v, float gr, float lr, float eps) { return p - lr * (gr / (sqrtf(v) + eps)); }
 __global__ void rmsprop_kernel(float* p, const float* g, float* v, size_t n, float lr, float alpha, float eps, float gscale) {
     size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
@@ -848,17 +781,17 @@ __global__ void rmsprop_kernel(float* p, const float* g, float* v, size_t n, flo
         f32x4 gg = *reinterpret_cast<const f32x4*>(g + i), vv = *reinterpret_cast<f32x4*>(v + i), pp = *reinterpret_cast<f32x4*>(p + i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float gr = gg[j] * gscale;
-            vv[j] = alpha * vv[j] + (1.f - alpha) * gr * gr;
-            pp[j] = pp[j] - lr * (gr / (sqrtf(vv[j]) + eps));
+            const float gr = gg[j] * gscale;
+            vv[j] = rmsprop_v(vv[j], gr, alpha);
+            pp[j] = rmsprop_p(pp[j], vv[j], gr, lr, eps);
         }
         *reinterpret_cast<f32x4*>(v + i) = vv;
         *reinterpret_cast<f32x4*>(p + i) = pp;
     }
     for (; i < n && i + 3 >= n; ++i) {          // tail (at most 3 elements, one thread)
-        float gr = g[i] * gscale;
-        v[i] = alpha * v[i] + (1.f - alpha) * gr * gr;
-        p[i] = p[i] - lr * (gr / (sqrtf(v[i]) + eps));
+        const float gr = g[i] * gscale;
+        v[i] = rmsprop_v(v[i], gr, alpha);
+        p[i] = rmsprop_p(p[i], v[i], gr, lr, eps);
     }
 }
 
@@ -896,25 +829,23 @@ __global__ void rmsprop_checked_kernel(float* p, const float* g, float* v, size_
         f32x4 gg = *reinterpret_cast<const f32x4*>(g + i), vv = *reinterpret_cast<f32x4*>(v + i), pp = *reinterpret_cast<f32x4*>(p + i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float gr = gg[j] * gscale;
-            vv[j] = alpha * vv[j] + (1.f - alpha) * gr * gr;
-            pp[j] = pp[j] - lr * (gr / (sqrtf(vv[j]) + eps));
+            const float gr = gg[j] * gscale;
+            vv[j] = rmsprop_v(vv[j], gr, alpha);
+            pp[j] = rmsprop_p(pp[j], vv[j], gr, lr, eps);
         }
         *reinterpret_cast<f32x4*>(v + i) = vv;
         *reinterpret_cast<f32x4*>(p + i) = pp;
     }
     for (; i < n && i + 3 >= n; ++i) {
-        float gr = g[i] * gscale;
-        v[i] = alpha * v[i] + (1.f - alpha) * gr * gr;
-        p[i] = p[i] - lr * (gr / (sqrtf(v[i]) + eps));
+        const float gr = g[i] * gscale;
+        v[i] = rmsprop_v(v[i], gr, alpha);
+        p[i] = rmsprop_p(p[i], v[i], gr, lr, eps);
     }
 }
 
 int pa_launch_rmsprop(float* p, const float* g, float* v, size_t n, float lr, float alpha, float eps, float gscale, int* state, hipStream_t st) {
     if (n == 0) return 0;
-    int blocks = (int)((n / 4 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
+    const int blocks = pa_grid_for(n / 4, 256, 2048);
 #ifdef PA_FP16
     hipLaunchKernelGGL(grad_check_reset_kernel, dim3(1), dim3(1), 0, st, state);
     hipLaunchKernelGGL(grad_check_kernel, dim3(blocks), dim3(256), 0, st, g, n, state);
@@ -962,15 +893,9 @@ int pa_launch_copy16(void* dst, const void* src, size_t bytes, hipStream_t st, i
         hipLaunchKernelGGL(copy16_flat_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16);
         return (int)hipGetLastError();
     }
-    if (form == 2) {
-        size_t nb = (n16 + 1023) / 1024;
-        if (nb > 256 * 16) nb = 256 * 16;
-        hipLaunchKernelGGL(copy16_nt_kernel, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16);
-        return (int)hipGetLastError();
-    }
-    size_t blocks = (n16 + 1023) / 1024;                 // 4 chunks per thread
-    if (blocks > 256 * 16) blocks = 256 * 16;            // 16 workgroups per CU, grid-stride beyond
-    hipLaunchKernelGGL(copy16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16);
+    const int blocks = pa_grid_for(n16, 1024, 256 * 16);        // 4 chunks per thread; 16 workgroups per CU, grid-stride beyond
+    if (form == 2) hipLaunchKernelGGL(copy16_nt_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16);
+    else hipLaunchKernelGGL(copy16_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16);
     return (int)hipGetLastError();
 }
 
@@ -1054,8 +979,7 @@ __global__ void nchw_to_nhwc4_kernel(const float* src, bf16* dst, int B, int H, 
 
 int pa_launch_nchw_to_nhwc4(const float* src, bf16* dst, int B, int H, int W, hipStream_t st) {
     size_t total = (size_t)B * H * W;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
+    const int blocks = pa_grid_for(total, 256, 4096);
     hipLaunchKernelGGL(nchw_to_nhwc4_kernel, dim3(blocks), dim3(256), 0, st, src, dst, B, H, W);
     return (int)hipGetLastError();
 }
@@ -1072,8 +996,7 @@ __global__ void nhwc_to_nchw_f32_kernel(const float* src, float* dst, int B, int
 
 int pa_launch_nhwc_to_nchw_f32(const float* src, float* dst, int B, int H, int W, int C, hipStream_t st) {
     size_t total = (size_t)B * H * W * C;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
+    const int blocks = pa_grid_for(total, 256, 4096);
     hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3(blocks), dim3(256), 0, st, src, dst, B, H, W, C);
     return (int)hipGetLastError();
 }
@@ -1090,8 +1013,7 @@ __global__ void nchw_f32_to_nhwc_bf16_kernel(const float* src, bf16* dst, int B,
 
 int pa_launch_nchw_f32_to_nhwc_bf16(const float* src, bf16* dst, int B, int C, int H, int W, hipStream_t st) {
     size_t total = (size_t)B * H * W * C;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
+    const int blocks = pa_grid_for(total, 256, 4096);
     hipLaunchKernelGGL(nchw_f32_to_nhwc_bf16_kernel, dim3(blocks), dim3(256), 0, st, src, dst, B, C, H, W);
     return (int)hipGetLastError();
 }
@@ -1111,8 +1033,7 @@ __global__ void nhwc_bf16_to_nchw_f32_kernel(PaOperand src, float* dst, int B, i
 
 int pa_launch_nhwc_bf16_to_nchw_f32(const PaOperand& src, float* dst, int B, int C, int H, int W, hipStream_t st) {
     size_t total = (size_t)B * H * W * C;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
+    const int blocks = pa_grid_for(total, 256, 4096);
     hipLaunchKernelGGL(nhwc_bf16_to_nchw_f32_kernel, dim3(blocks), dim3(256), 0, st, src, dst, B, C, H, W);
     return (int)hipGetLastError();
 }
@@ -1131,19 +1052,18 @@ __global__ __launch_bounds__(1024) void ep_apply_kernel(PaOperand g, PaEpilogue 
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         const size_t idx = (t / CG) * C + c;
         float v[8];
-        load8_rt(g, idx, c, v);
+        pa_read8(g, idx, c, v);
         *reinterpret_cast<bf16x8*>(out + idx) = epilogue8(ep, idx, c, v, s1, s2);
     }
     if (ep.mode != PA_OUT_PLAIN) flush_stats(red, ep.stats, C, c, s1, s2);
 }
 
 int pa_launch_ep_apply(const PaOperand& g, const PaEpilogue& ep, bf16* out, size_t M, int C, hipStream_t st, int* stat_rows) {
-    size_t total = M * (C / 8);
-    int blocks, threads;
-    stream_launch_dims(total, blocks, threads);
-    if (stat_rows) *stat_rows = blocks;
-    if (ep.rows_out) *ep.rows_out = blocks;
-    hipLaunchKernelGGL(ep_apply_kernel, dim3(blocks), dim3(threads), (threads / 64) * 2 * C * sizeof(float), st, g, ep, out, M, C);
+    PaEltPlan p;
+    if (pa_elt_plan(p, PA_ELT_APPLY, M * (C / 8), 0, 0, 0, C, ep.mode != PA_OUT_PLAIN, false)) return 1;
+    if (stat_rows) *stat_rows = p.blocks;
+    if (ep.rows_out) *ep.rows_out = p.blocks;
+    hipLaunchKernelGGL(ep_apply_kernel, dim3(p.blocks), dim3(p.threads), p.lds, st, g, ep, out, M, C);
     return (int)hipGetLastError();
 }
 
@@ -1168,7 +1088,7 @@ __global__ __launch_bounds__(1024) void cell_mask_kernel(PaOperand x, const floa
         const int y = (int)(q % H), b = (int)(q / H);
         const float m = mask[(size_t)b * 16 + 4 * (y / ch) + xw / cw];
         float v[8];
-        load8_rt(x, idx, c, v);
+        pa_read8(x, idx, c, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] *= m;
         *reinterpret_cast<bf16x8*>(out + idx) = epilogue8(ep, idx, c, v, s1, s2);
@@ -1179,26 +1099,10 @@ __global__ __launch_bounds__(1024) void cell_mask_kernel(PaOperand x, const floa
 int pa_launch_cell_mask(const PaOperand& x, const float* mask, const PaEpilogue& ep, bf16* out, int B, int H, int W, int C,
                         hipStream_t st) {
     if (H % 4 != 0 || W % 4 != 0 || C % 8 != 0) { pa_set_error_msg("pa_launch_cell_mask: the map must be a multiple of the 4x4 cell grid"); return 1; }
-    const int CG = C / 8;
-    // flush_stats reduces the lanes of a wave that share a channel group by xor shuffles: a power of two, at most one wave wide
-    if (ep.mode != PA_OUT_PLAIN && (CG > 64 || (CG & (CG - 1)) != 0)) {
-        pa_set_error_msg("pa_launch_cell_mask: a statistics epilogue needs C / 8 a power of two <= 64"); return 1;
-    }
-    if (CG > 1024) { pa_set_error_msg("pa_launch_cell_mask: C / 8 exceeds the workgroup size"); return 1; }
-    size_t total = (size_t)B * H * W * CG;
-    int blocks, threads;
-    stream_launch_dims(total, blocks, threads);
-    // a thread keeps the channel group threadIdx.x % CG over its whole grid-stride walk: the workgroup size (and with it the stride)
-    // must be a multiple of CG.  256 / 512 are for every power of two; otherwise the largest multiple below (C = 24: 255, 384: 240)
-    if (threads % CG != 0) {
-        threads = CG > threads ? CG : threads / CG * CG;
-        blocks = (int)((total + threads - 1) / threads);
-        if (blocks > 512) blocks = 512;
-    }
-    if (ep.rows_out) *ep.rows_out = blocks;
-    // flush_stats' LDS: one row of 2 * C floats per wave (a plain epilogue never reaches it)
-    const size_t lds = ep.mode != PA_OUT_PLAIN ? (size_t)((threads + 63) / 64) * 2 * C * sizeof(float) : 0;
-    hipLaunchKernelGGL(cell_mask_kernel, dim3(blocks), dim3(threads), lds, st, x, mask, ep, out, B, H, W, C);
+    PaEltPlan p;
+    if (pa_elt_plan(p, PA_ELT_MASK, (size_t)B * H * W * (C / 8), B, H, W, C, ep.mode != PA_OUT_PLAIN, false)) return 1;
+    if (ep.rows_out) *ep.rows_out = p.blocks;
+    hipLaunchKernelGGL(cell_mask_kernel, dim3(p.blocks), dim3(p.threads), p.lds, st, x, mask, ep, out, B, H, W, C);
     return (int)hipGetLastError();
 }
 
@@ -1224,9 +1128,7 @@ __global__ void fill_kernel(float* p, float v, size_t n) {
 }
 
 int pa_launch_fill(float* p, float v, size_t n, hipStream_t st) {
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
+    const int blocks = pa_grid_for(n, 256, 1024);
     hipLaunchKernelGGL(fill_kernel, dim3(blocks), dim3(256), 0, st, p, v, n);
     return (int)hipGetLastError();
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "bn_fin.h"
+#include "launch_plan.h"
 
 struct PaConvArgs {
     PaOperand in;        // [B][H][W][Cin] NHWC bf16
@@ -98,7 +99,8 @@ int pa_launch_bn_bwd_finalize(const float* bstats, int rows, const float* scale,
                               float* kA, float* kB, float* kC, float* dgamma, float* dbeta, int C, float count,
                               hipStream_t st);
 
-// ---- pooling / upsampling (NHWC bf16)
+// ---- pooling / upsampling (NHWC bf16).  These launches, pa_launch_ep_apply and pa_launch_cell_mask take their geometry from pa_elt_plan
+// (launch_plan.h), which also refuses what the kernels cannot do: a statistics epilogue needs C / 8 a power of two <= 64
 int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st);
 // grad of 2x2 max pool routed to the arg-max (first max in scan order), + optional addend, then epilogue
 int pa_launch_maxpool_bwd(const bf16* dout, const PaOperand& in, const PaOperand& add, const PaEpilogue& ep, bf16* din,

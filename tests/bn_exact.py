@@ -45,7 +45,7 @@ in the engine's own units (the fp16 build carries pa_grad_scale() in every gradi
 Pool forward, merge forward and merge backward involve no accumulation: one fp32 max / add / 2 x 2 sum in a fixed order, rounded once to
 the storage type (round to nearest even, the conversion of gfx950 and of torch), so they are compared bit for bit.
 
-Pool backward (maxpool_bwd_kernel elementwise.hip:511-525, the streaming maxpool_bwd_s_kernel :582-602, both `if (v[k] > m)` over
+Pool backward (maxpool_bwd_kernel and the streaming maxpool_bwd_s_kernel of elementwise.hip, both `if (v[k] > m)` over
 k = 0..3 = top-left, top-right, bottom-left, bottom-right: the FIRST maximum in scan order keeps the gradient) is bit-exact too: the
 value compared is the fp32 BatchNorm+ReLU value view 0 (the kernels' own fmaxf(fmaf(k0, raw, k1), 0)), the routed gradient takes at
 most one fp32 add (the addend: d xin<i+1> into poolgrad1 of an inner stack, Hourglass::bwd net.hip:807) and one rounding; with a

@@ -543,7 +543,7 @@ def run_leg(stacks, chan, B, res, seed, log=print, expect=(), history='fresh', m
             fails.append(('heat gradient', 'heat%d padded channels' % i, float('inf')))
         ls, r = loss_check(S.losses[i], outs[i], target)
         note('loss', 'stack %d' % i, (r, 0.0))
-        loss_sum = ls if loss_sum is None else loss_sum + ls                # loss_out_kernel (elementwise.hip:1193-1199): s += v, from 0
+        loss_sum = ls if loss_sum is None else loss_sum + ls                # loss_out_kernel (elementwise.hip): s += v, from 0
         del dh64, inner_add
         if i + 1 < stacks:
             fc, ic = 'forth_conv.%d' % i, 'in_conv.%d' % i

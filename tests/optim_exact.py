@@ -1,4 +1,4 @@
-"""Exact check of the fused RMSprop step (rmsprop_kernel / rmsprop_checked_kernel, csrc/elementwise.hip; pa_rmsprop_step and
+"""Exact check of the fused RMSprop step (rmsprop_kernel / rmsprop_checked_kernel and the rmsprop_v / rmsprop_p both share, csrc/elementwise.hip; pa_rmsprop_step and
 pa_rmsprop_step_state): every element of p AND of square_avg after a step, against a float64 evaluation of
 
     v' = alpha32 v + c32 (g s)^2,      p' = p - lr32 (g s) / (sqrt(v') + eps32)

@@ -362,6 +362,42 @@ def test_residual_op_stays_inside_its_workspace(C_, H, B):
     assert bool(torch.isfinite(dxd).all()) and bool(torch.isfinite(gd).all())
 
 
+CHAN_RULE = 'must be a power of two <= 64'
+
+
+def test_nets_refuse_a_channel_count_the_statistics_kernels_cannot_reduce():
+    """chan 384 is a multiple of 128 but chan / 8 = 48 is no power of two: the streaming kernels reduce the lanes of a wave that
+    share a channel group by xor shuffles, and 16 of every 64 lanes' partial sums would be dropped from the BatchNorm-backward
+    reductions.  Creation refuses it, for the pose net, the agent and the occlusion agent, and says why; 128, 256 and 512 are taken."""
+    from pose_adv_aug_amd._lib import lib
+    L = lib()
+    for create in (lambda c: L.pa_hg_create(2, 16, c, 2, 256), lambda c: L.pa_asn_create(c, 7, 7, 2, 256),
+                   lambda c: L.pa_asn_create_dropout(c, 2, 256)):
+        assert not create(384)
+        assert CHAN_RULE in L.pa_last_error().decode(), L.pa_last_error()
+        for chan in (128, 256, 512):
+            h = create(chan)
+            assert h, (chan, L.pa_last_error())
+            L.pa_net_destroy(h)
+
+
+def test_residual_op_refuses_a_channel_count_the_statistics_kernels_cannot_reduce():
+    """pa_residual_fwd_bwd at C = 384 returns the error before any launch (its output buffers stay as they were)."""
+    from pose_adv_aug_amd._lib import lib, ptr, stream
+    L = lib()
+    C_, H, B = 384, 8, 1
+    blk = om.Residual(C_, C_); om.deterministic_fill_(blk, seed=3)
+    params = torch.cat([p.detach().flatten() for p in blk.parameters()]).cuda()
+    bufs = torch.cat([b.flatten().float() for n, b in blk.named_buffers() if 'num_batches' not in n]).cuda()
+    ws = torch.zeros(L.pa_residual_workspace_bytes(B, H, H, C_), dtype=torch.uint8, device='cuda')
+    x = torch.rand(B, C_, H, H, device='cuda'); dy = torch.randn(B, C_, H, H, device='cuda')
+    yd = torch.full_like(x, 7.0); dxd = torch.full_like(x, 7.0); gd = torch.zeros_like(params)
+    rc = L.pa_residual_fwd_bwd(ptr(x), ptr(dy), ptr(params), ptr(yd), ptr(dxd), ptr(gd), ptr(bufs), B, C_, H, H, ptr(ws), stream())
+    torch.cuda.synchronize()
+    assert rc != 0 and CHAN_RULE in L.pa_last_error().decode(), (rc, L.pa_last_error())
+    assert bool((yd == 7.0).all()) and bool((dxd == 7.0).all()) and float(gd.abs().max()) == 0.0
+
+
 def test_network_step_stays_inside_its_workspace():
     """pa_net_workspace_bytes vs what pa_hg_forward / pa_hg_backward and the agent touch: 64 MB guard regions around the
     workspaces of a 2-stack pose net (chan 128, 256x256, B = 2) and of its agent stay untouched."""

@@ -1,4 +1,4 @@
-"""The bound of tests/optim_exact.py is not vacuous: a numpy fp32 emulation of the RMSprop kernel (csrc/elementwise.hip rmsprop_kernel:
+"""The bound of tests/optim_exact.py is not vacuous: a numpy fp32 emulation of the RMSprop kernel (csrc/elementwise.hip rmsprop_kernel, through rmsprop_v / rmsprop_p:
 gr = g * gscale; v = alpha * v + (1.f - alpha) * gr * gr; p = p - lr * (gr / (sqrtf(v) + eps)), each operation rounded on its own, and the
 same with the update of v contracted into one fma) stays inside it for p and for square_avg over 200 003 elements at every gscale of the
 GPU cases, and each of these defects is reported at every gscale at which it is one:
