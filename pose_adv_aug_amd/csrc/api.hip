@@ -223,6 +223,8 @@ struct ConvOp {
     }
 };
 
+// An upper bound: laid out without the net's batch, the layer gets the slab count of a launch alone (PaWgradPlan::splits); pa_conv2d lays it
+// out with the batch and may get the grouped count, which is never larger (tests/test_conv_exact_cpu.py sweeps the rule).
 size_t pa_conv2d_workspace_bytes(int B, int Cin, int Cout, int H, int W, int k) {
     ConvOp op; op.n.is_agent = true; op.n.declare_conv(op.c, "c", Cin, Cout, k, false);
     return op.build(B, H, W, nullptr);
@@ -343,7 +345,7 @@ int pa_wgrad_group(const pa_wgrad_job* jobs, int njobs, int mode, void* ws, void
         for (int j = 0; j < njobs; ++j) TRY(pa_launch_wgrad(args[j], n.st));
     } else {
         for (int j = 0; j < njobs; ++j)
-            if (!pa_wgrad_group_takes(args[j])) { pa_set_error_msg("pa_wgrad_group: a job the grouped kernel does not take (shape / operand modes)"); return 2; }
+            if (pa_wgrad_job_workgroups(args[j]) == 0) { pa_set_error_msg("pa_wgrad_group: a job the grouped kernel does not take (shape / operand modes)"); return 2; }
         TRY(pa_launch_wgrad_group(ptrs, njobs, n.st, mode == 2));
     }
     TRY(pa_launch_wgrad_reduce(n.red_jobs, n.n_red, n.red_max, n.st));

@@ -224,37 +224,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(PaWgradArgs a) {
     }
 }
 
-static int round_up8(int v) { return (v + 7) & ~7; }
-
-static void tile_of(int Cin, int Cout, int taps, int& TN, int& TK) {
-    TN = (Cout % 128 == 0) ? 128 : 64;
-    TK = (Cin % 128 == 0) ? 128 : 64;
-    const int f = taps == 1 ? pa_tuning().wgrad_tile1 : pa_tuning().wgrad_tile9;       // experiments: 1 = 64x64, 2 = 128x64, 3 = 64x128
-    if (f == 1) { TN = 64; TK = 64; }
-    if (f == 2) { TK = 64; }
-    if (f == 3) { TN = 64; }
-}
-
-int pa_wgrad_splits(int M, int H, int W, int Cin, int Cout, int taps) {
-    if (H > 0 && W > 0 && M % (H * W) == 0) {
-        const int ts = pa_wgrad_tile_splits(M / (H * W), H, W, Cin, Cout, taps);
-        if (ts > 0) return ts;
-    }
-    int TN, TK;
-    tile_of(Cin, Cout, taps, TN, TK);
-    const int tiles = (Cout / TN) * (taps * Cin / TK);
-    const int ms = (TN + TK <= 128) ? 128 : 64;
-    const int steps_total = (M + ms - 1) / ms;
-    // enough workgroups to keep every CU busy with several of them (measured on MI355X: 512 for the
-    // 1x1 layers, 1024 for the 3x3 layers; PA_WGRAD_BLOCKS overrides for experiments)
-    const int forced = pa_tuning().wgrad_blocks;
-    const int target = forced >= 8 ? forced : (taps == 9 ? 1024 : 512);
-    int s = round_up8((target + tiles - 1) / tiles);
-    if (s > steps_total) s = steps_total;
-    if (s < 1) s = 1;
-    return s;
-}
-
 template <int TN, int TK, int PMODE, int QMODE>
 static void launch_w_taps(const PaWgradArgs& a, dim3 grid, hipStream_t st) {
     if (a.taps == 1) hipLaunchKernelGGL((conv_wgrad_kernel<TN, TK, PMODE, QMODE, 1>), grid, dim3(256), 0, st, a);
@@ -270,14 +239,16 @@ static void launch_w_modes(const PaWgradArgs& a, dim3 grid, hipStream_t st) {
     else launch_w_taps<TN, TK, PA_LD_PLAIN, PA_LD_PLAIN>(a, grid, st);
 }
 
+// every launch takes its kernel and grid from pa_wgrad_launch_plan (wgrad_plan.h)
 int pa_launch_stem_wgrad(const PaWgradArgs& a, hipStream_t st) {
     // a.x.p = img4, a.Cin = 256 (virtual patch length), a.Cout = 64, a.H/a.W output dims
     if (a.Cin != 256 || a.Cout != 64 || a.taps != 1 || a.x.mode != PA_LD_PLAIN || a.splits < 1) {
         pa_set_error_msg("pa_launch_stem_wgrad: bad arguments");
         return 1;
     }
-    { const int rc = pa_launch_stem_wgrad_tile(a, st); if (rc >= 0) return rc; }
-    dim3 grid(a.splits, 2, 1);
+    const PaWgradPlan p = pa_wgrad_launch_plan(a.B, a.H, a.W, a.Cin, a.Cout, a.taps, true, a.splits, false);
+    if (p.path == PA_WGP_STEM_TILE) return pa_launch_stem_wgrad_tile(a, p, st);
+    dim3 grid(a.splits, p.blocks, 1);
     if (a.dy.mode == PA_LD_LIN2)
         hipLaunchKernelGGL((conv_wgrad_kernel<64, 128, PA_LD_LIN2, PA_LD_PLAIN, 1, true>), grid, dim3(256), 0, st, a);
     else
@@ -290,14 +261,12 @@ int pa_launch_wgrad(const PaWgradArgs& a, hipStream_t st) {
         pa_set_error_msg("pa_launch_wgrad: channel counts must be multiples of 64, taps 1 or 9, splits >= 1");
         return 1;
     }
-    const int rc = pa_launch_wgrad_tile(a, st);
-    if (rc >= 0) return rc;
-    int TN, TK;
-    tile_of(a.Cin, a.Cout, a.taps, TN, TK);
-    dim3 grid(a.splits, a.taps * a.Cin / TK, a.Cout / TN);
-    if (TN == 128 && TK == 128) launch_w_modes<128, 128>(a, grid, st);
-    else if (TN == 128) launch_w_modes<128, 64>(a, grid, st);
-    else if (TK == 128) launch_w_modes<64, 128>(a, grid, st);
+    const PaWgradPlan p = pa_wgrad_launch_plan(a.B, a.H, a.W, a.Cin, a.Cout, a.taps, false, a.splits, a.dbpart != nullptr);
+    if (p.path == PA_WGP_TILE) return pa_launch_wgrad_tile(a, p, st);
+    dim3 grid(a.splits, a.taps * a.Cin / p.cb, a.Cout / p.nb);
+    if (p.nb == 128 && p.cb == 128) launch_w_modes<128, 128>(a, grid, st);
+    else if (p.nb == 128) launch_w_modes<128, 64>(a, grid, st);
+    else if (p.cb == 128) launch_w_modes<64, 128>(a, grid, st);
     else launch_w_modes<64, 64>(a, grid, st);
     return (int)hipGetLastError();
 }

@@ -491,7 +491,6 @@ __global__ __launch_bounds__(256, PIPE ? OCC : 2) void wgrad_tile_kernel(PaWgrad
 // Plain (two workgroups per CU, <= 244 registers) rather than pipelined bodies: 6.27 vs 6.31 ms per step -- a pipelined workgroup owns its
 // CU's registers, and the main chain's kernels then find no room beside the group.
 #define PA_WG_MAXJOBS 8
-enum { PA_WGK_9_44 = 0, PA_WGK_9_44L, PA_WGK_1_44, PA_WGK_1_42, PA_WGK_1_24, PA_WGK_1_22, PA_WGK_N };      // 3x3 64 x 64 (n x c) with a plain / BatchNorm-backward dy operand (fixed modes: the 144-accumulator body has no registers to spare for both) | 1x1 128 x 128 | 128 x 64 | 64 x 128 | 64 x 64
 struct PaWgradGroup {
     PaWgradArgs a[PA_WG_MAXJOBS];
     int ntiles[PA_WG_MAXJOBS], S[PA_WG_MAXJOBS], ny[PA_WG_MAXJOBS], kind[PA_WG_MAXJOBS];
@@ -532,35 +531,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_group_kernel(PaWgradGroup g) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct WgTileCfg { int nb, cb, ntiles, splits; };
-
-static bool wg_tile_cfg(int B, int H, int W, int Cin, int Cout, int taps, WgTileCfg& c) {
-    const PaTuning& t = pa_tuning();
-    if (t.wgrad_old || H <= 0 || W <= 0) return false;
-    const int M = B * H * W;
-    if (taps == 9) {
-        if (Cin % 64 || Cout % 64 || H % 8 || W % 16) return false;
-        c.nb = 64; c.cb = 64; c.ntiles = B * (H / 8) * (W / 16);
-        if (c.ntiles < 48) return false;
-    } else if (taps == 1) {
-        if (Cin % 64 || Cout % 64) return false;
-        c.nb = Cout % 128 == 0 ? 128 : 64; c.cb = Cin % 128 == 0 ? 128 : 64; c.ntiles = (M + 127) / 128;
-        if (c.ntiles < t.wgrad_min1) return false;      // (3: also the 16x16 ... 4x4 levels: 6.90 vs 6.97 ms (96))
-    } else return false;
-    const int types = (Cout / c.nb) * (Cin / c.cb);
-    int s = (taps == 9 ? t.wgrad_wgs9 : t.wgrad_wgs1) / types;
-    if (s < 1) s = 1;
-    if (s > c.ntiles) s = c.ntiles;
-    const int per = (c.ntiles + s - 1) / s;          // tiles per workgroup
-    c.splits = (c.ntiles + per - 1) / per;           // balanced
-    return true;
-}
-
-int pa_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout, int taps) {
-    WgTileCfg c;
-    return wg_tile_cfg(B, H, W, Cin, Cout, taps, c) ? c.splits : 0;
-}
-
 // Launch flags of the tile weight gradients (hip_ext.h): Net::flush_wgrads sets hipExtAnyOrderLaunch for the 2nd, 3rd ... launch of a
 // group of INDEPENDENT weight gradients behind one event.  Measured on gfx950 / ROCm 7.2 (tools/ubench/anyorder.hip): the flag never
 // overlaps two kernels of a stream, but the next one starts the moment the previous one's last wave ends instead of 3.6 us later (256
@@ -591,102 +561,67 @@ static void launch_wt_modes(const PaWgradArgs& a, dim3 grid, int ntiles, hipStre
     else launch_wt_modes2<TAPS, NF, CF, WNW, false>(a, grid, ntiles, st);
 }
 
-// 7x7/2 stem weight gradient on the tile kernel: NB = 64 output channels x CB = 256 patch elements per workgroup, dy read once
-int pa_launch_stem_wgrad_tile(const PaWgradArgs& a, hipStream_t st) {
-    const bool off = pa_tuning().wgrad_old || pa_tuning().stem_wgrad_old;
-    const int M = a.B * a.H * a.W, ntiles = (M + 127) / 128;
-    if (off || a.Cin != 256 || a.Cout != 64 || a.splits > ntiles) return -1;
+// 7x7/2 stem weight gradient on the tile kernel (p.path == PA_WGP_STEM_TILE): NB = 64 output channels x CB = 256 patch elements per
+// workgroup, dy read once
+int pa_launch_stem_wgrad_tile(const PaWgradArgs& a, const PaWgradPlan& p, hipStream_t st) {
     dim3 grid(a.splits, 1, 1);
     // the plain form at two workgroups per CU: a pipelined one needs the CU to itself (297 registers) -- with the stem's 512 splits that is
     // two rounds of workgroups, 95 us against 45 us (measured in the step, where this launch is the tail everything waits for)
-    if (a.dy.mode == PA_LD_LIN2) hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_LIN2, PA_WG_STEM, false>), grid, dim3(256), 0, st, a, ntiles);
-    else hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_PLAIN, PA_WG_STEM, false>), grid, dim3(256), 0, st, a, ntiles);
+    if (a.dy.mode == PA_LD_LIN2) hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_LIN2, PA_WG_STEM, false>), grid, dim3(256), 0, st, a, p.ntiles);
+    else hipLaunchKernelGGL((wgrad_tile_kernel<1, 2, 8, 2, PA_LD_PLAIN, PA_WG_STEM, false>), grid, dim3(256), 0, st, a, p.ntiles);
     return (int)hipGetLastError();
 }
 
-// returns -1 when the shape is not handled here (caller falls back to conv_wgrad.hip)
-int pa_launch_wgrad_tile(const PaWgradArgs& a, hipStream_t st) {
-    WgTileCfg c;
-    if (!wg_tile_cfg(a.B, a.H, a.W, a.Cin, a.Cout, a.taps, c) || a.splits < 1 || a.splits > c.ntiles) return -1;
-    if (a.taps == 9 && a.dbpart) return -1;
-    c.splits = a.splits;                 // (the layer's slab was laid out for this count: wg_tile_cfg's own, or the grouped policy's)
-    dim3 grid(c.splits, a.Cout / c.nb, a.Cin / c.cb);
-    if (a.taps == 9) launch_wt_modes<9, 4, 1, 1>(a, grid, c.ntiles, st);
-    else if (c.nb == 128 && c.cb == 128) launch_wt_modes<1, 4, 4, 2>(a, grid, c.ntiles, st);
-    else if (c.nb == 128) launch_wt_modes<1, 4, 2, 2>(a, grid, c.ntiles, st);
-    else if (c.cb == 128) launch_wt_modes<1, 2, 4, 2>(a, grid, c.ntiles, st);
-    else launch_wt_modes<1, 2, 2, 2>(a, grid, c.ntiles, st);
+// p.path == PA_WGP_TILE; a.splits is the count the layer's slab was laid out for: the plan's own, or the grouped policy's
+int pa_launch_wgrad_tile(const PaWgradArgs& a, const PaWgradPlan& p, hipStream_t st) {
+    dim3 grid(a.splits, a.Cout / p.nb, a.Cin / p.cb);
+    if (a.taps == 9) launch_wt_modes<9, 4, 1, 1>(a, grid, p.ntiles, st);
+    else if (p.nb == 128 && p.cb == 128) launch_wt_modes<1, 4, 4, 2>(a, grid, p.ntiles, st);
+    else if (p.nb == 128) launch_wt_modes<1, 4, 2, 2>(a, grid, p.ntiles, st);
+    else if (p.cb == 128) launch_wt_modes<1, 2, 4, 2>(a, grid, p.ntiles, st);
+    else launch_wt_modes<1, 2, 2, 2>(a, grid, p.ntiles, st);
     return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------ grouped launch
-static int wg_group_on() { return pa_tuning().wg_group; }
-
-static int wg_kind(const WgTileCfg& c, int taps, int pmode = PA_LD_PLAIN) {
-    if (taps == 9) return (c.nb == 64 && c.cb == 64) ? (pmode == PA_LD_LIN2 ? PA_WGK_9_44L : PA_WGK_9_44) : -1;
-    if (c.nb == 128 && c.cb == 128) return PA_WGK_1_44;
-    if (c.nb == 128 && c.cb == 64) return PA_WGK_1_42;
-    if (c.nb == 64 && c.cb == 128) return PA_WGK_1_24;
-    if (c.nb == 64 && c.cb == 64) return PA_WGK_1_22;
-    return -1;
-}
-
-// split count of a layer whose weight gradient is launched in a group (0: the shape is not one the grouped kernel takes -- the layer
-// keeps pa_wgrad_splits' count and its own launch): a WORKGROUP budget per job (64 each: three jobs of a residual block stay below the
-// 256-workgroup cap of a group launch, Net::flush_wgrads -- 5.91 vs 5.98 ms for 96 / 128 without a cap), at least minper tiles per workgroup
-int pa_wgrad_group_splits(int B, int H, int W, int Cin, int Cout, int taps) {
-    if (!wg_group_on() || H <= 0 || W <= 0) return 0;
-    WgTileCfg c;
-    if (!wg_tile_cfg(B, H, W, Cin, Cout, taps, c) || wg_kind(c, taps) < 0) return 0;
-    const PaTuning& t = pa_tuning();
-    const int types = (Cout / c.nb) * (Cin / c.cb);
-    int s = (taps == 9 ? t.wg_group_wgs9 : t.wg_group_wgs1) / types;
-    const int minper = taps == 9 ? t.wg_group_minper9 : t.wg_group_minper1;
-    if (s * minper > c.ntiles) s = c.ntiles / minper;
-    if (s < 1) s = 1;
-    const int per = (c.ntiles + s - 1) / s;
-    return (c.ntiles + per - 1) / per;               // balanced
-}
-
-// can this launch be a job of a group (its slab laid out with a grouped split count, tile shape known to the grouped kernel)?
-bool pa_wgrad_group_takes(const PaWgradArgs& a) {
-    if (!wg_group_on() || (a.taps == 9 && a.dbpart)) return false;
+// The plan of a launch as a job of a group; false: the grouped kernel does not take it (its slab laid out with a count the tile kernel
+// cannot run, a tile shape or operand modes the grouped kernel has no body for).
+static bool wg_job_plan(const PaWgradArgs& a, PaWgradPlan& p) {
+    p = pa_wgrad_launch_plan(a.B, a.H, a.W, a.Cin, a.Cout, a.taps, false, a.splits, a.dbpart != nullptr);
+    if (p.group_kind < 0) return false;
     if (a.dy.mode != PA_LD_PLAIN && a.dy.mode != PA_LD_LIN2) return false;
     if (a.x.mode != PA_LD_PLAIN && a.x.mode != PA_LD_BNRELU) return false;
-    if (a.taps == 9 && a.x.mode != PA_LD_BNRELU) return false;          // (the 3x3 bodies are compiled for a BatchNorm+ReLU x operand: every conv2 of the networks)
-    WgTileCfg c;
-    if (!wg_tile_cfg(a.B, a.H, a.W, a.Cin, a.Cout, a.taps, c) || wg_kind(c, a.taps) < 0) return false;
-    return a.splits >= 1 && a.splits <= c.ntiles;
+    return a.taps != 9 || a.x.mode == PA_LD_BNRELU;          // (the 3x3 bodies are compiled for a BatchNorm+ReLU x operand: every conv2 of the networks)
 }
 
 int pa_wgrad_job_workgroups(const PaWgradArgs& a) {
-    WgTileCfg c;
-    if (!wg_tile_cfg(a.B, a.H, a.W, a.Cin, a.Cout, a.taps, c)) return 0;
-    return a.splits * (a.Cout / c.nb) * (a.Cin / c.cb);
+    PaWgradPlan p;
+    return wg_job_plan(a, p) ? a.splits * p.blocks : 0;
 }
 
-// n <= PA_WG_MAXJOBS launches that pa_wgrad_group_takes() admitted, in one launch (the longest jobs first: their workgroups start first)
+// n <= PA_WG_MAXJOBS launches with pa_wgrad_job_workgroups() > 0, in one launch (the longest jobs first: their workgroups start first)
 int pa_launch_wgrad_group(const PaWgradArgs* const* as, int n, hipStream_t st, bool keep_order, const PaWgradReduceJob* red_jobs, const int* red_idx, int red_n) {
     if (n < 1 || n > PA_WG_MAXJOBS) { pa_set_error_msg("pa_launch_wgrad_group: 1 .. 8 jobs"); return 1; }
     if (red_n < 0 || red_n > PA_RED_LIST_MAX || (red_n > 0 && (!red_jobs || !red_idx))) { pa_set_error_msg("pa_launch_wgrad_group: bad reduction list"); return 1; }
     PaWgradGroup g;
     memset(&g, 0, sizeof g);
     int order[PA_WG_MAXJOBS]; long work[PA_WG_MAXJOBS];
-    WgTileCfg cs[PA_WG_MAXJOBS];
+    PaWgradPlan ps[PA_WG_MAXJOBS];
     for (int j = 0; j < n; ++j) {
-        if (!pa_wgrad_group_takes(*as[j])) { pa_set_error_msg("pa_launch_wgrad_group: a job the grouped kernel does not take"); return 1; }
-        wg_tile_cfg(as[j]->B, as[j]->H, as[j]->W, as[j]->Cin, as[j]->Cout, as[j]->taps, cs[j]);
+        if (!wg_job_plan(*as[j], ps[j])) { pa_set_error_msg("pa_launch_wgrad_group: a job the grouped kernel does not take"); return 1; }
         order[j] = j;
-        work[j] = (long)((cs[j].ntiles + as[j]->splits - 1) / as[j]->splits) * (as[j]->taps == 9 ? 3 : 2);      // tiles per workgroup x relative tile cost
+        work[j] = (long)((ps[j].ntiles + as[j]->splits - 1) / as[j]->splits) * (as[j]->taps == 9 ? 3 : 2);      // tiles per workgroup x relative tile cost
     }
     for (int i = 1; i < n && !keep_order; ++i)       // insertion sort, descending work
         for (int k = i; k > 0 && work[order[k]] > work[order[k - 1]]; --k) { const int t = order[k]; order[k] = order[k - 1]; order[k - 1] = t; }
     int begin = 0;
     for (int jj = 0; jj < n; ++jj) {
         const int j = order[jj];
-        g.a[jj] = *as[j]; g.ntiles[jj] = cs[j].ntiles; g.S[jj] = as[j]->splits; g.ny[jj] = as[j]->Cout / cs[j].nb; g.kind[jj] = wg_kind(cs[j], as[j]->taps, as[j]->dy.mode);
+        const PaWgradPlan& p = ps[j];
+        g.a[jj] = *as[j]; g.ntiles[jj] = p.ntiles; g.S[jj] = as[j]->splits; g.ny[jj] = as[j]->Cout / p.nb;
+        g.kind[jj] = p.group_kind == PA_WGK_9_44 && as[j]->dy.mode == PA_LD_LIN2 ? PA_WGK_9_44L : p.group_kind;
         g.begin[jj] = begin;
-        begin += as[j]->splits * (as[j]->Cout / cs[j].nb) * (as[j]->Cin / cs[j].cb);
+        begin += as[j]->splits * p.blocks;
     }
     g.begin[n] = begin; g.njobs = n;
     if (red_n > 0) {

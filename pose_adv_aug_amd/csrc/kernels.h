@@ -3,6 +3,7 @@
 #include "common.h"
 #include "bn_fin.h"
 #include "launch_plan.h"
+#include "wgrad_plan.h"
 
 struct PaConvArgs {
     PaOperand in;        // [B][H][W][Cin] NHWC bf16
@@ -51,18 +52,14 @@ struct PaWgradArgs {
     float* dbpart;       // or nullptr
     int B, H, W, Cin, Cout, taps, splits;
 };
+// kernel, channel blocks, tiles and slab counts: wgrad_plan.h (pa_wgrad_layer_splits set `splits` at layout time, pa_wgrad_launch_plan at launch)
 int pa_launch_wgrad(const PaWgradArgs& a, hipStream_t st);
-// H, W = 0: spatial shape unknown (generic kernel only)
-int pa_wgrad_splits(int M, int H, int W, int Cin, int Cout, int taps);
-// tile kernels (conv_wgrad_tile.hip): 0 / -1 = shape not handled there
-int pa_wgrad_tile_splits(int B, int H, int W, int Cin, int Cout, int taps);
-int pa_launch_stem_wgrad_tile(const PaWgradArgs& a, hipStream_t st);   // -1: not handled
-int pa_launch_wgrad_tile(const PaWgradArgs& a, hipStream_t st);
-// several independent weight gradients in one launch (conv_wgrad_tile.hip): split count of a layer that will be a job (0 = its shape is not
-// taken), may this launch be a job, launch n <= 8 jobs
-int pa_wgrad_group_splits(int B, int H, int W, int Cin, int Cout, int taps);
-bool pa_wgrad_group_takes(const PaWgradArgs& a);
-int pa_wgrad_job_workgroups(const PaWgradArgs& a);          // workgroups of the launch as a job
+// tile kernels (conv_wgrad_tile.hip), called by pa_launch_wgrad / pa_launch_stem_wgrad with the plan that chose them
+int pa_launch_stem_wgrad_tile(const PaWgradArgs& a, const PaWgradPlan& p, hipStream_t st);
+int pa_launch_wgrad_tile(const PaWgradArgs& a, const PaWgradPlan& p, hipStream_t st);
+// several independent weight gradients in one launch (conv_wgrad_tile.hip): workgroups of this launch as a job (0: it cannot be one -- slab
+// count, tile shape or operand modes the grouped kernel does not take), launch n <= 8 jobs
+int pa_wgrad_job_workgroups(const PaWgradArgs& a);
 struct PaWgradReduceJob;
 // keep_order: jobs in the caller's order (default: longest first); red_*: red_n <= PA_RED_LIST_MAX entries of the reduce table whose slabs
 // (complete on `st` before this launch) are summed by a few more workgroups of the same launch

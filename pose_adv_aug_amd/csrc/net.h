@@ -164,7 +164,7 @@ struct Net {
     hipEvent_t ev_wdone;
     // weight-gradient launches are collected and flushed in groups: ONE event record on the producing stream per group
     // (an event record between two kernels of a queue costs a 15-20 us bubble on it: ~100 records per step were 1.5 ms)
-    struct PendingWgrad { PaWgradArgs a; int cls; double bytes, flops; bool stem; ConvLayer* c; };
+    struct PendingWgrad { PaWgradArgs a; int cls; double bytes, flops; bool stem; int job_wgs; ConvLayer* c; };      // job_wgs: workgroups as a job of a group launch (0: launched alone)
     // with a weight-gradient stream, the slabs of a group are summed right behind it on that stream (part of them still in the 256 MB
     // Infinity Cache) instead of by one 280 us reduction on the main stream at the end of the step
     std::vector<PendingWgrad> pending_wgrads;

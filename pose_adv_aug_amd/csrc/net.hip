@@ -114,15 +114,10 @@ void Net::layout_conv(ConvLayer& c, Arena& a, int M, int H, int W) {
     const size_t wn = (size_t)c.pcout * (c.k == 7 ? 1 : c.taps()) * c.pcin;
     c.wf = a.get<bf16>(wn);
     c.wb = (c.k == 7) ? nullptr : a.get<bf16>(wn);
-    c.splits = c.k == 7 ? pa_wgrad_splits(M, 0, 0, c.pcin, c.pcout, 1) : pa_wgrad_splits(M, H, W, c.pcin, c.pcout, c.taps());
-    if (c.k != 7 && H > 0 && B > 0 && M == B * H * W) {          // a layer the grouped weight-gradient kernel takes: few, long splits
-        const int gs = pa_wgrad_group_splits(B, H, W, c.pcin, c.pcout, c.taps());
-        if (gs > 0) c.splits = gs;
-    }
-    if (c.k == 7) {                              // stem: 64 KB slabs, so two workgroups per CU (their load / MFMA phases overlap)
-        const int ss = pa_tuning().stem_splits;       // 512: 6.96 vs 7.00 ms (256)
-        if (ss > 0 && ss <= (M + 127) / 128) c.splits = ss;
-    }
+    // slab count (wgrad_plan.h): the grouped kernel's few, long splits where the layer's launches will be jobs of a group
+    const bool shaped = H > 0 && W > 0 && M % (H * W) == 0;
+    const PaWgradPlan p = pa_wgrad_plan(shaped ? M / (H * W) : M, shaped ? H : 0, shaped ? W : 0, c.pcin, c.pcout, c.k == 7 ? 1 : c.taps(), c.k == 7);
+    c.splits = pa_wgrad_layer_splits(p, H > 0 && B > 0 && M == B * H * W);
     c.part_floats = (size_t)c.splits * wn;
     c.db_floats = c.has_bn_after ? 0 : (size_t)c.splits * c.pcout;
     c.part = a.get<float>(c.part_floats);
@@ -467,8 +462,9 @@ int Net::conv_wgrad(ConvLayer& c, const PaOperand& dy, const PaOperand& x, int B
     // then see the kernels of the real step; the others are launched here and summed by reduce_grads().
     const bool aside = wgrads_aside();
     const bool stem_now = c.k == 7 && aside && pa_tuning().stem_on_main;
-    if (aside ? !stem_now : (c.k != 7 && pa_wgrad_group_takes(a))) {
-        PendingWgrad p; p.a = a; p.cls = cls; p.bytes = wb; p.flops = wf; p.stem = c.k == 7; p.c = &c;
+    const int job_wgs = c.k == 7 ? 0 : pa_wgrad_job_workgroups(a);
+    if (aside ? !stem_now : job_wgs > 0) {
+        PendingWgrad p; p.a = a; p.cls = cls; p.bytes = wb; p.flops = wf; p.stem = c.k == 7; p.job_wgs = job_wgs; p.c = &c;
         pending_wgrads.push_back(p);
         return 0;
     }
@@ -544,8 +540,8 @@ int Net::launch_pending_wgrads() {
     int wgs = 0;
     for (size_t pi = 0; pi < pending_wgrads.size(); ++pi) {
         PendingWgrad& p = pending_wgrads[pi];
-        if (p.stem || !pa_wgrad_group_takes(p.a)) continue;
-        const int w = pa_wgrad_job_workgroups(p.a);
+        const int w = p.job_wgs;
+        if (w == 0) continue;
         if (nj > 0 && (nj == 8 || wgs + w > cap)) { TRY(fire()); wgs = 0; }
         grouped[pi] = 1;
         jidx[nj] = (int)pi;

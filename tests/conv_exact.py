@@ -25,15 +25,15 @@ conv_wgrad_tile.hip:157/171, pose_ops.hip:137): no split of the reduction across
     channel counts (multiples of 64; 256 for the stem's 7 x 7 x 4 patch) and A the epilogue adds (bias, add1, add2).
   * weight gradient: a split owns a contiguous (conv_wgrad.hip: steps of 64 / 128 pixels) or strided (conv_wgrad_tile.hip: tiles of
     128 pixels) share of the ceil(M / P) tiles of P <= 128 pixels, at most M / S + 2 P pixels, one MFMA per 32 of them; the slabs of the S
-    splits are then chained in split order (wgrad_reduce.h; the stem's reducer: four slices of S / 4 plus three adds, conv_wgrad.hip:340):
+    splits are then chained in split order (wgrad_reduce.h; the stem's reducer: four slices of S / 4 plus three adds, stem_wgrad_reduce_kernel):
     D = 32 + ceil((M / S + 256) / 32) + S.
   * bias gradient (convs without a BatchNorm behind them): any tree over the <= M / S + 256 values of a split (per-thread column sums
     and their LDS sum, conv_wgrad_tile.hip:466, conv_wgrad.hip:222), then the chain over S: D = M / S + 256 + S.
-  S is the split count Net::layout_conv (net.hip:108-125) gives the layer: pa_wgrad_splits (conv_wgrad.hip:238-256, with the tile
-  kernels' count wg_tile_cfg conv_wgrad_tile.hip:537-557), replaced by pa_wgrad_group_splits (conv_wgrad_tile.hip:637-649) where the
-  grouped kernel takes the layer, and 512 for the stem (net.hip:120-123).  They are not exported: wgrad_splits() mirrors them for the
-  release build, which reads no tuning variable (common.h pa_getenv); tests/test_gpu_conv_exact.py checks the mirror against the
-  workspace sizes the library reports.  A shape no kernel takes raises instead of getting a default.
+  S is the split count Net::layout_conv gives the layer: pa_wgrad_layer_splits over the layer's pa_wgrad_plan (csrc/wgrad_plan.h) -- the
+  count of the layer launched alone (the tile kernels' where they take the shape, else the generic kernel's), replaced by the grouped
+  count where the grouped kernel takes the layer, and 512 for the stem.  The plan is not exported: wgrad_plan() mirrors it for the
+  release build, which reads no tuning variable (csrc/tuning.h); tests/test_gpu_conv_exact.py checks the mirror against the workspace
+  sizes the library reports.  A shape no kernel takes raises instead of getting a default.
 
 Per-element bound (16-bit storage output):  |got - ref| <= e + 1/2 ulp_T(|ref| + e),  e = 2u D (sum |a w| + |bias| + sum |addends|),
 where sum |a w| is the float64 convolution of the absolute operands and ulp_T the storage type's ulp at that magnitude (bf16: 2^-7
@@ -50,6 +50,7 @@ have a bound of at least 1 % of the sum of the absolute values of their terms (s
 hundredth of the terms could pass.  (Relative to the result itself it cannot be judged: the bias gradients of forth_conv / in_conv sum a
 gradient whose per-channel sums nearly cancel -- it has passed through BatchNorm backward passes -- to values far below any fp32 sum's
 error.)"""
+import collections
 import os
 import sys
 
@@ -124,73 +125,81 @@ def pad64(c):
     return (c + 63) // 64 * 64
 
 
-# ---- split counts of the release build (not exported; see the module docstring for the source lines)
-def _tile_cfg(B, H, W, Cin, Cout, taps):
-    """wg_tile_cfg (conv_wgrad_tile.hip:537-557): (n block, c block, tiles, splits) or None."""
-    if H <= 0 or W <= 0:
-        return None
+# ---- split counts of the release build (not exported): pa_wgrad_plan and pa_wgrad_layer_splits of csrc/wgrad_plan.h, field for field
+WgradPlan = collections.namedtuple('WgradPlan', 'path nb cb ntiles splits group_splits group_kind blocks')
+
+
+def _balanced(ntiles, s):
+    """pa_wgrad_balanced"""
+    per = -(-ntiles // s)
+    return -(-ntiles // per)
+
+
+def _has_kernel(Cin, Cout, taps):
+    return taps in (1, 9) and Cin % 64 == 0 and Cout % 64 == 0
+
+
+def wgrad_plan(B, H, W, Cin, Cout, taps, stem=False):
+    """pa_wgrad_plan (over pa_wgrad_generic_plan) at the release values of csrc/tuning.h.  H <= 0 or W <= 0: spatial shape unknown, B
+    counts the pixels.  group_kind: the name of the wgrad_group_kernel body, None for -1."""
+    if not _has_kernel(Cin, Cout, taps):
+        raise ValueError('no weight-gradient kernel for Cin %d Cout %d taps %d' % (Cin, Cout, taps))
+    shaped = H > 0 and W > 0
+    M = B * H * W if shaped else B
+    # pa_wgrad_generic_plan
+    nb, cb = (128 if Cout % 128 == 0 else 64), (128 if Cin % 128 == 0 else 64)
+    blocks = (Cout // nb) * (taps * Cin // cb)
+    ms = 128 if nb + cb <= 128 else 64
+    ntiles = -(-M // ms)
+    s = (-(-(1024 if taps == 9 else 512) // blocks) + 7) & ~7
+    p = WgradPlan('stem generic' if stem else 'generic', nb, cb, ntiles, max(min(s, ntiles), 1), 0, None, blocks)
+    if stem:
+        p = p._replace(nb=64, cb=128, ntiles=-(-M // 64), blocks=2)
+        ntiles = -(-M // 128)
+        if 512 <= ntiles:
+            p = p._replace(splits=512)
+        return p._replace(path='stem tile', nb=64, cb=256, ntiles=ntiles, blocks=1)
+    if not shaped:
+        return p
     if taps == 9:
-        if Cin % 64 or Cout % 64 or H % 8 or W % 16:
-            return None
+        if H % 8 or W % 16:
+            return p
         nb = cb = 64
-        nt = B * (H // 8) * (W // 16)
-        if nt < 48:
-            return None
-    elif taps == 1:
-        if Cin % 64 or Cout % 64:
-            return None
-        nb, cb = (128 if Cout % 128 == 0 else 64), (128 if Cin % 128 == 0 else 64)
-        nt = -(-(B * H * W) // 128)
-        if nt < 3:
-            return None
+        ntiles = B * (H // 8) * (W // 16)
+        if ntiles < 48:
+            return p
     else:
-        return None
-    types = (Cout // nb) * (Cin // cb)
-    s = min(max(256 // types, 1), nt)
-    per = min(max(-(-nt // s), 1), nt)                      # tiles per workgroup (at least 1, at most all)
-    return nb, cb, nt, -(-nt // per)
+        ntiles = -(-M // 128)
+        if ntiles < 3:
+            return p
+    blocks = (Cout // nb) * (Cin // cb)
+    splits = _balanced(ntiles, min(max(256 // blocks, 1), ntiles))
+    s = 64 // blocks
+    minper = 4 if taps == 9 else 2
+    if s * minper > ntiles:
+        s = ntiles // minper
+    kind = 'PA_WGK_9_44' if taps == 9 else 'PA_WGK_1_%d%d' % (nb // 32, cb // 32)
+    return WgradPlan('tile', nb, cb, ntiles, splits, _balanced(ntiles, max(s, 1)), kind, blocks)
 
 
 def wgrad_splits(M, H, W, Cin, Cout, taps):
-    """pa_wgrad_splits (conv_wgrad.hip:238-256)."""
-    if taps not in (1, 9) or Cin % 64 or Cout % 64:
-        raise ValueError('no weight-gradient kernel for Cin %d Cout %d taps %d' % (Cin, Cout, taps))
-    if H > 0 and W > 0 and M % (H * W) == 0:
-        c = _tile_cfg(M // (H * W), H, W, Cin, Cout, taps)
-        if c:
-            return c[3]
-    TN, TK = (128 if Cout % 128 == 0 else 64), (128 if Cin % 128 == 0 else 64)
-    tiles = (Cout // TN) * (taps * Cin // TK)
-    ms = 128 if TN + TK <= 128 else 64
-    s = (-(-(1024 if taps == 9 else 512) // tiles) + 7) & ~7
-    return max(min(s, -(-M // ms)), 1)
+    """PaWgradPlan::splits, the count of the layer launched alone, as Net::layout_conv asks for it: M pixels, a map only where it divides
+    them."""
+    shaped = H > 0 and W > 0 and M % (H * W) == 0
+    return (wgrad_plan(M // (H * W), H, W, Cin, Cout, taps) if shaped else wgrad_plan(M, 0, 0, Cin, Cout, taps)).splits
 
 
 def group_splits(B, H, W, Cin, Cout, taps):
-    """pa_wgrad_group_splits (conv_wgrad_tile.hip:637-649); 0: the grouped kernel does not take the shape."""
-    c = _tile_cfg(B, H, W, Cin, Cout, taps)
-    if not c:
-        return 0
-    nb, cb, nt, _ = c
-    types = (Cout // nb) * (Cin // cb)
-    s = 64 // types
-    minper = 4 if taps == 9 else 2
-    if s * minper > nt:
-        s = nt // minper
-    s = max(s, 1)
-    per = -(-nt // s)
-    return -(-nt // per)
+    """PaWgradPlan::group_splits; 0: the grouped kernel does not take the shape."""
+    return wgrad_plan(B, H, W, Cin, Cout, taps).group_splits if _has_kernel(Cin, Cout, taps) else 0
 
 
 def layer_splits(B, H, W, Cin, Cout, k):
-    """S of a layer of the net (Net::layout_conv, net.hip:108-125); Cin / Cout real, padded here."""
-    M = B * H * W
+    """S of a layer of the net (pa_wgrad_layer_splits as Net::layout_conv calls it, the batch known); Cin / Cout real, padded here."""
     if k == 7:
-        s = wgrad_splits(M, 0, 0, 256, pad64(Cout), 1)
-        return 512 if 512 <= -(-M // 128) else s
-    s = wgrad_splits(M, H, W, pad64(Cin), pad64(Cout), k * k)
-    gs = group_splits(B, H, W, pad64(Cin), pad64(Cout), k * k)
-    return gs if gs > 0 else s
+        return wgrad_plan(B, H, W, 256, pad64(Cout), 1, stem=True).splits
+    p = wgrad_plan(B, H, W, pad64(Cin), pad64(Cout), k * k)
+    return p.group_splits if p.group_splits > 0 else p.splits
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -190,7 +190,7 @@ def test_an_element_whose_terms_are_all_zero_must_be_zero(dtype, floor):
 
 
 def test_split_mirror_knows_the_net_layers_and_refuses_unknown_shapes():
-    assert X.layer_splits(24, 128, 128, 3, 64, 7) == 512              # the stem at benchmark size (net.hip:120-123)
+    assert X.layer_splits(24, 128, 128, 3, 64, 7) == 512              # the stem at benchmark size (pa_wgrad_plan's stem override)
     assert X.layer_splits(2, 64, 64, 3, 64, 7) == 128                 # tiny maps: the generic count
     assert X.group_splits(24, 64, 64, 128, 128, 9) > 0                # the grouped kernel takes the 64 x 64 3 x 3 layers
     assert X.group_splits(2, 8, 8, 128, 128, 9) == 0
@@ -198,6 +198,28 @@ def test_split_mirror_knows_the_net_layers_and_refuses_unknown_shapes():
         X.wgrad_splits(100, 10, 10, 96, 64, 1)
     with pytest.raises(ValueError):
         X.wgrad_splits(100, 10, 10, 64, 64, 4)
+
+
+def test_the_grouped_split_count_never_exceeds_the_count_of_the_layer_alone():
+    """pa_conv2d_workspace_bytes lays its layer out without the batch (PaWgradPlan::splits), pa_conv2d with it (group_splits where the
+    grouped kernel takes the shape): the size query covers the run only while group_splits <= splits.  Release values, every shape of the
+    sweep."""
+    n = 0
+    for taps in (1, 9):
+        for Cin in (64, 128, 192, 256, 384, 512):
+            for Cout in (64, 128, 192, 256, 384, 512):
+                for B in (1, 2, 3, 5, 8, 16, 24, 32):
+                    for H in (4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128):
+                        for W in sorted(set((H, 2 * H, 16, 32))):
+                            p = X.wgrad_plan(B, H, W, Cin, Cout, taps)
+                            assert p.group_splits <= p.splits, ((B, H, W, Cin, Cout, taps), p)
+                            n += 1
+    assert n == 23040
+
+
+# The workspace queries make no HIP call, so the mirror test of the GPU selection also runs here (same body, collected a second time
+# under this module): it pins every layer's slab count without a GPU.
+from tests.test_gpu_conv_exact import test_split_mirror_matches_the_library  # noqa: E402,F401
 
 
 def test_data_gradient_of_a_plain_input_catches_a_relu_mask():

@@ -185,9 +185,10 @@ _TABLES = [48, 56, 56]
     [(3, 128, 128, 96 >> j, 96 >> j, 3) for j in range(5)] + [(2, 64, 64, 32 >> j, 32 >> j, 3) for j in range(4)] +
     [(24, 256, 64, 64, 64, 1), (24, 64, 256, 64, 64, 1), (3, 64, 256, 96, 96, 1), (2, 64, 128, 32, 32, 1)])))
 def test_split_mirror_matches_the_library(B, Cin, Cout, H, W, k):
-    """S of tests/conv_exact.py (pa_wgrad_splits and pa_wgrad_group_splits) against the split counts the library's workspace sizes
-    reveal: pa_conv2d_workspace_bytes lays the layer out without a batch (no grouped split: pa_wgrad_splits), pa_wgrad_group_workspace_bytes
-    with it (the grouped split where the grouped kernel takes the shape).  Both workspaces hold S slabs of Cout * taps * Cin floats."""
+    """S of tests/conv_exact.py (wgrad_plan, the mirror of pa_wgrad_plan) against the split counts the library's workspace sizes reveal:
+    pa_conv2d_workspace_bytes lays the layer out without a batch (no grouped split: PaWgradPlan::splits), pa_wgrad_group_workspace_bytes
+    with it (group_splits where the grouped kernel takes the shape).  Both workspaces hold S slabs of Cout * taps * Cin floats.  No HIP
+    call is made: tests/test_conv_exact_cpu.py runs this test without a GPU as well."""
     from pose_adv_aug_amd._lib import lib
     L = lib()
     M, wn = B * H * W, Cout * k * k * Cin
@@ -207,3 +208,37 @@ def test_split_mirror_matches_the_library(B, Cin, Cout, H, W, k):
     grp = lambda S: _arena(_TABLES + [2 * wn, 2 * wn, 4 * S * wn, 2 * M * Cout, 2 * M * Cin, 4 * (nparams + 8), 4 * (nparams + 8)])
     S2 = [S for S in range(1, 4097) if grp(S) == got]
     assert S2 == [X.layer_splits(B, H, W, Cin, Cout, k)], (got, S2)
+
+
+@pytest.mark.parametrize('B,Cin,Cout,H,W,k,alone,grouped', [(2, 64, 64, 16, 16, 1, 4, 2), (3, 64, 64, 32, 64, 3, 48, 12)])
+def test_conv2d_weight_gradient_stays_inside_its_workspace(B, Cin, Cout, H, W, k, alone, grouped):
+    """pa_conv2d_workspace_bytes lays the layer out without the batch (the slab count of a launch alone), pa_conv2d with it (the smaller
+    grouped count): the smallest shapes where the two differ, run inside exactly the reported bytes with 64 MB guard regions on both
+    sides.  With a bias gradient (the layout of the size query; a 3 x 3 launch then takes the generic kernel at the grouped count) and
+    without one (fewer bytes; the tile kernels).  The guards stay untouched and the gradients are within their bounds at S = grouped."""
+    import ctypes as C
+    from pose_adv_aug_amd._lib import lib, check, ptr, stream, act_dtype
+    L = lib()
+    dt = act_dtype()
+    assert (X.wgrad_splits(B * H * W, H, W, Cin, Cout, k * k), X.layer_splits(B, H, W, Cin, Cout, k)) == (alone, grouped)
+    g = inputs.rng(501, B, Cin, Cout, H, W, k)
+    f = lambda *s: torch.from_numpy(g.standard_normal(s).astype(np.float32))
+    x, dy, w = f(B, Cin, H, W).cuda(), f(B, Cout, H, W).cuda(), f(Cout, Cin, k, k).cuda()
+    xd, dyd = X.rnd(x.double(), dt), X.rnd(dy.double(), dt)
+    nws = L.pa_conv2d_workspace_bytes(B, Cin, Cout, H, W, k)
+    SL = 64 << 20
+    for want_db in (True, False):
+        big = torch.zeros(nws + 2 * SL, dtype=torch.uint8, device='cuda')
+        big[:SL] = 0x5A; big[SL + nws:] = 0x5A
+        dw = torch.empty((Cout, Cin, k, k), device='cuda')
+        db = torch.empty(Cout, device='cuda') if want_db else None
+        check(L.pa_conv2d(2, ptr(dy), ptr(x), ptr(w), None, ptr(dw), ptr(db), B, Cin, Cout, H, W, k,
+                          C.c_void_p(big.data_ptr() + SL), stream()), 'pa_conv2d')
+        torch.cuda.synchronize()
+        assert bool((big[:SL] == 0x5A).all()) and bool((big[SL + nws:] == 0x5A).all()), want_db
+        worst = {'weight gradient': X.wgrad_check(dw, xd, dyd, k, grouped)}
+        if want_db:
+            worst['bias gradient'] = X.bgrad_check(db, dyd, grouped)
+        for kind, (r, deg) in worst.items():
+            assert r <= 1.0, (kind, want_db, r, worst)
+            assert deg <= X.DEGENERATE, ('degenerate bound', kind, want_db, deg)
