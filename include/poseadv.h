@@ -261,6 +261,14 @@ typedef struct pa_net pa_net;
 /* create_hg(num_stacks, num_modules=1, num_classes=16, chan) (models/asn_stacked_hg.py:344-347) for a
  * fixed per-GPU batch B and input resolution res (256).  chan must be a multiple of 128. */
 pa_net* pa_hg_create(int num_stacks, int num_classes, int chan, int B, int res);
+/* create_hg with num_modules residual blocks per site (models/asn_stacked_hg.py:73-77, :272-276): each of the 13 sites of an
+ * hourglass and post_res is a chain of num_modules blocks, named "hg.<i>.<site>.<j>." (sites in the order down1-4, up1-4,
+ * skip1-4, neck; j = 0 .. num_modules-1) and "post_res.<i>.<j>.".  1 <= num_modules <= 8, anything else returns NULL with
+ * pa_last_error() set; every other condition is pa_hg_create's.  pa_hg_create is the num_modules == 1 case of the same code
+ * (same tensor table, counts and workspace size). */
+pa_net* pa_hg_create_modules(int num_stacks, int num_modules, int num_classes, int chan, int B, int res);
+/* blocks per site of a pose net; 1 for an agent */
+int pa_net_num_modules(const pa_net* net);
 /* create_asn(chan, chan, scale_num, rotation_num, is_aug=True) (models/asn_stacked_hg.py:441-444) bound
  * to the feature shapes of a pose net with neck resolution res/64.  The head is the reference's AvgPool2d(4) + view +
  * Linear(chan, K): the mean of the TOP-LEFT 4 x 4 window of the res/64 top map (the whole map at res 256), gradient df / 16 inside
@@ -304,7 +312,7 @@ int pa_hg_backward(pa_net* net);
  * phase p = 0 .. num_stacks-1 enqueues the backward pass of stack num_stacks-1-p (its head layers, post block and hourglass),
  * phase num_stacks the stem and the final reductions; all phases in order == pa_hg_backward.
  * pa_hg_bucket_range: [lo, hi) = the contiguous range of the flat parameter / gradient array that holds hg.<stack> (13
- * residual blocks: 42 % of a 2-stack net's parameters each).
+ * sites of num_modules residual blocks each: 42 % of a 2-stack net's parameters per stack at num_modules 1).
  * pa_hg_bucket_wait: call after the phase of `stack`: makes `stream` (the caller's communication stream) wait until every
  * gradient in that range is final -- the main chain's work so far AND the slab reductions of the engine's weight-gradient
  * stream.  Returns 0, or -1 if the current stream mode finishes gradients only at the end (exchange everything after the
@@ -433,7 +441,10 @@ int pa_net_set_multi_stream(pa_net* net, int on);
  * 1 and 3 return an error for a tensor without a gradient buffer; any other grad value is an error.  Every buffer the hook names keeps
  * its value to the end of the step (the arena gives each tensor its own storage).
  * Names: "stem", "res1".."res3", "pool0", "hg<i>.skip<k>|pool<k>|down<k>|up<k>|merge<k>|neck" (k=1..4),
- * "post<i>", "lin<i>", "xin<i>", optional suffix ".x1"/".x2" for a block's inner tensors; "heat<i>" (the heat maps as stored for
+ * "post<i>", "lin<i>", "xin<i>", optional suffix ".x1"/".x2" for a block's inner tensors.  A site of num_modules blocks (skip /
+ * down / up / neck / post): the plain name is the site's output, i.e. its LAST block; "<site>.m<j>" names block j of the chain
+ * ("hg0.up3.m0", "post1.m1.x2": ".x1"/".x2" come behind it), ".m<num_modules-1>" is the same tensor as the plain name, a j past the
+ * chain is an error.  "heat<i>" (the heat maps as stored for
  * in_conv, 64 channels of which 16..63 are zero; its gradient: d heat as stored for out_conv's weight gradient), "heat<i>.in"
  * (in_conv's data gradient, 64 channels, no gradient) and "forth<i>" (forth_conv's stored output forth_conv(lin) + xin, no gradient)
  * for the head layers between stacks i and i + 1; "hg<i>.poolgrad<k>" (no gradient): the gradient max pool k routes back to its

@@ -101,6 +101,8 @@ _PROTOS = {
     'pa_nchw_to_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'pa_nhwc_to_nchw': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'pa_hg_create': (_vp, [_i, _i, _i, _i, _i]),
+    'pa_hg_create_modules': (_vp, [_i, _i, _i, _i, _i, _i]),
+    'pa_net_num_modules': (_i, [_vp]),
     'pa_asn_create': (_vp, [_i, _i, _i, _i, _i]),
     'pa_asn_create_dropout': (_vp, [_i, _i, _i]),
     'pa_asn_forward_masks': (_i, [_vp, _vp, _i, _vp]),

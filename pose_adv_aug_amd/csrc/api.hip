@@ -432,21 +432,38 @@ int pa_conv2d_time(int mode, int variant, int B, int Cin, int Cout, int H, int W
 }
 
 // ---------------------------------------------------------------------------- networks
-pa_net* pa_hg_create(int num_stacks, int num_classes, int chan, int B, int res) {
+static pa_net* hg_create(const char* who, int num_stacks, int num_modules, int num_classes, int chan, int B, int res) {
     g_err[0] = 0;
-    if (num_classes != 16 || chan % 128 != 0 || chan > 2048 || res % 64 != 0 || B < 1 || num_stacks < 1) {
-        pa_set_error_msg("pa_hg_create: need num_classes == 16, chan % 128 == 0, res % 64 == 0");
+    char msg[160];
+    if (num_modules < 1 || num_modules > 8) {
+        snprintf(msg, sizeof msg, "%s: need 1 <= num_modules <= 8", who);
+        pa_set_error_msg(msg);
         return nullptr;
     }
-    if (!pa_stats_groups_ok(chan)) { pa_set_error_msg("pa_hg_create: " PA_STATS_GROUPS_MSG); return nullptr; }
+    if (num_classes != 16 || chan % 128 != 0 || chan > 2048 || res % 64 != 0 || B < 1 || num_stacks < 1) {
+        snprintf(msg, sizeof msg, "%s: need num_classes == 16, chan %% 128 == 0, res %% 64 == 0", who);
+        pa_set_error_msg(msg);
+        return nullptr;
+    }
+    if (!pa_stats_groups_ok(chan)) { snprintf(msg, sizeof msg, "%s: " PA_STATS_GROUPS_MSG, who); pa_set_error_msg(msg); return nullptr; }
     pa_net* p = new (std::nothrow) pa_net;
     if (!p) return nullptr;
     Net& n = p->n;
-    n.stacks = num_stacks; n.classes = num_classes; n.chan = chan; n.B = B; n.res = res;
+    n.stacks = num_stacks; n.modules = num_modules; n.classes = num_classes; n.chan = chan; n.B = B; n.res = res;
     n.declare_pose();
     n.workspace_bytes = n.layout_all(nullptr);
     return p;
 }
+
+pa_net* pa_hg_create(int num_stacks, int num_classes, int chan, int B, int res) {
+    return hg_create("pa_hg_create", num_stacks, 1, num_classes, chan, B, res);
+}
+
+pa_net* pa_hg_create_modules(int num_stacks, int num_modules, int num_classes, int chan, int B, int res) {
+    return hg_create("pa_hg_create_modules", num_stacks, num_modules, num_classes, chan, B, res);
+}
+
+int pa_net_num_modules(const pa_net* net) { return net->n.is_agent ? 1 : net->n.modules; }
 
 pa_net* pa_asn_create(int chan, int scale_num, int rotation_num, int B, int res) {
     g_err[0] = 0;
@@ -761,7 +778,8 @@ static int debug_copy(Net& n, const Act& a, int grad, float* out, int* shape4, c
 // debug / test hook: copy an internal activation (BatchNorm+ReLU applied) or its gradient buffer out as
 // NCHW fp32.  which: "stem", "res1", "pool0", "res2", "res3", "hg<i>.skip<k>", "hg<i>.pool<k>",
 // "hg<i>.down<k>", "hg<i>.neck", "hg<i>.up<k>", "hg<i>.merge<k>", "post<i>", "lin<i>", "xin<i>" (k = 1..4)
-// and "<name>.x1"/".x2" for the inner tensors of a residual block; "hg<i>.maskedskip<k>", "hg<i>.maskedneck" (occlusion branch);
+// and "<name>.x1"/".x2" for the inner tensors of a residual block; the names of the sites of num_modules blocks (skip / down / neck / up /
+// post) mean the site's output, i.e. its last block, and "<site>.m<j>" names block j ("hg0.up3.m0", "post1.m1.x2"); "hg<i>.maskedskip<k>", "hg<i>.maskedneck" (occlusion branch);
 // "heat<i>": the heat maps in the storage type as in_conv reads them (64 channels, 16..63 zero), gradient: d heat as out_conv's
 // weight gradient reads it; "heat<i>.in": in_conv's data gradient (its part of d heat); "forth<i>": forth_conv's output
 // (forth_conv(lin) + xin), in_conv's addend; "hg<i>.poolgrad<k>": the gradient pool k routes back to its input (plus, k = 1, the
@@ -777,6 +795,14 @@ int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int
         if (rest == ".x2") { mat = r.dz2_valid ? r.dz2 : nullptr; return &r.x2; }
         mat = r.dz3_valid ? r.dz3 : nullptr;
         return &r.x3;
+    };
+    // a site of num_modules blocks: "<site>" is its output (the last block), "<site>.m<j>" block j; ".x1" / ".x2" come behind either
+    bool bad_block = false;
+    auto pick_chain = [&](Chain& c, std::string rest) -> const Act* {
+        size_t j = c.m.size() - 1;
+        if (rest.size() >= 3 && rest[0] == '.' && rest[1] == 'm' && rest[2] >= '0' && rest[2] <= '9') { j = (size_t)(rest[2] - '0'); rest = rest.substr(3); }
+        if (j >= c.m.size()) { bad_block = true; return nullptr; }
+        return pick_res(c.m[j], rest);
     };
     auto starts = [&](const char* p) { return w.rfind(p, 0) == 0; };
     Act head;                        // buffers that are no activation of their own: "heat<i>", "heat<i>.in", "forth<i>", "hg<i>.poolgrad<k>"
@@ -796,32 +822,33 @@ int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int
     else if (starts("pool0")) a = &n.pool0;
     else if (starts("res2")) a = pick_res(n.res2, w.substr(4));
     else if (starts("res3")) a = pick_res(n.res3, w.substr(4));
-    else if (starts("post")) { int i = w[4] - '0'; a = pick_res(n.post[i], w.substr(5)); }
+    else if (starts("post")) { int i = w[4] - '0'; a = pick_chain(n.post[i], w.substr(5)); }
     else if (starts("lin")) { int i = w[3] - '0'; a = &n.lin_out[i]; }
     else if (starts("xin")) { int i = w[3] - '0'; a = &n.xin[i]; }
     else if (starts("hg")) {
         int i = w[2] - '0';
         std::string r = w.substr(4);
         Hourglass& h = n.hg[i];
-        if (r.rfind("neck", 0) == 0) a = pick_res(h.neck, r.substr(4));
+        if (r.rfind("neck", 0) == 0) a = pick_chain(h.neck, r.substr(4));
         else if (r == "maskedneck") a = &h.neckm;                                  // occlusion branch: neck * cell mask
         else if (r.rfind("maskedskip", 0) == 0) a = &h.skipm[r[10] - '1'];
         else if (r.rfind("poolgrad", 0) == 0) {                                     // the pool's gradient routed to its input (+ extra0)
             const int k = r.size() == 9 ? r[8] - '1' : -1;
             if (k >= 0 && k < 4 && h.poolgrad[k]) {
-                const Act& x = h.skip[k].x3;
+                const Act& x = h.skip[k].out();
                 head.raw = h.poolgrad[k]; head.B = x.B; head.H = x.H; head.W = x.W; head.C = x.C; a = &head;
             }
         } else {
             int k = r[r.find_first_of("1234")] - '1';
             std::string rest = r.substr(r.find_first_of("1234") + 1);
-            if (r.rfind("skip", 0) == 0) a = pick_res(h.skip[k], rest);
-            else if (r.rfind("down", 0) == 0) a = pick_res(h.down[k], rest);
-            else if (r.rfind("up", 0) == 0) a = pick_res(h.up[k], rest);
+            if (r.rfind("skip", 0) == 0) a = pick_chain(h.skip[k], rest);
+            else if (r.rfind("down", 0) == 0) a = pick_chain(h.down[k], rest);
+            else if (r.rfind("up", 0) == 0) a = pick_chain(h.up[k], rest);
             else if (r.rfind("pool", 0) == 0) a = &h.pooled[k];
             else if (r.rfind("merge", 0) == 0) a = &h.merged[k];
         }
     }
+    if (bad_block) { pa_set_error_msg("pa_hg_debug_tensor: no such block in the site's chain"); return 1; }
     if (!a) { pa_set_error_msg("pa_hg_debug_tensor: unknown tensor name"); return 1; }
     return debug_copy(n, *a, grad, out, shape4, "pa_hg_debug_tensor", mat);
 }

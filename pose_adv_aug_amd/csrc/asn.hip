@@ -247,7 +247,7 @@ int Net::asn_forward_trunk(Net& pose, bool train, const Act** top) {
     TRY(begin_step());
     if (!train) TRY(pa_launch_bn_eval(bneval_jobs, n_bneval, eps, st));
     Hourglass& h = pose.hg[0];
-    const Act* feats[5] = {&h.skip[0].x3, &h.skip[1].x3, &h.skip[2].x3, &h.skip[3].x3, &h.neck.x3};
+    const Act* feats[5] = {&h.skip[0].out(), &h.skip[1].out(), &h.skip[2].out(), &h.skip[3].out(), &h.neck.out()};      // (a chain's last block)
     for (int k = 0; k < 5; ++k) TRY(asn_in[k].fwd(*this, *feats[k]));
     // the agent reads the pose net's BatchNorm scale/shift through op(): they belong to `pose`
     const Act* x = &asn_in[0].x3;
@@ -318,7 +318,7 @@ int Net::asn_backward(Net& pose, const float* target_s, const float* target_r, f
 
 int Net::asn_backward_trunk(Net& pose, const bf16* dact) {
     Hourglass& h = pose.hg[0];
-    const Act* feats[5] = {&h.skip[0].x3, &h.skip[1].x3, &h.skip[2].x3, &h.skip[3].x3, &h.neck.x3};
+    const Act* feats[5] = {&h.skip[0].out(), &h.skip[1].out(), &h.skip[2].out(), &h.skip[3].out(), &h.neck.out()};      // (a chain's last block)
     const Act& top = asn_deep[2].x3;
     TRY(pa_launch_ep_apply(pa_plain(dact), final_ep(top), top.grad, (size_t)top.M(), top.C, st));
     TRY(finish_grad(top));

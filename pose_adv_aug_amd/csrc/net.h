@@ -110,8 +110,28 @@ struct Residual {
     int bwd_b(Net& n, const Act& in, const PaOperand& extra);           // input gradient (needs `extra`)
 };
 
+// One site of the reference's module tree: nn.Sequential of num_modules residual blocks (reference :73-77, :272-276).  Block j reads block
+// j-1's x3 (pending BatchNorm, two readers: conv1 and conv3's shortcut addend).  What a site does towards its neighbours splits between the two
+// ends: head() carries the input side (low_of_in / low_fused, the `extra` addend of the input gradient), tail() the output side (out(),
+// b3_rows_scale, the target of a fused low-resolution gradient).  Sized once in declare(): the layers register pointers into Net::convs / bns.
+struct Chain {
+    std::vector<Residual> m;
+    Residual& head() { return m.front(); }
+    Residual& tail() { return m.back(); }
+    const Residual& tail() const { return m.back(); }
+    const Act& out() const { return m.back().x3; }
+    const Act& tail_in(const Act& in) const { return m.size() > 1 ? m[m.size() - 2].x3 : in; }      // what the last block reads
+    void declare(Net& n, const std::string& site_prefix, int chan, int modules);      // "<site_prefix><j>." per block
+    void layout(Net& n, Arena& a, int B, int H, int W, bool need_grad, int tail_b3_rows_scale = 1);
+    int fwd(Net& n, const Act& in);
+    // precondition as Residual::bwd, on the last block.  bwd_a: everything except the first block's input gradient; bwd_b: that gradient
+    int bwd_a(Net& n, const Act& in);
+    int bwd_b(Net& n, const Act& in, const PaOperand& extra) { return m.front().bwd_b(n, in, extra); }
+    int bwd(Net& n, const Act& in, const PaOperand& extra, bool in_needs_grad);
+};
+
 struct Hourglass {
-    Residual down[4], up[4], skip[4], neck;
+    Chain down[4], up[4], skip[4], neck;
     Act pooled[4], merged[4];     // pool outputs p_k (k=1..4), upsample-add outputs o_k
     Act skipm[4], neckm;          // occlusion branch only: skip / neck outputs times the 4x4 cell mask (reference :79-100)
     bf16* poolgrad[4] = {nullptr, nullptr, nullptr, nullptr};   // gradient of the pool routed back to its input
@@ -127,7 +147,7 @@ struct Hourglass {
 
 struct Net {
     // configuration
-    int stacks = 2, chan = 256, classes = 16, B = 0, res = 256;
+    int stacks = 2, modules = 1, chan = 256, classes = 16, B = 0, res = 256;
     bool is_agent = false;
     // tables
     std::vector<TensorInfo> tensors;           // state_dict order
@@ -197,7 +217,7 @@ struct Net {
     ConvLayer stem_conv; BNLayer stem_bn;
     Residual res1, res2, res3;
     std::vector<Hourglass> hg;
-    std::vector<Residual> post;
+    std::vector<Chain> post;
     std::vector<ConvLayer> lin; std::vector<BNLayer> lin_bn;
     std::vector<ConvLayer> outc, forth, inc;
     bf16* img4 = nullptr;
@@ -259,6 +279,7 @@ struct Net {
     int finish_grad_or_defer(const Act& a, bool defer);
     int finish_grad2_or_defer(const Act& a, bool defer_a, const Act& b, bool defer_b);
     bool x3_fin_ok(const Residual& r, const Act& in) const;     // can r.x3's backward finalize ride in conv3's data gradient?
+    bool x3_fin_ok(const Chain& c, const Act& in) const { return x3_fin_ok(c.tail(), c.tail_in(in)); }      // the same for a chain's output
     int conv_wgrad(ConvLayer& c, const PaOperand& dy, const PaOperand& x, int B, int H, int W);
 
     int prepare_weights();

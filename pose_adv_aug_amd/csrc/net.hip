@@ -71,15 +71,20 @@ void Residual::declare(Net& n, const std::string& p, int cin_, int cout_, bool a
     if (adapter) n.declare_conv(ad, p + "adapter", cin, cout, 1, true);     // feeds bn3: bias gradient is zero
 }
 
+void Chain::declare(Net& n, const std::string& p, int chan, int modules) {
+    m.resize(modules);                     // before the first block registers its layers: nothing moves afterwards
+    for (int j = 0; j < modules; ++j) m[j].declare(n, p + std::to_string(j) + ".", chan, chan, false);
+}
+
 void Hourglass::declare(Net& n, const std::string& p, int chan) {
-    // registration order of the reference (:56-68); num_modules == 1 => "<site>.0."
-    const char* dn[4] = {"down1", "down2", "down3", "down4"};
-    const char* un[4] = {"up1", "up2", "up3", "up4"};
-    const char* sn[4] = {"skip1", "skip2", "skip3", "skip4"};
-    for (int k = 0; k < 4; ++k) down[k].declare(n, p + dn[k] + ".0.", chan, chan, false);
-    for (int k = 0; k < 4; ++k) up[k].declare(n, p + un[k] + ".0.", chan, chan, false);
-    for (int k = 0; k < 4; ++k) skip[k].declare(n, p + sn[k] + ".0.", chan, chan, false);
-    neck.declare(n, p + "neck.0.", chan, chan, false);
+    // registration order of the reference (:56-68): "<site>.<j>." for the num_modules blocks of a site
+    const char* dn[4] = {"down1.", "down2.", "down3.", "down4."};
+    const char* un[4] = {"up1.", "up2.", "up3.", "up4."};
+    const char* sn[4] = {"skip1.", "skip2.", "skip3.", "skip4."};
+    for (int k = 0; k < 4; ++k) down[k].declare(n, p + dn[k], chan, n.modules);
+    for (int k = 0; k < 4; ++k) up[k].declare(n, p + un[k], chan, n.modules);
+    for (int k = 0; k < 4; ++k) skip[k].declare(n, p + sn[k], chan, n.modules);
+    neck.declare(n, p + "neck.", chan, n.modules);
 }
 
 void Net::declare_pose() {
@@ -92,7 +97,7 @@ void Net::declare_pose() {
     forth.resize(stacks > 0 ? stacks - 1 : 0); inc.resize(stacks > 0 ? stacks - 1 : 0);
     char buf[64];
     for (int i = 0; i < stacks; ++i) { snprintf(buf, sizeof buf, "hg.%d.", i); hg[i].declare(*this, buf, chan); }
-    for (int i = 0; i < stacks; ++i) { snprintf(buf, sizeof buf, "post_res.%d.0.", i); post[i].declare(*this, buf, chan, chan, false); }
+    for (int i = 0; i < stacks; ++i) { snprintf(buf, sizeof buf, "post_res.%d.", i); post[i].declare(*this, buf, chan, modules); }
     for (int i = 0; i < stacks; ++i) {
         snprintf(buf, sizeof buf, "linear.%d.0", i); declare_conv(lin[i], buf, chan, chan, 1, true);
         snprintf(buf, sizeof buf, "linear.%d.1", i); declare_bn(lin_bn[i], buf, chan);
@@ -155,8 +160,13 @@ void Residual::layout(Net& n, Arena& a, int B, int H, int W, bool need_grad) {
     }
 }
 
+void Chain::layout(Net& n, Arena& a, int B, int H, int W, bool need_grad, int tail_b3_rows_scale) {
+    tail().b3_rows_scale = tail_b3_rows_scale;
+    for (Residual& r : m) r.layout(n, a, B, H, W, need_grad);
+}
+
 void Hourglass::layout(Net& n, Arena& a, int B, int H, int W, bool need_grad) {
-    const int C = neck.cout;
+    const int C = n.chan;
     for (int k = 0; k < 4; ++k) {
         skip[k].layout(n, a, B, H >> k, W >> k, need_grad);
         pooled[k] = n.new_act(a, B, H >> (k + 1), W >> (k + 1), C, nullptr, need_grad);
@@ -165,8 +175,8 @@ void Hourglass::layout(Net& n, Arena& a, int B, int H, int W, bool need_grad) {
     }
     neck.layout(n, a, B, H >> 4, W >> 4, need_grad);
     for (int k = 3; k >= 0; --k) {
-        up[k].b3_rows_scale = 4;          // (its backward reductions can come from the data gradient over merged[k], 4 x the pixels: Residual::low_of_in)
-        up[k].layout(n, a, B, H >> (k + 1), W >> (k + 1), need_grad);
+        // (the backward reductions of its last block can come from the data gradient over merged[k], 4 x the pixels: Residual::low_of_in)
+        up[k].layout(n, a, B, H >> (k + 1), W >> (k + 1), need_grad, 4);
         merged[k] = n.new_act(a, B, H >> k, W >> k, C, nullptr, need_grad);
     }
     for (int k = 0; k < 4; ++k) skipm[k] = n.new_act(a, B, H >> k, W >> k, C, nullptr, need_grad);
@@ -691,6 +701,29 @@ int Residual::bwd(Net& n, const Act& in, const PaOperand& extra, bool in_needs_g
 }
 
 // ------------------------------------------------------------------------------------------------
+// chain of residual blocks: the launches the stem chains (residual2 -> residual3) and the hourglass chains (down4 -> neck)
+int Chain::fwd(Net& n, const Act& in) {
+    const Act* cur = &in;
+    for (Residual& r : m) { TRY(r.fwd(n, *cur)); cur = &r.x3; }
+    return 0;
+}
+
+// from the last block to the first; every block flushes its own weight gradients (Residual::bwd_a)
+int Chain::bwd_a(Net& n, const Act& in) {
+    for (int j = (int)m.size() - 1; j >= 1; --j) {
+        const Act& bin = m[j - 1].x3;
+        TRY(m[j].bwd(n, bin, pa_none(), true));
+        TRY(n.finish_grad_or_defer(bin, n.x3_fin_ok(m[j - 1], j >= 2 ? m[j - 2].x3 : in)));
+    }
+    return m[0].bwd_a(n, in);
+}
+
+int Chain::bwd(Net& n, const Act& in, const PaOperand& extra, bool in_needs_grad) {
+    TRY(bwd_a(n, in));
+    return in_needs_grad ? bwd_b(n, in, extra) : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // hourglass (reference :139-157 down path, :192-203 up path)
 // The skip branch of level k (a full-resolution residual block) does not depend on the low-resolution path
 // below it: it is enqueued on the side stream and joined where its result is consumed.
@@ -700,7 +733,7 @@ int Hourglass::encode(Net& n, const Act& in) {
     for (int k = 0; k < 4; ++k) {
         auto skip_branch = [&]() -> int {
             TRY(skip[k].fwd(n, *cur));
-            if (n.drop_mask) TRY(pa_launch_cell_mask(n.op(skip[k].x3), n.drop_mask, ep_plain(), skipm[k].raw, cur->B, cur->H, cur->W, cur->C, n.st));
+            if (n.drop_mask) TRY(pa_launch_cell_mask(n.op(skip[k].out()), n.drop_mask, ep_plain(), skipm[k].raw, cur->B, cur->H, cur->W, cur->C, n.st));
             return 0;
         };
         if (n.multi_stream) {
@@ -712,23 +745,23 @@ int Hourglass::encode(Net& n, const Act& in) {
         }
         TRY(c_maxpool_fwd(n, n.op(*cur), pooled[k].raw, cur->B, cur->H, cur->W, cur->C, n.st));
         TRY(down[k].fwd(n, pooled[k]));
-        cur = &down[k].x3;
+        cur = &down[k].out();
     }
     TRY(neck.fwd(n, *cur));
     if (n.drop_mask) {
-        const Act& x = neck.x3;
+        const Act& x = neck.out();
         TRY(pa_launch_cell_mask(n.op(x), n.drop_mask, ep_plain(), neckm.raw, x.B, x.H, x.W, x.C, n.st));
     }
     return 0;
 }
 
 int Hourglass::decode(Net& n) {
-    const Act* low = n.drop_mask ? &neckm : &neck.x3;
+    const Act* low = n.drop_mask ? &neckm : &neck.out();
     for (int k = 3; k >= 0; --k) {
         TRY(up[k].fwd(n, *low));
         const Act& m = merged[k];
         if (n.multi_stream) TRY(n.wait_join(k));
-        TRY(c_upadd_fwd(n, n.op(up[k].x3), n.op(n.drop_mask ? skipm[k] : skip[k].x3), m.raw, m.B, m.H, m.W, m.C, n.st));
+        TRY(c_upadd_fwd(n, n.op(up[k].out()), n.op(n.drop_mask ? skipm[k] : skip[k].out()), m.raw, m.B, m.H, m.W, m.C, n.st));
         low = &merged[k];
     }
     return 0;
@@ -737,69 +770,74 @@ int Hourglass::decode(Net& n) {
 bool Hourglass::low_fusable(const Net& n, int k) const {
     if (n.drop_mask || k < 0 || k > 3) return false;
     const Act& m = merged[k];
-    return pa_upadd_bwd_splits(n.final_ep(up[k].x3), n.final_ep(skip[k].x3), m.B, m.H, m.W, m.C);
+    return pa_upadd_bwd_splits(n.final_ep(up[k].out()), n.final_ep(skip[k].out()), m.B, m.H, m.W, m.C);
 }
 
 // precondition: merged[0].grad holds the finished (plain) gradient of the hourglass output.
 // extra0: gradient reaching the hourglass INPUT from consumers outside the hourglass.
+// Chains (num_modules > 1): merged[k] is read by the FIRST block of up[k-1] (its conv1 data gradient may emit d up[k].out() too: low_of_in /
+// low_fused sit on head()), the upsample-add and the pool write the gradient of the LAST block of up[k] / skip[k] / down[k] (out()).  Of a skip
+// chain only the first block's input gradient needs poolgrad[k]: everything else of the chain stays on the side stream (Chain::bwd_a).
 int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
     for (int k = 0; k < 4; ++k) {
         const Act& m = merged[k];
+        const Act& upo = up[k].out();
+        const Act& sko = skip[k].out();
         // the two outputs of the upsample-add backward as two launches: d low on the main chain (the low-resolution path waits for it), d skip
         // on the side stream in front of the skip block's backward pass, its only reader -- the main chain waits for 75 MB instead of 175
-        if (pa_tuning().upadd_split && !n.drop_mask && n.multi_stream && pa_upadd_bwd_splits(n.final_ep(up[k].x3), n.final_ep(skip[k].x3), m.B, m.H, m.W, m.C)) {
-            const Act& upin_ = (k == 3) ? neck.x3 : merged[k + 1];
-            const Act& x = (k == 0) ? in : down[k - 1].x3;
+        if (pa_tuning().upadd_split && !n.drop_mask && n.multi_stream && pa_upadd_bwd_splits(n.final_ep(upo), n.final_ep(sko), m.B, m.H, m.W, m.C)) {
+            const Act& upin_ = (k == 3) ? neck.out() : merged[k + 1];
+            const Act& x = (k == 0) ? in : down[k - 1].out();
             TRY(n.fork_to(k));
             {
                 StreamScope sc(n, n.side);
-                TRY(c_upadd_bwd(n, m.grad, n.final_ep(up[k].x3), up[k].x3.grad, n.final_ep(skip[k].x3), skip[k].x3.grad, m.B, m.H, m.W, m.C, n.st, nullptr, 2));
-                TRY(n.finish_grad_or_defer(skip[k].x3, n.x3_fin_ok(skip[k], x)));
+                TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad, m.B, m.H, m.W, m.C, n.st, nullptr, 2));
+                TRY(n.finish_grad_or_defer(sko, n.x3_fin_ok(skip[k], x)));
                 TRY(skip[k].bwd_a(n, x));
             }
             TRY(n.record_join(k));
-            // (d up[k].x3 may have come out of the data gradient that produced d merged[k]: low_done)
-            if (!low_done[k]) TRY(c_upadd_bwd(n, m.grad, n.final_ep(up[k].x3), up[k].x3.grad, n.final_ep(skip[k].x3), skip[k].x3.grad, m.B, m.H, m.W, m.C, n.st, nullptr, 1));
-            TRY(n.finish_grad_or_defer(up[k].x3, n.x3_fin_ok(up[k], upin_)));
-            up[k].low_of_in = low_fusable(n, k + 1) ? &up[k + 1].x3 : nullptr;
+            // (d up[k].out() may have come out of the data gradient that produced d merged[k]: low_done)
+            if (!low_done[k]) TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad, m.B, m.H, m.W, m.C, n.st, nullptr, 1));
+            TRY(n.finish_grad_or_defer(upo, n.x3_fin_ok(up[k], upin_)));
+            up[k].head().low_of_in = low_fusable(n, k + 1) ? &up[k + 1].out() : nullptr;
             TRY(up[k].bwd(n, upin_, pa_none(), true));
-            if (k < 3) low_done[k + 1] = up[k].low_fused;
+            if (k < 3) low_done[k + 1] = up[k].head().low_fused;
             continue;
         }
         if (n.drop_mask) {              // the skip tensor entered the sum through the cell mask: d skip = mask * d (masked skip)
-            TRY(c_upadd_bwd(n, m.grad, n.final_ep(up[k].x3), up[k].x3.grad, ep_plain(), skipm[k].grad, m.B, m.H, m.W, m.C, n.st));
-            TRY(pa_launch_cell_mask(pa_plain(skipm[k].grad), n.drop_mask, n.final_ep(skip[k].x3), skip[k].x3.grad, m.B, m.H, m.W, m.C, n.st));
+            TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, ep_plain(), skipm[k].grad, m.B, m.H, m.W, m.C, n.st));
+            TRY(pa_launch_cell_mask(pa_plain(skipm[k].grad), n.drop_mask, n.final_ep(sko), sko.grad, m.B, m.H, m.W, m.C, n.st));
         } else {
             // (low_done: only d skip is left -- the launch that can do one half exists wherever the fused data gradient does)
-            TRY(c_upadd_bwd(n, m.grad, n.final_ep(up[k].x3), up[k].x3.grad, n.final_ep(skip[k].x3), skip[k].x3.grad,
+            TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad,
                                     m.B, m.H, m.W, m.C, n.st, nullptr, low_done[k] ? 2 : 3));
         }
         {
-            const Act& upin_ = (k == 3) ? (n.drop_mask ? neckm : neck.x3) : merged[k + 1];
-            const Act& skin_ = (k == 0) ? in : down[k - 1].x3;
-            TRY(n.finish_grad2_or_defer(up[k].x3, n.x3_fin_ok(up[k], upin_), skip[k].x3, n.x3_fin_ok(skip[k], skin_)));
+            const Act& upin_ = (k == 3) ? (n.drop_mask ? neckm : neck.out()) : merged[k + 1];
+            const Act& skin_ = (k == 0) ? in : down[k - 1].out();
+            TRY(n.finish_grad2_or_defer(upo, n.x3_fin_ok(up[k], upin_), sko, n.x3_fin_ok(skip[k], skin_)));
         }
-        if (n.multi_stream) {          // parameter / inner gradients of the skip block next to the deeper levels
-            const Act& x = (k == 0) ? in : down[k - 1].x3;
+        if (n.multi_stream) {          // parameter / inner gradients of the skip chain next to the deeper levels
+            const Act& x = (k == 0) ? in : down[k - 1].out();
             TRY(n.fork_to(k));
             { StreamScope sc(n, n.side); TRY(skip[k].bwd_a(n, x)); }
             TRY(n.record_join(k));
         }
-        const Act& upin = (k == 3) ? (n.drop_mask ? neckm : neck.x3) : merged[k + 1];
-        up[k].low_of_in = low_fusable(n, k + 1) ? &up[k + 1].x3 : nullptr;
+        const Act& upin = (k == 3) ? (n.drop_mask ? neckm : neck.out()) : merged[k + 1];
+        up[k].head().low_of_in = low_fusable(n, k + 1) ? &up[k + 1].out() : nullptr;
         TRY(up[k].bwd(n, upin, pa_none(), true));
-        if (k < 3) low_done[k + 1] = up[k].low_fused;
+        if (k < 3) low_done[k + 1] = up[k].head().low_fused;
     }
     if (n.drop_mask) {
-        const Act& x = neck.x3;
+        const Act& x = neck.out();
         TRY(pa_launch_cell_mask(pa_plain(neckm.grad), n.drop_mask, n.final_ep(x), x.grad, x.B, x.H, x.W, x.C, n.st));
     }
-    TRY(n.finish_grad_or_defer(neck.x3, n.x3_fin_ok(neck, down[3].x3)));
-    TRY(neck.bwd(n, down[3].x3, pa_none(), true));
-    TRY(n.finish_grad_or_defer(down[3].x3, n.x3_fin_ok(down[3], pooled[3])));
+    TRY(n.finish_grad_or_defer(neck.out(), n.x3_fin_ok(neck, down[3].out())));
+    TRY(neck.bwd(n, down[3].out(), pa_none(), true));
+    TRY(n.finish_grad_or_defer(down[3].out(), n.x3_fin_ok(down[3], pooled[3])));
     for (int k = 3; k >= 0; --k) {
         TRY(down[k].bwd(n, pooled[k], pa_none(), true));
-        const Act& x = (k == 0) ? in : down[k - 1].x3;
+        const Act& x = (k == 0) ? in : down[k - 1].out();
         TRY(c_maxpool_bwd(n, pooled[k].grad, n.op(x), (k == 0) ? extra0 : pa_none(), ep_plain(), poolgrad[k],
                                   x.B, x.H, x.W, x.C, n.st));
         if (n.multi_stream) {
@@ -808,7 +846,7 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
         } else {
             TRY(skip[k].bwd(n, x, pa_plain(poolgrad[k]), true));
         }
-        if (k >= 1) TRY(n.finish_grad_or_defer(x, n.x3_fin_ok(down[k - 1], pooled[k - 1])));      // x = down[k-1].x3: read next by down[k-1]'s backward pass
+        if (k >= 1) TRY(n.finish_grad_or_defer(x, n.x3_fin_ok(down[k - 1], pooled[k - 1])));      // x = down[k-1].out(): read next by down[k-1]'s backward pass
         else TRY(n.finish_grad(x));
     }
     return 0;
@@ -927,7 +965,7 @@ int Net::forward_pose_body(const float* img_nchw, const bf16* img4_in, const dou
         TRY(hg[i].encode(*this, xin[i]));
         TRY(hg[i].decode(*this));
         TRY(post[i].fwd(*this, hg[i].out()));
-        TRY(conv_fwd(lin[i], op(post[i].x3), B, Hh, Hh, pa_none(), pa_none(), lin_out[i].raw, &lin_bn[i]));
+        TRY(conv_fwd(lin[i], op(post[i].out()), B, Hh, Hh, pa_none(), pa_none(), lin_out[i].raw, &lin_bn[i]));
         TRY(c_head_fwd(*this, op(lin_out[i]), outc[i].wf, params + outc[i].p_b, heat[i], heat64[i], pts ? pts_dev : nullptr,
                                pts ? loss_dev + i : nullptr, B, Hh, Hh, chan, st));
         if (i + 1 < stacks) {
@@ -963,13 +1001,13 @@ int Net::backward_stack(int i) {
     TRY(finish_grad(lin_out[i]));
     PaOperand gl = gradop(lin_out[i]);
     bool gl_stored = false;                  // lgrad_tmp[i] is free again: the data gradient stores dz there for the weight gradient
-    TRY(conv_dgrad(lin[i], gl, B, Hh, Hh, pa_none(), pa_none(), final_ep(post[i].x3), post[i].x3.grad, lgrad_tmp[i], &gl_stored));
+    TRY(conv_dgrad(lin[i], gl, B, Hh, Hh, pa_none(), pa_none(), final_ep(post[i].out()), post[i].out().grad, lgrad_tmp[i], &gl_stored));
     if (gl_stored) gl = pa_plain(lgrad_tmp[i]);
-    TRY(conv_wgrad(lin[i], gl, op(post[i].x3), B, Hh, Hh));
-    TRY(finish_grad(post[i].x3));
-    post[i].low_of_in = hg[i].low_fusable(*this, 0) ? &hg[i].up[0].x3 : nullptr;          // (post_res reads merged[0]: its conv1 data gradient can emit d up1 too)
+    TRY(conv_wgrad(lin[i], gl, op(post[i].out()), B, Hh, Hh));
+    TRY(finish_grad(post[i].out()));
+    post[i].head().low_of_in = hg[i].low_fusable(*this, 0) ? &hg[i].up[0].out() : nullptr;          // (post_res reads merged[0]: its conv1 data gradient can emit d up1 too)
     TRY(post[i].bwd(*this, hg[i].out(), pa_none(), true));
-    hg[i].low_done[0] = post[i].low_fused;
+    hg[i].low_done[0] = post[i].head().low_fused;
     TRY(hg[i].bwd(*this, xin[i], inner ? pa_plain(xin[i + 1].grad) : pa_none()));
     return 0;
 }

@@ -173,7 +173,7 @@ def main(argv=None):
     vis = Visualizer(opt, log_path=(joint_dir + '/' + ('train-log.txt' if opt.is_train else 'val-log.txt')) if rank == 0 else None)
     log = (lambda m: (print(m), vis.write_log(m))) if rank == 0 else (lambda m: None)
 
-    hg = create_hg(num_stacks=2, num_modules=1, num_classes=16, chan=256, default_batch=opt.bs)          # :61-62
+    hg = create_hg(num_stacks=2, num_modules=opt.num_modules, num_classes=16, chan=256, default_batch=opt.bs)          # :61-62
     optimizer_hg = RMSprop(hg, lr=opt.lr, alpha=0.99, eps=1e-8)
     train_history_pose, checkpoint_hg = PoseTrainHistory(), Checkpoint()
     if opt.load_checkpoint:                                                                   # resume the joint stage (:72-74)

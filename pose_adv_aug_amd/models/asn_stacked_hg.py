@@ -194,14 +194,17 @@ class HourglassNet(_HipModule):
 
     def __init__(self, num_modules, num_stacks, chan=256, num_classes=16, res=256, default_batch=24):
         super().__init__()
-        if num_modules != 1:
-            raise ValueError('the reference scripts always use num_modules=1; that is what the engine builds')
+        if int(num_modules) != num_modules or not 1 <= num_modules <= 8:
+            raise ValueError('num_modules must be an integer from 1 to 8 (residual blocks per site), got %r' % (num_modules,))
+        self.num_modules = int(num_modules)
         self.num_stacks, self.chan, self.num_classes, self.res = num_stacks, chan, num_classes, res
         self.default_batch = default_batch
         self._last_B = None
 
     def _create(self, B):
-        return lib().pa_hg_create(self.num_stacks, self.num_classes, self.chan, B, self.res)
+        if self.num_modules == 1:
+            return lib().pa_hg_create(self.num_stacks, self.num_classes, self.chan, B, self.res)
+        return lib().pa_hg_create_modules(self.num_stacks, self.num_modules, self.num_classes, self.chan, B, self.res)
 
     def forward(self, x=None, asn=None, is_half_hg=False, is_aug=False, is_dropout=False, img4=None, pts=None,
                 dropout_masks=None, seed=0):

@@ -31,6 +31,8 @@ class BaseOptions(object):
         # (not a flag of the reference) 1: crops reproduce scipy's toimage() min/max byte stretch, as the reference's host pipeline
         # does for training and validation alike; 0 (default): the frame is scaled by its full range
         p.add_argument('--crop_stretch', type=int, default=0, help='1: reproduce scipy toimage() min/max byte stretching in the crop')
+        # (not a flag of the reference, whose scripts hard-wire 1) residual blocks per site of the pose net: create_hg's num_modules
+        p.add_argument('--num_modules', type=int, default=1, help='residual blocks per hourglass site / post_res (1..8)')
         self.initialized = True
 
     @staticmethod

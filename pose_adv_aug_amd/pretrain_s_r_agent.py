@@ -147,7 +147,7 @@ def main(argv=None):
     exp = os.path.join(opt.exp_dir, opt.exp_id)
     sr_dir = os.path.join(exp, opt.sr_dir + '-' + opt.load_prefix_pose[0:-1]) if opt.load_prefix_pose != '' else os.path.join(exp, opt.sr_dir)
     os.makedirs(sr_dir, exist_ok=True)
-    hg = create_hg(num_stacks=2, num_modules=1, num_classes=16, chan=256, default_batch=opt.bs)
+    hg = create_hg(num_stacks=2, num_modules=opt.num_modules, num_classes=16, chan=256, default_batch=opt.bs)
     if opt.load_prefix_pose != '':
         ck = Checkpoint(); ck.load_prefix = os.path.join(exp, opt.load_prefix_pose)[0:-1]
         ck.load_checkpoint(hg)

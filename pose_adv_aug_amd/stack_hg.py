@@ -189,7 +189,7 @@ def main(argv=None):
     from .utils.visualizer import Visualizer
     opt = TrainOptions().parse(argv)
     rank, world, _ = init_distributed()
-    net = create_hg(num_stacks=2, num_modules=1, num_classes=16, chan=256, default_batch=opt.bs)     # stack-hg.py:40-41
+    net = create_hg(num_stacks=2, num_modules=opt.num_modules, num_classes=16, chan=256, default_batch=opt.bs)     # stack-hg.py:40-41
     optimizer = RMSprop(net, lr=opt.lr, alpha=0.99, eps=1e-8)
     history, ckpt = PoseTrainHistory(), Checkpoint()
     exp_dir = os.path.join(opt.exp_dir, opt.exp_id)
