@@ -51,6 +51,14 @@ int pa_get_preds(const float* maps, int B, int J, int H, int W, float* preds, fl
 int pa_final_preds(const float* maps, const float* center, const float* scale, const float* rot,
                    int B, int J, int H, int W, float* out, float* scratch_preds, void* stream);
 
+/* The same two operations on joint-minor maps [B][H*W][J] fp32 -- the layout of the engine's own heat maps
+ * (pa_hg_heatmap_nhwc), which pa_hg_accuracy / pa_hg_pckh read in place.  With J = 16 and a 16-byte-aligned `maps`
+ * the arg-max is the one-workgroup-per-sample kernel those two use; any other J or alignment takes the generic
+ * kernel with a stride of J floats between pixels. */
+int pa_get_preds_nhwc(const float* maps, int B, int J, int H, int W, float* preds, float* maxval, void* stream);
+int pa_final_preds_nhwc(const float* maps, const float* center, const float* scale, const float* rot,
+                        int B, int J, int H, int W, float* out, float* scratch_preds, void* stream);
+
 /* PCK from point sets: Evaluation.calc_dists/dist_acc/accuracy (pylib/Evaluation.py:25-75; boundary
  * 1), accuracy_origin_res (:77-97; boundary 0), per_person_pckh (:99-167; `person` output with the
  * visibility points `vis`), HumanAcc.approx_PCKh (pylib/HumanAcc.py:7-44; boundary 0, norm = res/10

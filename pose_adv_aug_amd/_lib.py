@@ -70,6 +70,8 @@ _PROTOS = {
     'pa_weighted_l2': (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     'pa_get_preds': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'pa_final_preds': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'pa_get_preds_nhwc': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'pa_final_preds_nhwc': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'pa_pck': (_i, [_vp, _vp, _vp, _f, _vp, _i, _f, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'pa_affine_params': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     'pa_transform_pts': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),

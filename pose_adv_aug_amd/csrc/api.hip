@@ -38,6 +38,16 @@ int pa_final_preds(const float* maps, const float* center, const float* scale, c
     TRY(pa_launch_final_preds(maps, (long)J * H * W, (long)H * W, 1, scratch_preds, center, scale, rot, B, J, H, W, out, ST(s)));
     return 0;
 }
+// joint-minor maps [B][H*W][J]: the strides Net::heat_argmax and pa_hg_pckh use on the engine's own heat maps
+int pa_get_preds_nhwc(const float* maps, int B, int J, int H, int W, float* preds, float* maxval, void* s) {
+    TRY(pa_launch_argmax(maps, (long)H * W * J, 1, J, B, J, H, W, preds, maxval, ST(s))); return 0;
+}
+int pa_final_preds_nhwc(const float* maps, const float* center, const float* scale, const float* rot, int B, int J, int H, int W,
+                        float* out, float* scratch_preds, void* s) {
+    TRY(pa_launch_argmax(maps, (long)H * W * J, 1, J, B, J, H, W, scratch_preds, nullptr, ST(s)));
+    TRY(pa_launch_final_preds(maps, (long)H * W * J, 1, J, scratch_preds, center, scale, rot, B, J, H, W, out, ST(s)));
+    return 0;
+}
 int pa_pck(const float* pred, const float* gt, const float* norm, float boundary, const int32_t* idxs, int nidx, float thr,
            const float* vis, int B, int J, float* acc, float* person, float* dists, void* s) {
     TRY(pa_launch_pck(pred, gt, norm, boundary, idxs, nidx, thr, vis, B, J, acc, person, dists, ST(s))); return 0;
