@@ -411,6 +411,13 @@ int pa_net_profile_classes(const pa_net* net, int32_t* out_host, int cap);
  * consumer convolution computes scale / shift (forward) or the BatchNorm-backward coefficients (backward) in its own prologue instead
  * of a finalize launch in front of it; 0 = always a launch.  Results are bit-identical either way (one summation order). */
 int pa_net_set_fin_prologue(pa_net* net, int max_rows);
+/* Gradient of the hourglass max pools (models/asn_stacked_hg.py:69): on (default) = the forward pool also stores a one-byte arg-max map per
+ * pooled element and the data gradient of the skip branch beside the pool reads the pool's gradient through that map in its epilogue --
+ * no pool backward launch and no full-resolution routed tensor, wherever the skip block's kernel has an instance for it; the stem's pool
+ * likewise (its forward also stores the value at the arg-max: the pool's BatchNorm-backward reductions come from a quarter-size launch, the
+ * routed gradient is formed on load by residual1's conv3 data gradient); off (0) = a pool backward launch per pool.  Results are
+ * bit-identical either way.  Takes effect with the next forward pass. */
+int pa_net_set_pool_route(pa_net* net, int on);
 /* Bytes THIS design moves per step, from the engine's own launch table (bench.py's `roofline.design_bytes_per_step`): every operand
  * a launch of the last forward + backward pass reads or writes, counted once per launch at its storage width -- activations, the
  * second operand of a BatchNorm-backward load, reference tensors of the masked epilogues, shortcut addends, stored dz tensors, fp32
@@ -456,7 +463,9 @@ int pa_net_set_multi_stream(pa_net* net, int on);
  * in_conv, 64 channels of which 16..63 are zero; its gradient: d heat as stored for out_conv's weight gradient), "heat<i>.in"
  * (in_conv's data gradient, 64 channels, no gradient) and "forth<i>" (forth_conv's stored output forth_conv(lin) + xin, no gradient)
  * for the head layers between stacks i and i + 1; "hg<i>.poolgrad<k>" (no gradient): the gradient max pool k routes back to its
- * input, plus for k = 1 the gradient reaching the hourglass input from the next stack, as skip k's conv1 data gradient adds it. */
+ * input, plus for k = 1 the gradient reaching the hourglass input from the next stack, as skip k's conv1 data gradient adds it.  With
+ * pool routing (pa_net_set_pool_route) the step does not store this tensor: asking for it runs the pool backward launch into its buffer
+ * first, from the operands of the last step (same bits as a step without routing stores). */
 int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int* shape4);
 
 /* The same hook (and the same views) for the agent: "in<k>" (k = 0..4: residual_skip1-4, residual_neck), "pa<k>", "merge<k>"

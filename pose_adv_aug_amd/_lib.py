@@ -145,6 +145,7 @@ _PROTOS = {
     'pa_copy_probe_form': (_i, [_vp, _vp, _sz, _i, _vp]),
     'pa_params_csr': (_i, [_vp, _i, _vp, _vp]),
     'pa_net_set_fin_prologue': (_i, [_vp, _i]),
+    'pa_net_set_pool_route': (_i, [_vp, _i]),
     'pa_wgrad_group_workspace_bytes': (_sz, [_vp, _i]),
     'pa_wgrad_group': (_i, [_vp, _i, _i, _vp, _vp]),
     'pa_conv2d_time': (_i, [_i] * 9 + [_vp, C.POINTER(C.c_float), _vp]),

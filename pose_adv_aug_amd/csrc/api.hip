@@ -755,6 +755,11 @@ int pa_net_set_fin_prologue(pa_net* net, int max_rows) {
     net->n.release_graph();
     return 0;
 }
+int pa_net_set_pool_route(pa_net* net, int on) {
+    net->n.pool_route = on ? 3 : 0;
+    net->n.release_graph();
+    return 0;
+}
 int pa_net_design_bytes(const pa_net* net, double* out) { out[0] = net->n.dbytes_rd; out[1] = net->n.dbytes_wr; return 0; }
 
 int pa_net_profile_classes(const pa_net* net, int32_t* out, int cap) {
@@ -828,7 +833,11 @@ int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int
         const int i = w.size() == 6 ? w[5] - '0' : -1;
         if (i >= 0 && i < (int)n.forth_tmp.size() && n.forth_tmp[i]) { head.raw = n.forth_tmp[i]; head.C = n.chan; a = &head; }
     } else if (starts("stem")) a = &n.a0;
-    else if (starts("res1")) a = pick_res(n.res1, w.substr(4));
+    else if (starts("res1")) {
+        a = pick_res(n.res1, w.substr(4));
+        // (a routed step never wrote residual1's gradient buffer: the pool backward launch runs now, same bits)
+        if (out && a == &n.res1.x3 && (grad == 1 || grad == 3) && n.stem_routed) TRY(n.fill_stem_grad());
+    }
     else if (starts("pool0")) a = &n.pool0;
     else if (starts("res2")) a = pick_res(n.res2, w.substr(4));
     else if (starts("res3")) a = pick_res(n.res3, w.substr(4));
@@ -846,6 +855,9 @@ int pa_hg_debug_tensor(pa_net* net, const char* which, int grad, float* out, int
             const int k = r.size() == 9 ? r[8] - '1' : -1;
             if (k >= 0 && k < 4 && h.poolgrad[k]) {
                 const Act& x = h.skip[k].out();
+                // (a routed level never wrote the buffer: the pool backward launch runs now, from the still-resident gradient of the pooled
+                // tensor, the pool's input and the addend)
+                if (out && h.routed[k]) TRY(h.fill_poolgrad(n, k, n.xin[i]));
                 head.raw = h.poolgrad[k]; head.B = x.B; head.H = x.H; head.W = x.W; head.C = x.C; a = &head;
             }
         } else {

@@ -232,6 +232,7 @@ int Net::forward_half(const float* img_nchw, const bf16* img4_in, bool train) {
     if (!img4_in) TRY(pa_launch_nchw_to_nhwc4(img_nchw, img4, B, res, res, st));
     TRY(conv_fwd(stem_conv, pa_plain(image), B, res / 2, res / 2, pa_none(), pa_none(), a0.raw, &stem_bn));
     TRY(res1.fwd(*this, a0));
+    maps_on = false; stem_map_written = false;      // (no backward pass of the pose net follows half a forward pass: no arg-max maps)
     TRY(pa_launch_maxpool_fwd(op(res1.x3), pool0.raw, B, res / 2, res / 2, 128, st));
     TRY(res2.fwd(*this, pool0));
     TRY(res3.fwd(*this, res2.x3));

@@ -75,7 +75,11 @@ void pa_set_error_msg(const char* msg);
 //   BNRELU: v = max(0, k0[c] * p[i] + k1[c])          (train/eval BatchNorm + ReLU applied on load)
 //   LIN2  : v = k0[c] * p[i] + k1[c] * q[i] + k2[c]    (BatchNorm backward applied on load:
 //                                                       p = masked upstream grad, q = raw conv output)
-enum { PA_LD_NONE = -1, PA_LD_PLAIN = 0, PA_LD_BNRELU = 1, PA_LD_LIN2 = 2 };
+//   POOL  : (second epilogue addend of the 1x1 data gradients that have an instance for it only: pa_conv_pool_route_supported) the gradient
+//           of a 2x2 max pool routed to its arg-max through the byte map the forward pool stored, plus an optional plain addend q:
+//           v = bf16((map[low(i)][c] == pos(i) ? p[low(i)][c] : 0) + q[i])   -- what maxpool_bwd would have stored at i
+//           (p: gradient of the pooled tensor, low(i) the pooled pixel over pixel i, pos(i) = 2 * (row & 1) + (column & 1))
+enum { PA_LD_NONE = -1, PA_LD_PLAIN = 0, PA_LD_BNRELU = 1, PA_LD_LIN2 = 2, PA_LD_POOL = 3 };
 
 struct PaOperand {
     const bf16* p;
@@ -84,6 +88,7 @@ struct PaOperand {
     const float* k1;
     const float* k2;
     int mode;
+    const unsigned char* map;      // POOL: arg-max position (0..3) per element of the pooled tensor
 };
 
 // What the epilogue of a conv / elementwise backward kernel does with its value v:

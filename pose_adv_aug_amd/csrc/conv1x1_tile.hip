@@ -39,7 +39,14 @@ PA_STAMP_DECL(pa_conv1t_clk, pa_debug_conv1t_clocks)
 // what a CU moves is proportional to the chains it interleaves (128-channel instance: 5.4 TB/s hot, the two-workgroup 256-channel one 4.0)
 // UP (round 6; CIN = 128, BM = 64, BN = 128, LIN2): the workgroup's 64 rows are 2 IMAGE ROWS x 32 columns instead of 64 consecutive pixels, and
 // the epilogue is pa_conv_epilogue_lds_up: d(merged) plus the low-resolution half of the upsample-add backward (a.out2 / a.ep2)
-template <int CIN, int BM, int BN, int LDMODE, int KS = 64, bool UP = false>
+// POOL (CIN = 128, BM = 64, BN = 128, LIN2): the instances whose second epilogue addend is pool-routed (PA_LD_POOL, conv_epilogue.h): the first
+// block of a skip branch reads the pool's gradient through the arg-max map instead of a full-resolution tensor.  PA_POOL_EP_BWD / _PLAIN: one
+// per epilogue
+// PIN (CIN = 128, BM = 64, BN = 64, LIN2): the first operand of the BatchNorm-backward load is pool-routed (a.in.mode == PA_LD_POOL): instead of a
+// stored full-resolution dz it is dz = (map[low] == pos && s * q + t > 0) ? g[low] : 0 -- the gradient g of a 2x2 max pool through the pool's
+// arg-max map, masked by the ReLU of the pooled tensor q (a.ep2.scale / shift: the epilogue the pool backward launch would have applied; its
+// reductions come from maxpool_bwd_stats_kernel).  The transformed tile goes to dz_out as in every LIN2 instance.
+template <int CIN, int BM, int BN, int LDMODE, int KS = 64, bool UP = false, int POOL = PA_POOL_EP_NONE, bool PIN = false>
 __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CIN == 64 && (BN == 64 || BM == 64))) ? PA_CONV1_UP_OCC(UP) : 2) void conv1x1_tile_kernel(PaConvArgs a, int nb_per_wg) {
     constexpr int CPP = CIN / 8;                     // 16-byte chunks per pixel row
     constexpr int NI = BN / 32, MI = BM / 32;
@@ -112,14 +119,29 @@ __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CI
                 if (LDMODE == PA_LD_LIN2) k2[j] = a.in.k2[c + j];
             }
         }
+        float ps[PIN ? 8 : 1], pt[PIN ? 8 : 1];
+        if constexpr (PIN) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { ps[j] = a.ep2.scale[c + j]; pt[j] = a.ep2.shift[c + j]; }
+        }
         constexpr int UN = (LDMODE == PA_LD_LIN2 && NPASS > 4) ? NPASS / 2 : NPASS;
 #pragma unroll
         for (int p0 = 0; p0 < NPASS; p0 += UN) {
             bf16x8 ra[UN], rq[UN];
+            uint2 rmp[PIN ? UN : 1];
+            unsigned rpos[PIN ? UN : 1];
 #pragma unroll
             for (int u = 0; u < UN; ++u) {
                 const int m = pixel_of_row((p0 + u) * PSTEP + tid / CPP);
                 const size_t idx = m < M ? (size_t)m * CIN + c : 0;        // clamped, unconditional loads
+                if constexpr (PIN) {
+                    // (H is even: the row pair of a pixel never straddles two images)
+                    const unsigned mm = m < M ? (unsigned)m : 0u, rowg = mm / (unsigned)a.W, x = mm - rowg * (unsigned)a.W;
+                    const size_t lo = (size_t)((rowg >> 1) * ((unsigned)a.W >> 1) + (x >> 1)) * CIN + c;
+                    rpos[u] = ((rowg & 1u) << 1) | (x & 1u);
+                    ra[u] = *reinterpret_cast<const bf16x8*>(a.in.p + lo);
+                    rmp[u] = *reinterpret_cast<const uint2*>(a.in.map + lo);
+                } else
                 ra[u] = *reinterpret_cast<const bf16x8*>(a.in.p + idx);
                 if (LDMODE == PA_LD_LIN2) rq[u] = *reinterpret_cast<const bf16x8*>(a.in.q + idx);
             }
@@ -133,6 +155,15 @@ __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CI
                 } else if (LDMODE == PA_LD_BNRELU) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) o[j] = (bf16)fmaxf(fmaf(k0[j], (float)ra[u][j], k1[j]), 0.f);
+                } else if constexpr (PIN) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const unsigned b = ((j < 4 ? rmp[u].x : rmp[u].y) >> (8 * (j & 3))) & 0xffu;
+                        const float q = (float)rq[u][j];
+                        const float r = (b == rpos[u] ? (float)ra[u][j] : 0.f) + 0.f;            // what the pool backward kernel forms ...
+                        const float dz = (float)(bf16)((fmaf(ps[j], q, pt[j]) > 0.f) ? r : 0.f);  // ... masks and stores
+                        o[j] = (bf16)fmaf(k0[j], dz, fmaf(k1[j], q, k2[j]));
+                    }
                 } else {
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
@@ -210,7 +241,7 @@ __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CI
                                                 [&](int x) { return up_rp * (a.W / 2) + up_cx * (BM / 4) + (x >> 1); },
                                                 T, (int)blockIdx.x, reinterpret_cast<float4*>(lds + BM * CIN + 2 * BN * KS));
         } else
-        pa_conv_epilogue_auto<BN, NI, MI, (CIN == 256 || CIN == 64 || CTAB), CTAB, 256, (BN < 128)>(a, acc, (nb0 + nbi) * BN, wm, wn,
+        pa_conv_epilogue_auto<BN, NI, MI, (CIN == 256 || CIN == 64 || CTAB), CTAB, 256, (BN < 128), POOL>(a, acc, (nb0 + nbi) * BN, wm, wn,
                                          [&](int wr, int mi, int p) { const int m = m0 + wr * (BM / 2) + mi * 16 + p; return m < M ? m : -1; },
                                          T, (int)blockIdx.x, CTAB ? reinterpret_cast<float4*>(lds + BM * CIN + 2 * BN * KS) : nullptr);
         if (nbi == 0) PA_STAMPT(5);                   // its epilogue
@@ -260,7 +291,23 @@ static int launch_conv1x1_tile_up(const PaConvArgs& a, hipStream_t st, int* stat
     return (int)hipGetLastError();
 }
 
+// the POOL instance: 128 -> 128 k channels in 64-row tiles, BatchNorm backward on load, plain output or the LDS BatchNorm-backward epilogue
+static bool tile_pool_ok(const PaConvArgs& a) {
+    return a.Cin == 128 && a.Cout % 128 == 0 && a.in.mode == PA_LD_LIN2 && !a.bias && !a.out2 && a.fin.rows == 0 && a.H % 2 == 0 && a.W % 2 == 0 &&
+           (a.add1.mode == PA_LD_NONE || a.add1.mode == PA_LD_PLAIN || a.add1.mode == PA_LD_LIN2) &&
+           (a.ep.mode == PA_OUT_PLAIN || (a.ep.mode == PA_OUT_BWD && a.xcd < 2));
+}
+
+// the PIN instance: 128 -> 64 channels in 64-row tiles, the transformed tile stored, the table form of the BatchNorm-backward epilogue
+static bool tile_pool_in_ok(const PaConvArgs& a) {
+    return a.Cin == 128 && a.Cout % 64 == 0 && a.Cout % 128 != 0 && a.in.map && a.in.q && a.dz_out && !a.bias && !a.out2 && a.fin.rows == 0 &&
+           a.H % 2 == 0 && a.W % 2 == 0 && a.add1.mode == PA_LD_NONE && a.add2.mode == PA_LD_NONE &&
+           a.ep.mode == PA_OUT_BWD && a.xcd < 2 && a.ep2.scale && a.ep2.shift;
+}
+
 bool pa_conv1x1_tile_supported(const PaConvArgs& a) {
+    if (a.add2.mode == PA_LD_POOL && !tile_pool_ok(a)) return false;
+    if (a.in.mode == PA_LD_POOL && !tile_pool_in_ok(a)) return false;
     if (a.taps != 1 || (a.Cin != 64 && a.Cin != 128 && a.Cin != 256) || a.Cout % 64 != 0) return false;
     const int M = a.B * a.H * a.W;
     if ((size_t)M * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;      // 32-bit element offsets in the epilogue
@@ -280,7 +327,7 @@ int pa_launch_conv1x1_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) 
     // 64 input channels, 128 output channels: 64-row tiles at three workgroups per CU (the 128-row instance spills at 168 registers)
     if (a.Cin == 64 && a.Cout % 128 == 0 && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a))) bm = 64;
     // the 64-row, 128-channel BatchNorm-backward instance (3 workgroups per CU) has the LDS epilogue only
-    if (a.Cin == 128 && bm == 64 && a.in.mode == PA_LD_LIN2 && a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a)) bm = 128;
+    if (a.Cin == 128 && bm == 64 && a.in.mode == PA_LD_LIN2 && a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a) && a.add2.mode != PA_LD_POOL) bm = 128;
     const int tiles = (M + bm - 1) / bm;
     if (stat_rows) *stat_rows = tiles;
     if (a.ep.rows_out) *a.ep.rows_out = tiles;
@@ -290,6 +337,19 @@ int pa_launch_conv1x1_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) 
     dim3 grid(tiles, nb / nbw);
     // 256 channels: the three-workgroup instance (32-channel weight slices) unless the launch needs the direct BatchNorm-backward epilogue
     const bool three = bigN && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a));
+    if (a.in.mode == PA_LD_POOL) {                 // (tile_pool_in_ok: Cin = 128, bm = 64, 64-channel blocks)
+        PaConvArgs b = a;
+        b.dbg = pa_tuning().conv1t_dbg;
+        hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 64, PA_LD_LIN2, 64, false, PA_POOL_EP_NONE, true>), grid, dim3(256), 0, st, b, nbw);
+        return (int)hipGetLastError();
+    }
+    if (a.add2.mode == PA_LD_POOL) {               // (tile_pool_ok: Cin = 128, bm = 64, bigN)
+        PaConvArgs b = a;
+        b.dbg = pa_tuning().conv1t_dbg;
+        if (a.ep.mode == PA_OUT_BWD) hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, false, PA_POOL_EP_BWD>), grid, dim3(256), 0, st, b, nbw);
+        else hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, false, PA_POOL_EP_PLAIN>), grid, dim3(256), 0, st, b, nbw);
+        return (int)hipGetLastError();
+    }
     if (a.Cin == 256) { if (bigN && three) launch_row_ld<256, 64, 128, 32>(a, grid, nbw, st); else if (bigN) launch_row_ld<256, 64, 128>(a, grid, nbw, st); else launch_row_ld<256, 64, 64>(a, grid, nbw, st); }
     else if (a.Cin == 128 && bm == 64) { if (bigN) launch_row_ld<128, 64, 128>(a, grid, nbw, st); else launch_row_ld<128, 64, 64>(a, grid, nbw, st); }
     else if (a.Cin == 128) { if (bigN) launch_row_ld<128, 128, 128, 64, true>(a, grid, nbw, st); else launch_row_ld<128, 128, 64, 64, true>(a, grid, nbw, st); }      // (bm == 128 here: a.in.mode is LIN2)

@@ -202,6 +202,30 @@ __device__ __forceinline__ f32x2 pa_stats_reduce(const float (&s1)[8], const flo
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Pool-routed addend (PA_LD_POOL, second addend of the POOL instances): what maxpool_bwd would have stored at pixel m, from the gradient of
+// the pooled tensor and the arg-max byte map of the forward pool -- one 16-byte and one 8-byte load per 8 channels instead of a
+// full-resolution tensor.  request: everything in flight (m >= 0; H even, so the row pair of a pixel never straddles two images);
+// value: channel j.  Same bits as the stored tensor: the bf16 rounding of (routed gradient + optional plain addend) is redone here.
+enum { PA_POOL_EP_NONE = 0, PA_POOL_EP_BWD = 1, PA_POOL_EP_PLAIN = 2 };      // POOL of the kernels / pa_conv_epilogue_auto: which epilogue the instance carries
+struct PaPoolRaw { bf16x8 g, e; uint2 mp; unsigned pos; };
+__device__ __forceinline__ void pa_pool_request(const PaOperand& o, unsigned m, unsigned W, unsigned N, unsigned n, unsigned idx, PaPoolRaw& r) {
+    // (opaque: the row arithmetic below is the same for every channel block of a workgroup -- hoisted out of that loop it would live in 3
+    // registers per request across the K loop of the 168-register kernels; it is ~15 instructions)
+    asm volatile("" : "+v"(m));
+    const unsigned rowg = m / W, x = m - rowg * W;
+    const unsigned lo = ((rowg >> 1) * (W >> 1) + (x >> 1)) * N + n;
+    r.pos = ((rowg & 1u) << 1) | (x & 1u);
+    r.g = *reinterpret_cast<const bf16x8*>(o.p + lo);
+    r.mp = *reinterpret_cast<const uint2*>(o.map + lo);
+    if (o.q) r.e = *reinterpret_cast<const bf16x8*>(o.q + idx);
+}
+__device__ __forceinline__ float pa_pool_value(const PaPoolRaw& r, bool has_e, int j) {
+    const unsigned b = ((j < 4 ? r.mp.x : r.mp.y) >> (8 * (j & 3))) & 0xffu;
+    const float v = (b == r.pos ? (float)r.g[j] : 0.f) + (has_e ? (float)r.e[j] : 0.f);
+    return (float)(bf16)v;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // LDS-TRANSPOSED epilogue.  The direct epilogue above stores, per instruction, 16-byte pieces that lie 32 bytes apart
 // in 16 different pixel rows: measured on the 3x3 tile kernel (tools/bench_conv3.py ablation) the plain store of a
 // 25 MB output costs 11.6 us = 2.2 TB/s, a third of the kernel.  Here the accumulators go through a 16 KB fp32 LDS
@@ -220,7 +244,8 @@ __device__ __forceinline__ f32x2 pa_stats_reduce(const float (&s1)[8], const flo
 // NT = threads of the workgroup: 256 (2 waves along the pixels: 32-row passes) or 512 (4 waves along the pixels: 64-row passes, T >= 64 * BN floats)
 // FUSE (MI * BN <= 128, i.e. the whole workgroup tile fits the 16 * NT floats the statistics reduction needs anyway): all MI passes are staged at
 // once -- one barrier instead of 2 * MI - 1
-template <int BN, int NI, int MI, int NT = 256, bool TSMALL = false, bool FUSE = false, class PixFn>
+// POOL: the second addend is pool-routed (PA_LD_POOL, pa_pool_request) -- instances of their own
+template <int BN, int NI, int MI, int NT = 256, bool TSMALL = false, bool FUSE = false, bool POOL = false, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
                                                      PixFn pix, float* T, int stat_row) {
     constexpr int CPR = BN / 8;                      // 8-channel chunks per pixel row
@@ -245,6 +270,8 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
     constexpr bool PRE = IT <= 2;
     const int m1 = a.add1.mode, m2 = a.add2.mode;
     bf16x8 p1[PRE ? IT : 1], q1[PRE ? IT : 1], p2[PRE ? IT : 1], q2[PRE ? IT : 1];
+    PaPoolRaw pr[POOL && PRE ? IT : 1];
+    const bool pool_e = POOL && a.add2.q != nullptr;
     float ka1[8], kb1[8], kc1[8], ka2[8], kb2[8], kc2[8];
     if constexpr (PRE) {
 #pragma unroll
@@ -256,6 +283,7 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
                 const unsigned idx = m < 0 ? 0u : (unsigned)m * (unsigned)N + (unsigned)n;      // clamped, unconditional
                 if (m1 != PA_LD_NONE) p1[it] = *reinterpret_cast<const bf16x8*>(a.add1.p + idx);
                 if (m1 == PA_LD_LIN2) q1[it] = *reinterpret_cast<const bf16x8*>(a.add1.q + idx);
+                if constexpr (POOL) { pa_pool_request(a.add2, m < 0 ? 0u : (unsigned)m, (unsigned)a.W, (unsigned)N, (unsigned)n, idx, pr[it]); continue; }
                 if (m2 != PA_LD_NONE) p2[it] = *reinterpret_cast<const bf16x8*>(a.add2.p + idx);
                 if (m2 == PA_LD_LIN2) q2[it] = *reinterpret_cast<const bf16x8*>(a.add2.q + idx);
             }
@@ -269,7 +297,7 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
                 for (int j = 0; j < 8; ++j) kc1[j] = a.add1.k2[n + j];
             }
         }
-        if (m2 == PA_LD_BNRELU || m2 == PA_LD_LIN2) {
+        if (!POOL && (m2 == PA_LD_BNRELU || m2 == PA_LD_LIN2)) {
             const f32x4 s0 = *reinterpret_cast<const f32x4*>(a.add2.k0 + n), s4 = *reinterpret_cast<const f32x4*>(a.add2.k0 + n + 4);
             const f32x4 t0 = *reinterpret_cast<const f32x4*>(a.add2.k1 + n), t4 = *reinterpret_cast<const f32x4*>(a.add2.k1 + n + 4);
 #pragma unroll
@@ -329,10 +357,22 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
             float e1[8], e2[8];
             if constexpr (PRE) {
                 addend(m1, p1[mi * SW + sw], q1[mi * SW + sw], ka1, kb1, kc1, e1);
+                if constexpr (POOL) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) e2[j] = pa_pool_value(pr[mi * SW + sw], pool_e, j);
+                } else
                 addend(m2, p2[mi * SW + sw], q2[mi * SW + sw], ka2, kb2, kc2, e2);
             } else {
+                if constexpr (POOL) {
+                    PaPoolRaw r;
+                    pa_pool_request(a.add2, (unsigned)m, (unsigned)a.W, (unsigned)N, (unsigned)n, idx, r);
+                    pa_read8(a.add1, idx, n, e1);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) e2[j] = pa_pool_value(r, pool_e, j);
+                } else {
                 pa_read8(a.add1, idx, n, e1);
                 pa_read8(a.add2, idx, n, e2);
+                }
             }
             bf16x8 o;
 #pragma unroll
@@ -362,7 +402,8 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
 // (2) a thread owns the same 8 channels for all its pixels, so the constants live in registers; (3) the second reduction
 // is accumulated as sum(dz * x) and turned into sum(dz * xhat) = invstd * (sum(dz*x) - mean * sum(dz)) once per
 // workgroup row, which removes mean / invstd from the per-element work.
-template <int BN, int NI, int MI, bool TAB, int NT = 256, bool TSMALL = false, bool FUSE = false, class PixFn>
+// POOL: the second addend is pool-routed (PA_LD_POOL, pa_pool_request) instead of plain -- instances of their own
+template <int BN, int NI, int MI, bool TAB, int NT = 256, bool TSMALL = false, bool FUSE = false, bool POOL = false, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue_lds_bwd(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
                                                          PixFn pix, float* T, int stat_row, float4* ctab = nullptr) {
     // ctab (optional, 2 * BN float4 of LDS outside T): the per-channel constants live there instead of in 40 registers
@@ -390,7 +431,9 @@ __device__ __forceinline__ void pa_conv_epilogue_lds_bwd(const PaConvArgs& a, f3
         // ---- request everything the next G passes need
         unsigned idx[IT];                            // 32-bit element offsets (the tile launchers admit M * Cout < 2^31 only)
         bool ok[IT];
-        bf16x8 xr[IT], p1[IT], q1[IT], p2[IT];
+        bf16x8 xr[IT], p1[IT], q1[IT], p2[POOL ? 1 : IT];
+        PaPoolRaw pr[POOL ? IT : 1];
+        const bool pool_e = POOL && a.add2.q != nullptr;
 #pragma unroll
         for (int pp = 0; pp < G; ++pp)
 #pragma unroll
@@ -405,7 +448,8 @@ __device__ __forceinline__ void pa_conv_epilogue_lds_bwd(const PaConvArgs& a, f3
                 xr[it] = *reinterpret_cast<const bf16x8*>(a.ep.xref + idx[it]);
                 if (m1 != PA_LD_NONE) p1[it] = *reinterpret_cast<const bf16x8*>(a.add1.p + idx[it]);
                 if (m1 == PA_LD_LIN2) q1[it] = *reinterpret_cast<const bf16x8*>(a.add1.q + idx[it]);
-                if (m2 != PA_LD_NONE) p2[it] = *reinterpret_cast<const bf16x8*>(a.add2.p + idx[it]);
+                if constexpr (POOL) pa_pool_request(a.add2, ok[it] ? (unsigned)m : 0u, (unsigned)a.W, (unsigned)N, (unsigned)n, idx[it], pr[it]);
+                else if (m2 != PA_LD_NONE) p2[it] = *reinterpret_cast<const bf16x8*>(a.add2.p + idx[it]);
             }
         if (g == 0) {
             if (TAB) {
@@ -458,7 +502,8 @@ __device__ __forceinline__ void pa_conv_epilogue_lds_bwd(const PaConvArgs& a, f3
                         if (TAB) { const float4 k = ctab[BN + j * CPR + chunk]; v += fmaf(k.x, (float)p1[it][j], fmaf(k.y, (float)q1[it][j], k.z)); }
                         else v += fmaf(ka[j], (float)p1[it][j], fmaf(kb[j], (float)q1[it][j], kc[j]));
                     }
-                    if (m2 != PA_LD_NONE) v += (float)p2[it][j];
+                    if constexpr (POOL) v += pa_pool_value(pr[it], pool_e, j);
+                    else if (m2 != PA_LD_NONE) v += (float)p2[it][j];
                     const float x = (float)xr[it][j];
                     const float dz = (fmaf(ej, x, tj) > 0.f) ? v : 0.f;
                     o[j] = (bf16)dz;
@@ -568,10 +613,19 @@ __host__ __device__ inline bool pa_bwd_epilogue_lds_ok(const PaConvArgs& a) {
 
 // forward epilogues through LDS (coalesced rows), backward epilogue direct; pix(wm, mi, p) as above
 // T: >= NT * 16 floats, or (TSMALL) >= NT * 8
-template <int BN, int NI, int MI, bool BWD_LDS = true, bool TAB = false, int NT = 256, bool TSMALL = false, class PixFn>
+// POOL: an instance for launches whose second addend is pool-routed (pa_conv_pool_route_supported admits them): 1 with the LDS form of the
+// BatchNorm-backward epilogue, 2 with plain output -- one epilogue per instance (each keeps its pixel offsets in registers across the kernel)
+template <int BN, int NI, int MI, bool BWD_LDS = true, bool TAB = false, int NT = 256, bool TSMALL = false, int POOL = 0, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue_auto(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
                                                       PixFn pix, float* T, int stat_row, float4* ctab = nullptr) {
     constexpr bool FUSE = !TSMALL && !TAB && MI > 1 && MI * BN <= 128;
+    if constexpr (POOL == PA_POOL_EP_BWD) {
+        pa_conv_epilogue_lds_bwd<BN, NI, MI, TAB, NT, TSMALL, FUSE, true>(a, acc, n0, wm, wn, pix, T, stat_row, ctab);
+        return;
+    } else if constexpr (POOL == PA_POOL_EP_PLAIN) {
+        pa_conv_epilogue_lds<BN, NI, MI, NT, TSMALL, FUSE, true>(a, acc, n0, wm, wn, pix, T, stat_row);
+        return;
+    }
     if (a.ep.mode == PA_OUT_BWD) {
         // supported operand modes of the LDS variant: addend 1 plain / LIN2, addend 2 plain, no bias (every data gradient of
         // the networks); anything else takes the direct epilogue

@@ -213,7 +213,8 @@ __global__ __launch_bounds__(256, FIN ? 2 : 1) void conv_igemm_kernel(PaConvArgs
 // two barriers per step: at 16 x 16 and below that chain of 2 - 4 round trips IS the kernel (6.5 - 7.8 us for 0.1 - 0.8 GFLOP).
 // Same tile, same fragment layout, same epilogue and weight-row permutation as conv_igemm_kernel<64, 64, ...>: same results bit for bit
 // (the MFMA accumulation order over K is unchanged).
-template <int NK, int LDMODE, bool FIN>
+// POOL: the instances whose second epilogue addend is pool-routed (PA_LD_POOL, conv_epilogue.h), one per epilogue
+template <int NK, int LDMODE, bool FIN, int POOL = PA_POOL_EP_NONE>
 __global__ __launch_bounds__(256, 2) void conv1x1_oneshot_kernel(PaConvArgs a) {
     PA_SET_MAIN_PRIO();
     PA_STAMP1(0);
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_oneshot_kernel(PaConvArgs a) {
         }
     PA_STAMP1(5);
     __syncthreads();            // every wave is done with the tiles before the epilogue reuses the LDS
-    pa_conv_epilogue_auto<BN, NI, MI>(a, acc, n0, wm, wn,
+    pa_conv_epilogue_auto<BN, NI, MI, true, false, 256, false, POOL>(a, acc, n0, wm, wn,
                                      [&](int wr, int mi, int p) { const int m = m0 + wr * (BM / 2) + mi * 16 + p; return m < M ? m : -1; },
                                      reinterpret_cast<float*>(lds), (int)blockIdx.x);
     PA_STAMP1(6);
@@ -334,6 +335,13 @@ template <int NK>
 static void launch_oneshot(const PaConvArgs& a0, dim3 grid, hipStream_t st) {
     PaConvArgs a = a0;
     a.dbg = pa_tuning().conv1_dbg;      // tuning builds: cycle stamps
+    if (a.add2.mode == PA_LD_POOL) {     // (pa_conv_pool_route_supported: 128 input channels, BatchNorm backward on load, no pending finalize)
+        if constexpr (NK == 2) {
+            if (a.ep.mode == PA_OUT_BWD) hipLaunchKernelGGL((conv1x1_oneshot_kernel<2, PA_LD_LIN2, false, PA_POOL_EP_BWD>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((conv1x1_oneshot_kernel<2, PA_LD_LIN2, false, PA_POOL_EP_PLAIN>), grid, dim3(256), 0, st, a);
+        }
+        return;
+    }
     if (a.fin.rows > 0) {
         if (a.in.mode == PA_LD_BNRELU) hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_BNRELU, true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_LIN2, true>), grid, dim3(256), 0, st, a);
@@ -394,9 +402,39 @@ bool pa_conv_takes_fin(const PaConvArgs& a) {
     return !bigM && !(bigN && M >= 64 * 256);
 }
 
+// mirrors the dispatch below: does a launch with a pool-routed second addend (PA_LD_POOL) reach an instance that carries the mode -- the
+// row-tile kernel's (conv1x1_tile.hip) or the one-shot kernel's for 128 input channels?
+bool pa_conv_pool_route_supported(const PaConvArgs& a0) {
+    PaConvArgs a = a0;
+    a.add2.mode = PA_LD_POOL;
+    a.xcd = pa_tuning().epi_bwd_direct ? 2 : 0;
+    if (a.taps != 1 || a.Cin != 128 || a.Cout % 64 != 0 || a.in.mode != PA_LD_LIN2 || a.bias || a.out2 || a.fin.rows > 0 || (a.H & 1) || (a.W & 1)) return false;
+    if (a.add1.mode != PA_LD_NONE && a.add1.mode != PA_LD_PLAIN && a.add1.mode != PA_LD_LIN2) return false;
+    if (a.ep.mode != PA_OUT_PLAIN && !(a.ep.mode == PA_OUT_BWD && a.xcd < 2)) return false;
+    const size_t M = (size_t)a.B * a.H * a.W;
+    if (M * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;
+    if (!pa_tuning().conv1_old && pa_conv1x1_tile_supported(a)) return true;
+    return M < 128 * 256 && !(a.Cout % 128 == 0 && M >= 64 * 256) && pa_tuning().igemm_oneshot != 0;
+}
+
+// ... and a launch whose INPUT is pool-routed (BatchNorm backward on load with the routed dz as first operand): the row-tile kernel's PIN instance
+bool pa_conv_pool_in_supported(const PaConvArgs& a0) {
+    PaConvArgs a = a0;
+    a.in.mode = PA_LD_POOL;
+    a.xcd = pa_tuning().epi_bwd_direct ? 2 : 0;
+    if (a.taps != 1 || pa_tuning().conv1_old || pa_tuning().no_dz3) return false;
+    if ((size_t)a.B * a.H * a.W * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;
+    return pa_conv1x1_tile_supported(a);
+}
+
 int pa_launch_conv(const PaConvArgs& a0, hipStream_t st, int* stat_rows) {
     PaConvArgs a = a0;
     a.xcd = pa_tuning().epi_bwd_direct ? 2 : 0;      // A/B: direct BatchNorm-backward epilogue
+    if (a.add1.mode == PA_LD_POOL || (a.in.mode == PA_LD_POOL && !pa_conv_pool_in_supported(a)) ||
+        (a.add2.mode == PA_LD_POOL && (!a.add2.map || !pa_conv_pool_route_supported(a)))) {
+        pa_set_error_msg("pa_launch_conv: a pool-routed operand is the second addend of a launch pa_conv_pool_route_supported() admits or the input of one pa_conv_pool_in_supported() admits");
+        return 1;
+    }
     if ((a.taps != 1 && a.taps != 9) || a.Cin % 64 != 0 || a.Cout % 64 != 0 || a.Cin > 512) {
         pa_set_error_msg("pa_launch_conv: channel counts must be multiples of 64 and taps 1 or 9");
         return 1;

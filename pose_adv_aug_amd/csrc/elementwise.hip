@@ -323,7 +323,10 @@ __device__ __forceinline__ void stage_bwd_consts(float4* dst, const PaEpilogue& 
 
 // ------------------------------------------------------------------------------------------------
 // 2x2/2 max pool (reference models/asn_stacked_hg.py:69,227), input transform applied on load
-__global__ void maxpool_fwd_kernel(PaOperand in, bf16* out, int B, int H, int W, int C) {
+// MAP: also store the arg-max position k = 2 * row + col (first maximum in scan order, strict >: the rule of maxpool_bwd_*) of every pooled
+// element as a byte, laid out like `out` -- the data gradient of the pool's other consumer routes the gradient through it (PA_LD_POOL)
+template <bool MAP>
+__global__ void maxpool_fwd_kernel(PaOperand in, bf16* out, unsigned char* map, int B, int H, int W, int C) {
     const int Ho = H / 2, Wo = W / 2, CG = C / 8;
     const size_t total = (size_t)B * Ho * Wo * CG;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
@@ -333,19 +336,29 @@ __global__ void maxpool_fwd_kernel(PaOperand in, bf16* out, int B, int H, int W,
         size_t q = p / Wo;
         int yo = (int)(q % Ho), b = (int)(q / Ho);
         int c = cg * 8;
-        float m[8];
+        float m[8], am[8];
+        unsigned arg[8];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             size_t idx = (((size_t)b * H + 2 * yo + (k >> 1)) * W + 2 * xo + (k & 1)) * C + c;
             float v[8];
             pa_read8(in, idx, c, v);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) m[j] = (k == 0) ? v[j] : fmaxf(m[j], v[j]);
+            for (int j = 0; j < 8; ++j) {
+                m[j] = (k == 0) ? v[j] : fmaxf(m[j], v[j]);
+                if (MAP) { if (k == 0) { am[j] = v[j]; arg[j] = 0u; } else if (v[j] > am[j]) { am[j] = v[j]; arg[j] = (unsigned)k; } }
+            }
         }
         bf16x8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (bf16)m[j];
         *reinterpret_cast<bf16x8*>(out + p * C + c) = o;
+        if (MAP) {
+            uint2 w;
+            w.x = arg[0] | (arg[1] << 8) | (arg[2] << 16) | (arg[3] << 24);
+            w.y = arg[4] | (arg[5] << 8) | (arg[6] << 16) | (arg[7] << 24);
+            *reinterpret_cast<uint2*>(map + p * C + c) = w;
+        }
     }
 }
 
@@ -374,8 +387,11 @@ __global__ void upadd_fwd_kernel(PaOperand low, PaOperand skip, bf16* out, int B
 // ---- streaming forward variants (row indexing, template modes, thread-fixed channel constants in registers, all loads of an
 // item issued first): OP 0 = 2x2 max pool of value(in), OP 1 = nearest-upsample(low) + value(skip); item = one low-resolution
 // pixel x 8 channels (4 high-resolution pixels).  Operand modes PLAIN / BNRELU.
-template <int OP, int MA, int MB>
-__global__ __launch_bounds__(256) void pool_up_fwd_s_kernel(PaOperand a, PaOperand b, bf16* __restrict__ out, int rows, int W, int C) {
+// MAP (OP 0): 1 = also the arg-max byte map (maxpool_fwd_kernel); 2 = the map and xmax, the RAW input value at the arg-max (the stem's pool: its
+// backward reductions then need a quarter of the input, maxpool_bwd_stats_kernel)
+template <int OP, int MA, int MB, int MAP = 0>
+__global__ __launch_bounds__(256) void pool_up_fwd_s_kernel(PaOperand a, PaOperand b, bf16* __restrict__ out, int rows, int W, int C,
+                                                            unsigned char* __restrict__ map = nullptr, bf16* __restrict__ xmax = nullptr) {
     PA_SET_ELT_PRIO();
     // rows = B * H/2 (low-resolution rows); W = high-resolution width
     const int CG = C / 8, Wl = W / 2;
@@ -406,19 +422,30 @@ __global__ __launch_bounds__(256) void pool_up_fwd_s_kernel(PaOperand a, PaOpera
             for (int k = 0; k < 4; ++k) hi[k] = *reinterpret_cast<const bf16x8*>((OP == 0 ? pa : pb) + off[k]);
             if (OP == 1) lo = *reinterpret_cast<const bf16x8*>(pa + li);
             if (OP == 0) {
-                bf16x8 o;
+                bf16x8 o, xm;
+                unsigned arg[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    float m = 0.f;
+                    float m = 0.f, am = 0.f;
+                    arg[j] = 0u;
+                    xm[j] = hi[0][j];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         float v = (float)hi[k][j];
                         if (MA == PA_LD_BNRELU) v = fmaxf(fmaf(a0[j], v, a1[j]), 0.f);
                         m = k == 0 ? v : fmaxf(m, v);
+                        if (MAP) { if (k == 0) am = v; else if (v > am) { am = v; arg[j] = (unsigned)k; if (MAP == 2) xm[j] = hi[k][j]; } }
                     }
                     o[j] = (bf16)m;
                 }
                 *reinterpret_cast<bf16x8*>(out + li) = o;
+                if (MAP) {
+                    uint2 w;
+                    w.x = arg[0] | (arg[1] << 8) | (arg[2] << 16) | (arg[3] << 24);
+                    w.y = arg[4] | (arg[5] << 8) | (arg[6] << 16) | (arg[7] << 24);
+                    *reinterpret_cast<uint2*>(map + li) = w;
+                    if (MAP == 2) *reinterpret_cast<bf16x8*>(xmax + li) = xm;
+                }
             } else {
                 float l[8];
 #pragma unroll
@@ -445,27 +472,35 @@ __global__ __launch_bounds__(256) void pool_up_fwd_s_kernel(PaOperand a, PaOpera
 
 // OP 0: max pool of `a`; OP 1: upsample(a) + b.  The streaming kernel where the plan and the operand modes admit it, else the generic one.
 template <int OP>
-static int launch_pool_up_fwd(const PaOperand& a, const PaOperand& b, bf16* out, int B, int H, int W, int C, hipStream_t st) {
+static int launch_pool_up_fwd(const PaOperand& a, const PaOperand& b, bf16* out, int B, int H, int W, int C, hipStream_t st, unsigned char* map = nullptr,
+                              bf16* xmax = nullptr) {
     const bool ma = a.mode == PA_LD_PLAIN || a.mode == PA_LD_BNRELU, mb = OP == 0 || b.mode == PA_LD_PLAIN || b.mode == PA_LD_BNRELU;
     const int rows = B * (H / 2);
     const size_t items = (size_t)rows * (W / 2) * (C / 8);
     PaEltPlan p;
     if (pa_elt_plan(p, PA_ELT_FWD, items, B, H, W, C, false, ma && mb)) return 1;
     const bool A = a.mode == PA_LD_BNRELU, Bm = OP == 1 && b.mode == PA_LD_BNRELU;
+    if (xmax && (!p.streaming || !map || !A)) { pa_set_error_msg("max pool: the value at the arg-max comes from the streaming kernel only (pa_pool_stats_route_supported)"); return 1; }
     if (!p.streaming) {
         // (the generic upsample-add walks the high-resolution pixels)
-        if (OP == 0) hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(p.blocks), dim3(p.threads), 0, st, a, out, B, H, W, C);
+        if (OP == 0 && map) hipLaunchKernelGGL(maxpool_fwd_kernel<true>, dim3(p.blocks), dim3(p.threads), 0, st, a, out, map, B, H, W, C);
+        else if (OP == 0) hipLaunchKernelGGL(maxpool_fwd_kernel<false>, dim3(p.blocks), dim3(p.threads), 0, st, a, out, map, B, H, W, C);
         else hipLaunchKernelGGL(upadd_fwd_kernel, dim3(pa_grid_for((size_t)B * H * W * (C / 8), p.threads, 4096)), dim3(p.threads), 0, st, a, b, out, B, H, W, C);
     }
-    else if (A && Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_BNRELU>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
-    else if (A) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_PLAIN>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
-    else if (Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_BNRELU>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
-    else hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_PLAIN>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C);
+    else if (OP == 0 && xmax) hipLaunchKernelGGL((pool_up_fwd_s_kernel<0, PA_LD_BNRELU, PA_LD_PLAIN, 2>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C, map, xmax);
+    else if (OP == 0 && map) {
+        if (A) hipLaunchKernelGGL((pool_up_fwd_s_kernel<0, PA_LD_BNRELU, PA_LD_PLAIN, 1>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C, map, nullptr);
+        else hipLaunchKernelGGL((pool_up_fwd_s_kernel<0, PA_LD_PLAIN, PA_LD_PLAIN, 1>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C, map, nullptr);
+    }
+    else if (A && Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_BNRELU>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C, nullptr, nullptr);
+    else if (A) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_BNRELU, PA_LD_PLAIN>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C, nullptr, nullptr);
+    else if (Bm) hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_BNRELU>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C, nullptr, nullptr);
+    else hipLaunchKernelGGL((pool_up_fwd_s_kernel<OP, PA_LD_PLAIN, PA_LD_PLAIN>), dim3(p.blocks), dim3(p.threads), 0, st, a, b, out, rows, W, C, nullptr, nullptr);
     return (int)hipGetLastError();
 }
 
-int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st) {
-    return launch_pool_up_fwd<0>(in, in, out, B, H, W, C, st);
+int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st, unsigned char* map, bf16* xmax) {
+    return launch_pool_up_fwd<0>(in, in, out, B, H, W, C, st, map, xmax);
 }
 
 // gradient of the max pool: routed to the first maximum in scan order (torch semantics), plus an
@@ -599,6 +634,66 @@ static void launch_maxpool_bwd_s(const bf16* dout, const PaOperand& in, const bf
         hipLaunchKernelGGL((maxpool_bwd_s_kernel<INMODE, HASADD, PA_OUT_BWD>), dim3(p.blocks), dim3(p.threads), p.lds, st, dout, in, add, ep, din, rows, W, C);
     else
         hipLaunchKernelGGL((maxpool_bwd_s_kernel<INMODE, HASADD, PA_OUT_PLAIN>), dim3(p.blocks), dim3(p.threads), p.lds, st, dout, in, add, ep, din, rows, W, C);
+}
+
+// The BatchNorm-backward reductions of maxpool_bwd_s_kernel<PA_LD_BNRELU, false, PA_OUT_BWD> WITHOUT its output, from a quarter of its input: the
+// gradient of the pooled tensor and xmax, the raw input value at the arg-max (stored by the forward pool).  The three other positions of a
+// window get dz = +0 there, which changes neither sum; with the same grid, thread -> item mapping, loop order and flush_stats tree the
+// partial rows are the same bits.  The routed dz itself is formed by its reader (conv1x1_tile.hip, PIN).
+__global__ __launch_bounds__(1024) void maxpool_bwd_stats_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ xmax, PaEpilogue ep,
+                                                                 int rows, int W, int C) {
+    PA_SET_ELT_PRIO();
+    extern __shared__ float red[];     // [nwaves][2*C] partial statistics, then float4 {scale, shift, mean, invstd}
+    float4* cst = reinterpret_cast<float4*>(red + (blockDim.x / 64) * 2 * C);
+    stage_bwd_consts(cst, ep, C);
+    __syncthreads();
+    const int CG = C / 8, Wo = W / 2;
+    const unsigned row_items = (unsigned)Wo * CG;
+    float s1[8], s2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    const int c = (threadIdx.x % CG) * 8;
+    const unsigned rows_per_it = row_items >= blockDim.x ? 1u : blockDim.x / row_items;
+    const unsigned rsub = row_items >= blockDim.x ? 0u : threadIdx.x / row_items;
+    const unsigned i0 = row_items >= blockDim.x ? threadIdx.x : threadIdx.x % row_items;
+    for (unsigned rb = blockIdx.x * rows_per_it; rb < (unsigned)rows; rb += gridDim.x * rows_per_it) {
+        const unsigned r = rb + rsub;
+        if (r >= (unsigned)rows) continue;
+        for (unsigned i = i0; i < row_items; i += blockDim.x) {
+            const unsigned xo = i / (unsigned)CG;
+            const unsigned li = (r * (unsigned)Wo + xo) * (unsigned)C + (unsigned)c;
+            const bf16x8 g = *reinterpret_cast<const bf16x8*>(dout + li);
+            const bf16x8 x = *reinterpret_cast<const bf16x8*>(xmax + li);
+            float rr[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) rr[j] = (float)g[j] + 0.f;
+            (void)Bwd8::apply(cst, c, x, rr, s1, s2);
+        }
+    }
+    flush_stats(red, ep.stats, C, c, s1, s2);
+}
+
+// the plan both launches of a stats-routed pool share: forward (streaming, BatchNorm + ReLU input: it stores xmax) and backward (streaming,
+// BatchNorm-backward epilogue on the pooled tensor itself: the partial rows the statistics kernel reproduces)
+static bool pool_stats_plan(PaEltPlan& p, const PaOperand& in, const PaEpilogue& ep, int B, int H, int W, int C) {
+    if (in.mode != PA_LD_BNRELU || ep.mode != PA_OUT_BWD || ep.xref != in.p || !pa_stats_groups_ok(C)) return false;
+    PaEltPlan f;
+    if (pa_elt_plan(f, PA_ELT_FWD, (size_t)B * (H / 2) * (W / 2) * (C / 8), B, H, W, C, false, true) || !f.streaming) return false;
+    if (pa_elt_plan(p, PA_ELT_POOL_BWD, (size_t)B * (H / 2) * (W / 2) * (C / 8), B, H, W, C, true, true) || !p.streaming) return false;
+    return true;
+}
+bool pa_pool_stats_route_supported(const PaOperand& in, const PaEpilogue& ep, int B, int H, int W, int C) {
+    PaEltPlan p;
+    return pool_stats_plan(p, in, ep, B, H, W, C);
+}
+int pa_launch_maxpool_bwd_stats(const bf16* dout, const bf16* xmax, const PaOperand& in, const PaEpilogue& ep, int B, int H, int W, int C,
+                                hipStream_t st, int* stat_rows) {
+    PaEltPlan p;
+    if (!pool_stats_plan(p, in, ep, B, H, W, C)) { pa_set_error_msg("pa_launch_maxpool_bwd_stats: not a pool pa_pool_stats_route_supported() admits"); return 1; }
+    if (stat_rows) *stat_rows = p.blocks;
+    if (ep.rows_out) *ep.rows_out = p.blocks;
+    hipLaunchKernelGGL(maxpool_bwd_stats_kernel, dim3(p.blocks), dim3(p.threads), p.lds, st, dout, xmax, ep, B * (H / 2), W, C);
+    return (int)hipGetLastError();
 }
 
 int pa_launch_maxpool_bwd(const bf16* dout, const PaOperand& in, const PaOperand& add, const PaEpilogue& ep, bf16* din,

@@ -32,6 +32,12 @@ bool pa_conv1x1_tile_up_supported(const PaConvArgs& a);
 int pa_launch_conv(const PaConvArgs& a, hipStream_t st, int* stat_rows = nullptr);
 // will pa_launch_conv send this launch to a kernel that carries the finalize prologue (generic kernel, 3x3 tile kernel)?
 bool pa_conv_takes_fin(const PaConvArgs& a);
+// may add2 of this launch be pool-routed (PA_LD_POOL: the gradient of a 2x2 max pool read through its arg-max map)?  Only instances of their own
+// carry the mode: the row-tile 1x1 kernel's and the one-shot 1x1 kernel's for 128 input channels
+bool pa_conv_pool_route_supported(const PaConvArgs& a);
+// ... and may its INPUT be pool-routed: a BatchNorm-backward load (k0 / k1 / k2, q) whose first operand is the routed, ReLU-masked gradient of a
+// 2x2 max pool (in.p: gradient of the pooled tensor, in.map; ep2.scale / shift: the mask's BatchNorm), stored transformed to dz_out?
+bool pa_conv_pool_in_supported(const PaConvArgs& a);
 // halo-tile 3x3 kernel (conv3x3_tile.hip); pa_launch_conv dispatches to it when the shape is supported
 bool pa_conv3x3_tile_supported(const PaConvArgs& a);
 bool pa_conv3x3_tile_takes_fin(const PaConvArgs& a);      // ... and the instance it would run exists with the finalize prologue
@@ -98,7 +104,16 @@ int pa_launch_bn_bwd_finalize(const float* bstats, int rows, const float* scale,
 
 // ---- pooling / upsampling (NHWC bf16).  These launches, pa_launch_ep_apply and pa_launch_cell_mask take their geometry from pa_elt_plan
 // (launch_plan.h), which also refuses what the kernels cannot do: a statistics epilogue needs C / 8 a power of two <= 64
-int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st);
+// map (optional, [B][H/2][W/2][C] bytes): the arg-max position 2 * row + col of every pooled element (first maximum in scan order, the rule of
+// pa_launch_maxpool_bwd); nullptr = do not write
+// xmax (optional, with map, like out): the RAW input value at the arg-max (streaming kernel, BatchNorm + ReLU input only)
+int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st, unsigned char* map = nullptr, bf16* xmax = nullptr);
+// The partial rows of pa_launch_maxpool_bwd(dout, in, none, ep, ...) with a BatchNorm-backward epilogue on the pooled tensor itself, same bits,
+// from dout and xmax alone (a quarter of the traffic, no output): for a pool whose routed gradient is formed by its reader
+// (pa_conv_pool_in_supported).  supported: both launches of the pool take their streaming kernels.
+bool pa_pool_stats_route_supported(const PaOperand& in, const PaEpilogue& ep, int B, int H, int W, int C);
+int pa_launch_maxpool_bwd_stats(const bf16* dout, const bf16* xmax, const PaOperand& in, const PaEpilogue& ep, int B, int H, int W, int C,
+                                hipStream_t st, int* stat_rows = nullptr);
 // grad of 2x2 max pool routed to the arg-max (first max in scan order), + optional addend, then epilogue
 int pa_launch_maxpool_bwd(const bf16* dout, const PaOperand& in, const PaOperand& add, const PaEpilogue& ep, bf16* din,
                           int B, int H, int W, int C, hipStream_t st, int* stat_rows = nullptr);

@@ -105,6 +105,8 @@ struct Residual {
     // (Net::conv_dgrad / pa_conv1x1_tile_up_supported); low_fused says whether it did
     const Act* low_of_in = nullptr;
     bool low_fused = false;
+    // the gradient of x3 arrives pool-routed (Net::stem_route_ok): conv3's data gradient forms dz from g3_pool (PA_LD_POOL) and g3_pool_ep's mask
+    bool g3_pool_on = false; PaOperand g3_pool; PaEpilogue g3_pool_ep;
     int b3_rows_scale = 1;   // partial-row capacity of bn3's backward reductions in units of this block's own map (4: the rows may come from a launch over the 2x larger map)
     int bwd_a(Net& n, const Act& in);                                  // everything except the input gradient
     int bwd_b(Net& n, const Act& in, const PaOperand& extra);           // input gradient (needs `extra`)
@@ -136,6 +138,14 @@ struct Hourglass {
     Act skipm[4], neckm;          // occlusion branch only: skip / neck outputs times the 4x4 cell mask (reference :79-100)
     bf16* poolgrad[4] = {nullptr, nullptr, nullptr, nullptr};   // gradient of the pool routed back to its input
     bool low_done[4] = {false, false, false, false};             // d up[k].x3 of this backward pass came out of the data gradient that produced d merged[k]
+    // pool routing (Net::pool_route): the forward pool k also stores its arg-max byte map, and the first block of skip[k] reads the pool's
+    // gradient through it (PA_LD_POOL) -- no pool backward launch, poolgrad[k] is only filled on request (fill_poolgrad: the debug view)
+    unsigned char* poolmap[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool map_written[4] = {false, false, false, false};          // by the last forward pass
+    bool routed[4] = {false, false, false, false};               // the last backward pass routed pool k: poolgrad[k] is stale
+    PaOperand route_extra[4];                                    // ... and this was its plain addend (extra0 at k = 0)
+    bool route_ok(Net& n, int k, const Act& x, const PaOperand& ex0);
+    int fill_poolgrad(Net& n, int k, const Act& in);             // run the pool backward launch of a routed level into poolgrad[k]
     void declare(Net& n, const std::string& prefix, int chan);
     void layout(Net& n, Arena& a, int B, int H, int W, bool need_grad);
     int encode(Net& n, const Act& in);
@@ -202,7 +212,10 @@ struct Net {
     Prof prof;
     // bytes this design moves (pa_net_design_bytes): operands of every launch since begin_step(), counted once per launch
     double dbytes_rd = 0, dbytes_wr = 0;
-    static double opb(const PaOperand& o, double elems) { return o.mode == PA_LD_NONE ? 0.0 : (o.mode == PA_LD_LIN2 ? 4.0 : 2.0) * elems; }
+    static double opb(const PaOperand& o, double elems) {
+        if (o.mode == PA_LD_POOL) return (2.0 + 1.0) * elems / 4 + (o.q ? 2.0 * elems : 0.0);      // pooled gradient + byte map, plain addend
+        return o.mode == PA_LD_NONE ? 0.0 : (o.mode == PA_LD_LIN2 ? 4.0 : 2.0) * elems;
+    }
     void cnt(double rd, double wr) { dbytes_rd += rd; dbytes_wr += wr; }
     // forward + loss + backward of the training step captured ONCE into a HIP graph (fork / join events of the side and
     // weight-gradient streams become graph edges) and replayed: pa_hg_train_step with use_graph
@@ -268,10 +281,19 @@ struct Net {
                  bf16* out, BNLayer* bn_after, BNLayer* pending_in = nullptr, bool defer_after = false);
     int conv_dgrad(ConvLayer& c, const PaOperand& dy, int B, int H, int W, const PaOperand& add1, const PaOperand& add2,
                    const PaEpilogue& ep, bf16* out, bf16* dz_out = nullptr, bool* dz_done = nullptr, BNLayer* pending_in = nullptr,
-                   const Act* low = nullptr, bool* low_done = nullptr);      // low: also emit the upsample-add backward's low-resolution output (Residual::low_of_in)
+                   const Act* low = nullptr, bool* low_done = nullptr,      // low: also emit the upsample-add backward's low-resolution output (Residual::low_of_in)
+                   const PaEpilogue* pool_in_ep = nullptr);                  // dy is pool-routed (PA_LD_POOL): the mask the pool backward launch would have applied
     // BatchNorm finalize in the consumer's prologue for launches with at most this many partial rows (the 16 x 16 and smaller levels;
     // 0 = always a launch of its own).  Same bits either way (bn_fin.h)
     int fin_rows_max = pa_tuning().fin_prologue > PA_FIN_SMALL_ROWS ? PA_FIN_SMALL_ROWS : pa_tuning().fin_prologue;
+    int pool_route = pa_tuning().pool_route;            // pool gradients through the arg-max map: bit 0 the hourglass pools (Hourglass::poolmap), bit 1 the stem's (stem_map); pa_net_set_pool_route
+    bool maps_on = false;                               // this forward pass stores the hourglass maps (a training pass of the whole net with pool_route & 1)
+    // the stem's pool (residual1 -> pool0): map + the raw value at the arg-max; its backward pass is then a quarter-size statistics launch and
+    // a pool-routed load in residual1's conv3 data gradient (Residual::g3_pool) instead of a launch that writes residual1's whole gradient
+    unsigned char* stem_map = nullptr; bf16* stem_xmax = nullptr;
+    bool stem_map_written = false, stem_routed = false;      // by the last forward pass / the last backward pass routed it: res1.x3.grad is stale
+    bool stem_route_ok();
+    int fill_stem_grad();                               // run the pool backward launch into res1.x3.grad (the debug view of a routed step)
     int fin_mask = pa_tuning().fin_mask;       // which finalizes may ride in a consumer: 1 forward x1 / x2, 2 backward x2, 4 backward x3
     bool fin_consumer_ok(const ConvLayer& c, int B, int H, int W, bool dgrad) const;
     PaBnFin fin_fwd(const BNLayer& b, int M) const;

@@ -14,8 +14,8 @@ static int ablate() { return pa_tuning().ablate; }
 static int ablate_h() { return pa_tuning().ablate_h; }
 #define TRY(x) do { int _r = (x); if (_r) return _r; } while (0)
 
-PaOperand pa_plain(const bf16* p) { PaOperand o; o.p = p; o.q = nullptr; o.k0 = o.k1 = o.k2 = nullptr; o.mode = PA_LD_PLAIN; return o; }
-PaOperand pa_none() { PaOperand o; o.p = o.q = nullptr; o.k0 = o.k1 = o.k2 = nullptr; o.mode = PA_LD_NONE; return o; }
+PaOperand pa_plain(const bf16* p) { PaOperand o; o.p = p; o.q = nullptr; o.k0 = o.k1 = o.k2 = nullptr; o.map = nullptr; o.mode = PA_LD_PLAIN; return o; }
+PaOperand pa_none() { PaOperand o; o.p = o.q = nullptr; o.k0 = o.k1 = o.k2 = nullptr; o.map = nullptr; o.mode = PA_LD_NONE; return o; }
 static PaEpilogue ep_plain() { PaEpilogue e; memset(&e, 0, sizeof e); e.mode = PA_OUT_PLAIN; return e; }
 static int round64(int v) { return (v + 63) / 64 * 64; }
 
@@ -172,6 +172,7 @@ void Hourglass::layout(Net& n, Arena& a, int B, int H, int W, bool need_grad) {
         pooled[k] = n.new_act(a, B, H >> (k + 1), W >> (k + 1), C, nullptr, need_grad);
         down[k].layout(n, a, B, H >> (k + 1), W >> (k + 1), need_grad);
         poolgrad[k] = need_grad ? a.get<bf16>((size_t)B * (H >> k) * (W >> k) * C) : nullptr;
+        poolmap[k] = need_grad ? a.get<unsigned char>(pooled[k].numel()) : nullptr;
     }
     neck.layout(n, a, B, H >> 4, W >> 4, need_grad);
     for (int k = 3; k >= 0; --k) {
@@ -206,6 +207,8 @@ size_t Net::layout_all(char* base) {
     a0 = new_act(a, B, H2, H2, 64, &stem_bn, true);
     res1.layout(*this, a, B, H2, H2, true);
     pool0 = new_act(a, B, H4, H4, 128, nullptr, true);
+    stem_map = a.get<unsigned char>(pool0.numel());
+    stem_xmax = a.get<bf16>(pool0.numel());
     res2.layout(*this, a, B, H4, H4, true);
     res3.layout(*this, a, B, H4, H4, true);
     lin_out.resize(stacks); xin.resize(stacks); heat.resize(stacks); heat_peak.resize(stacks); heat_peak_valid.assign(stacks, 0); heat64.resize(stacks); dheat64.resize(stacks);
@@ -420,13 +423,18 @@ int Net::conv_fwd(ConvLayer& c, const PaOperand& in, int B_, int H, int W, const
 }
 
 int Net::conv_dgrad(ConvLayer& c, const PaOperand& dy, int B_, int H, int W, const PaOperand& add1, const PaOperand& add2,
-                    const PaEpilogue& ep, bf16* out, bf16* dz_out, bool* dz_done, BNLayer* pending_in, const Act* low, bool* low_done) {
+                    const PaEpilogue& ep, bf16* out, bf16* dz_out, bool* dz_done, BNLayer* pending_in, const Act* low, bool* low_done,
+                    const PaEpilogue* pool_in_ep) {
     PaConvArgs a; memset(&a, 0, sizeof a);
     if (low_done) *low_done = false;
     if (pending_in && pending_in->bfin_pending) { a.fin = fin_bwd(*pending_in, B_ * H * W); pending_in->bfin_pending = false; }
     a.in = dy; a.w = c.wb; a.bias = nullptr; a.add1 = add1; a.add2 = add2; a.out = out; a.ep = ep; a.low_prio = on_side ? 1 : 0;
     a.B = B_; a.H = H; a.W = W; a.Cin = c.pcout; a.Cout = c.pcin; a.taps = c.taps();
     if (dz_done) *dz_done = false;
+    if (dy.mode == PA_LD_POOL) {                   // (Net::stem_route_ok checked pa_conv_pool_in_supported: the instance stores dz)
+        if (!pool_in_ep || !dz_out) { pa_set_error_msg("conv_dgrad: a pool-routed gradient needs its mask and a dz buffer"); return 1; }
+        a.ep2 = *pool_in_ep; a.dz_out = dz_out; if (dz_done) *dz_done = true;
+    }
     if (dz_out && dy.mode == PA_LD_LIN2) {         // only the 1x1 row-tile kernel stores its transformed input
         const PaTuning& t = pa_tuning();
         const bool off = t.conv1_old || t.no_dz3, off3 = t.conv3_old || t.no_dz2;
@@ -435,6 +443,13 @@ int Net::conv_dgrad(ConvLayer& c, const PaOperand& dy, int B_, int H, int W, con
     double wb, wf; conv_work(B_ * H * W, c.Cin, c.Cout, c.taps(), false, wb, wf);
     ProfEntry* pe = prof.begin((long)B_ * H * W < PA_PROF_LOW_M ? PA_PROF_LOW_DGRAD : (c.k == 3 ? PA_PROF_DGRAD3 : PA_PROF_DGRAD1), wb, wf, st);
     if ((c.k == 3 && (ablate() & 8)) || (c.k == 1 && (ablate() & 16)) || ((ablate() & 256) && H <= ablate_h())) { if (a.ep.rows_out) *a.ep.rows_out = 1; prof.end(pe, st); return 0; }
+    if (dy.mode == PA_LD_POOL) {
+        { const double M = (double)B_ * H * W;
+          cnt(opb(dy, M * a.Cin) + 2.0 * M * a.Cout + 2.0 * a.Cout * a.taps * a.Cin, 2.0 * M * a.Cout + 2.0 * M * a.Cin); }
+        int rc = pa_launch_conv(a, st);
+        prof.end(pe, st);
+        return rc;
+    }
     // the low-resolution half of the upsample-add backward in this launch's epilogue (round 6): an instance of the row-tile 1x1 kernel
     const bool up_fuse = pa_tuning().upadd_fuse && !pa_tuning().conv1_old;
     bool up = false;
@@ -595,10 +610,10 @@ int Net::launch_pending_wgrads() {
 }
 
 // the streaming launches with their operand bytes counted (Net::cnt, pa_net_design_bytes)
-static int c_maxpool_fwd(Net& n, const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st) {
-    const double e = (double)B * H * W * C; n.cnt(Net::opb(in, e), 2.0 * e / 4);
+static int c_maxpool_fwd(Net& n, const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st, unsigned char* map = nullptr, bf16* xmax = nullptr) {
+    const double e = (double)B * H * W * C; n.cnt(Net::opb(in, e), 2.0 * e / 4 + (map ? e / 4 : 0.0) + (xmax ? 2.0 * e / 4 : 0.0));
     if (ablate() & 4096) return 0;
-    return pa_launch_maxpool_fwd(in, out, B, H, W, C, st);
+    return pa_launch_maxpool_fwd(in, out, B, H, W, C, st, map, xmax);
 }
 static int c_maxpool_bwd(Net& n, const bf16* dout, const PaOperand& in, const PaOperand& add, const PaEpilogue& ep, bf16* din, int B, int H, int W, int C,
                          hipStream_t st, int* rows = nullptr) {
@@ -661,9 +676,10 @@ int Residual::bwd_a(Net& n, const Act& in) {
     // conv3's data gradient goes first: its kernel also stores dz3 = BatchNorm-backward(x3.grad, x3.raw), and the weight
     // gradients / the shortcut addend after it read that one tensor instead of recomputing it from two
     // (x3.bn: its finalize may be pending -- then this launch does it in its prologue, Net::x3_fin_ok)
-    PaOperand g3 = n.gradop(x3);
+    PaOperand g3 = g3_pool_on ? g3_pool : n.gradop(x3);
     dz3_valid = false;
-    TRY(n.conv_dgrad(c3, g3, B, H, W, pa_none(), pa_none(), n.final_ep(x2), x2.grad, dz3, &dz3_valid, x3.bn));
+    TRY(n.conv_dgrad(c3, g3, B, H, W, pa_none(), pa_none(), n.final_ep(x2), x2.grad, dz3, &dz3_valid, x3.bn, nullptr, nullptr, g3_pool_on ? &g3_pool_ep : nullptr));
+    if (g3_pool_on && !dz3_valid) { pa_set_error_msg("Residual::bwd_a: the pool-routed data gradient did not store dz3"); return 1; }
     if (dz3_valid) g3 = pa_plain(dz3);
     TRY(n.conv_wgrad(c3, g3, n.op(x2), B, H, W));
     // (x2's BatchNorm-backward constants are first read by conv2's data gradient, which can compute them in its prologue; conv2's
@@ -743,7 +759,8 @@ int Hourglass::encode(Net& n, const Act& in) {
         } else {
             TRY(skip_branch());
         }
-        TRY(c_maxpool_fwd(n, n.op(*cur), pooled[k].raw, cur->B, cur->H, cur->W, cur->C, n.st));
+        map_written[k] = n.maps_on && poolmap[k] != nullptr;
+        TRY(c_maxpool_fwd(n, n.op(*cur), pooled[k].raw, cur->B, cur->H, cur->W, cur->C, n.st, map_written[k] ? poolmap[k] : nullptr));
         TRY(down[k].fwd(n, pooled[k]));
         cur = &down[k].out();
     }
@@ -771,6 +788,24 @@ bool Hourglass::low_fusable(const Net& n, int k) const {
     if (n.drop_mask || k < 0 || k > 3) return false;
     const Act& m = merged[k];
     return pa_upadd_bwd_splits(n.final_ep(up[k].out()), n.final_ep(skip[k].out()), m.B, m.H, m.W, m.C);
+}
+
+// Can the first block of skip[k] take the gradient of pool k through the arg-max map (its conv1 data gradient as Residual::bwd_b launches it:
+// BatchNorm backward on load, dz3 or its LIN2 form as first addend, the epilogue of the block input x)?
+bool Hourglass::route_ok(Net& n, int k, const Act& x, const PaOperand& ex0) {
+    if (!(n.pool_route & 1) || !map_written[k] || (ablate() & 2048)) return false;
+    if (ex0.mode != PA_LD_NONE && ex0.mode != PA_LD_PLAIN) return false;
+    Residual& r = skip[k].head();
+    if (r.has_adapter || r.low_of_in) return false;
+    PaConvArgs a; memset(&a, 0, sizeof a);
+    a.in = n.gradop(r.x1); a.add1 = pa_plain(r.dz3); a.add2 = pa_none(); a.ep = n.final_ep(x);
+    a.B = x.B; a.H = x.H; a.W = x.W; a.Cin = r.c1.pcout; a.Cout = r.c1.pcin; a.taps = r.c1.taps();
+    return pa_conv_pool_route_supported(a);
+}
+
+int Hourglass::fill_poolgrad(Net& n, int k, const Act& in) {
+    const Act& x = (k == 0) ? in : down[k - 1].out();
+    return pa_launch_maxpool_bwd(pooled[k].grad, n.op(x), route_extra[k], ep_plain(), poolgrad[k], x.B, x.H, x.W, x.C, n.st);
 }
 
 // precondition: merged[0].grad holds the finished (plain) gradient of the hourglass output.
@@ -838,13 +873,22 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
     for (int k = 3; k >= 0; --k) {
         TRY(down[k].bwd(n, pooled[k], pa_none(), true));
         const Act& x = (k == 0) ? in : down[k - 1].out();
-        TRY(c_maxpool_bwd(n, pooled[k].grad, n.op(x), (k == 0) ? extra0 : pa_none(), ep_plain(), poolgrad[k],
-                                  x.B, x.H, x.W, x.C, n.st));
+        // the pool's gradient reaches skip[k]'s first block through the arg-max map of the forward pool (no launch, no full-resolution tensor),
+        // or as poolgrad[k] from a launch of its own
+        const PaOperand ex0 = (k == 0) ? extra0 : pa_none();
+        PaOperand pg = pa_plain(poolgrad[k]);
+        routed[k] = route_ok(n, k, x, ex0);
+        if (routed[k]) {
+            route_extra[k] = ex0;
+            pg.mode = PA_LD_POOL; pg.p = pooled[k].grad; pg.map = poolmap[k]; pg.q = ex0.mode == PA_LD_PLAIN ? ex0.p : nullptr;
+        } else {
+            TRY(c_maxpool_bwd(n, pooled[k].grad, n.op(x), ex0, ep_plain(), poolgrad[k], x.B, x.H, x.W, x.C, n.st));
+        }
         if (n.multi_stream) {
             TRY(n.wait_join(k));
-            TRY(skip[k].bwd_b(n, x, pa_plain(poolgrad[k])));
+            TRY(skip[k].bwd_b(n, x, pg));
         } else {
-            TRY(skip[k].bwd(n, x, pa_plain(poolgrad[k]), true));
+            TRY(skip[k].bwd(n, x, pg, true));
         }
         if (k >= 1) TRY(n.finish_grad_or_defer(x, n.x3_fin_ok(down[k - 1], pooled[k - 1])));      // x = down[k-1].out(): read next by down[k-1]'s backward pass
         else TRY(n.finish_grad(x));
@@ -957,7 +1001,10 @@ int Net::forward_pose_body(const float* img_nchw, const bf16* img4_in, const dou
     if (pts && pts != pts_dev) PA_CHECK(hipMemcpyAsync(pts_dev, pts, (size_t)B * classes * 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     TRY(conv_fwd(stem_conv, pa_plain(image), B, res / 2, res / 2, pa_none(), pa_none(), a0.raw, &stem_bn));
     TRY(res1.fwd(*this, a0));
-    TRY(c_maxpool_fwd(*this, op(res1.x3), pool0.raw, B, res / 2, res / 2, 128, st));
+    // (with pool routing a training pass also stores the pools' arg-max maps, and the stem's pool the raw value at the arg-max)
+    maps_on = (pool_route & 1) && train;
+    stem_map_written = (pool_route & 2) && train && stem_map && pa_pool_stats_route_supported(op(res1.x3), final_ep(res1.x3), B, res / 2, res / 2, 128);
+    TRY(c_maxpool_fwd(*this, op(res1.x3), pool0.raw, B, res / 2, res / 2, 128, st, stem_map_written ? stem_map : nullptr, stem_map_written ? stem_xmax : nullptr));
     TRY(res2.fwd(*this, pool0));
     TRY(res3.fwd(*this, res2.x3));
     const int Hh = res / 4;
@@ -1017,13 +1064,45 @@ int Net::backward_stem() {
     TRY(res3.bwd(*this, res2.x3, pa_none(), true));
     TRY(finish_grad(res2.x3));
     TRY(res2.bwd(*this, pool0, pa_none(), true));
-    TRY(c_maxpool_bwd(*this, pool0.grad, op(res1.x3), pa_none(), final_ep(res1.x3), res1.x3.grad, B, res / 2, res / 2, 128, st));
-    TRY(finish_grad(res1.x3));
+    // the stem's pool: a launch that routes d pool0 into residual1's whole (four times larger) gradient -- or, routed, the launch's reductions
+    // from a quarter of its input, and the routed gradient formed on load by its one reader, conv3's data gradient (which stores dz3 for the rest)
+    stem_routed = stem_route_ok();
+    res1.g3_pool_on = stem_routed;
+    if (stem_routed) {
+        const double e = (double)B * (res / 4) * (res / 4) * 128;
+        cnt(4.0 * e, 0.0);
+        TRY(pa_launch_maxpool_bwd_stats(pool0.grad, stem_xmax, op(res1.x3), final_ep(res1.x3), B, res / 2, res / 2, 128, st));
+        TRY(finish_grad(res1.x3));
+        res1.g3_pool = gradop(res1.x3);
+        res1.g3_pool.mode = PA_LD_POOL; res1.g3_pool.p = pool0.grad; res1.g3_pool.map = stem_map;
+        res1.g3_pool_ep = final_ep(res1.x3);
+    } else {
+        TRY(c_maxpool_bwd(*this, pool0.grad, op(res1.x3), pa_none(), final_ep(res1.x3), res1.x3.grad, B, res / 2, res / 2, 128, st));
+        TRY(finish_grad(res1.x3));
+    }
     TRY(res1.bwd(*this, a0, pa_none(), true));
+    res1.g3_pool_on = false;
     TRY(finish_grad(a0));
     TRY(conv_wgrad(stem_conv, gradop(a0), pa_plain(cur_image), B, res / 2, res / 2));
     TRY(reduce_grads());
     return join_meters();               // the step's meters ran beside this pass: later readers on the main stream come behind them
+}
+
+// both halves of the stem's routed pool exist for this shape: the statistics launch (the streaming plans of the pool) and the pool-routed load
+// of residual1's conv3 data gradient, which must also be the launch that stores dz3 for the later readers of that gradient
+bool Net::stem_route_ok() {
+    if (!(pool_route & 2) || !stem_map_written || (ablate() & (2048 | 16 | 4))) return false;
+    const int H = res / 2;
+    if (!pa_pool_stats_route_supported(op(res1.x3), final_ep(res1.x3), B, H, H, 128)) return false;
+    PaConvArgs a; memset(&a, 0, sizeof a);
+    a.in = gradop(res1.x3); a.in.map = stem_map; a.add1 = pa_none(); a.add2 = pa_none(); a.ep = final_ep(res1.x2); a.ep2 = final_ep(res1.x3);
+    a.dz_out = res1.dz3; a.out = res1.x2.grad;
+    a.B = B; a.H = H; a.W = H; a.Cin = res1.c3.pcout; a.Cout = res1.c3.pcin; a.taps = res1.c3.taps();
+    return pa_conv_pool_in_supported(a);
+}
+
+int Net::fill_stem_grad() {
+    return pa_launch_maxpool_bwd(pool0.grad, op(res1.x3), pa_none(), final_ep(res1.x3), res1.x3.grad, B, res / 2, res / 2, 128, st);
 }
 
 int Net::backward_pose() {

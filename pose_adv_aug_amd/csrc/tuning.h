@@ -25,6 +25,7 @@
     X(wgrad_nopipe,     "PA_WGRAD_NOPIPE",     0,   "plain instead of pipelined tile weight gradients")                            \
     X(upadd_fuse,       "PA_UPADD_FUSE",       1,   "0: the upsample-add backward's low-resolution half as a launch of its own")   \
     X(upadd_split,      "PA_UPADD_SPLIT",      1,   "0: both halves of the upsample-add backward in one launch on the main stream") \
+    X(pool_route,       "PA_POOL_ROUTE",       3,   "pool gradients through the forward pools' arg-max maps: bit 0 the hourglass pools, bit 1 the stem's pool (0: a pool backward launch each)") \
     X(fin_prologue,     "PA_FIN_PROLOGUE",     128, "most partial rows a consumer finalizes in its prologue (0: always a finalize launch; at most 128)") \
     X(fin_mask,         "PA_FIN_MASK",         7,   "which finalizes may ride in a consumer: 1 forward x1 / x2, 2 backward x2, 4 backward x3") \
     X(single_stream,    "PA_SINGLE_STREAM",    0,   "everything on the caller's stream")                                           \
