@@ -220,6 +220,28 @@ int pa_rmsprop_step_state(float* param, const float* grad, float* square_avg, si
                           float eps, float gscale, int32_t* state, void* stream);
 int pa_rmsprop_skipped_steps_state(const int32_t* state, long long* count, void* stream);
 
+/* The other options of torch.optim.RMSprop (momentum, weight_decay, centered) and the coefficient of
+ * torch.nn.utils.clip_grad_norm_.  The reference trains with all of them off (stack-hg.py:51-52): these calls have no reference
+ * counterpart beyond torch's option set.  Per element, in fp32 (torch 2.10 _single_tensor_rmsprop):
+ *   gr = (grad * gscale) * clip_coef[0] + weight_decay * param;  v = alpha v + (1 - alpha) gr^2;  ga = alpha ga + (1 - alpha) gr;
+ *   den = sqrt(centered ? max(0, v - ga^2) : v) + eps;  momentum > 0: buf = momentum buf + gr / den, param -= lr buf;
+ *   else param -= lr gr / den.
+ * max(0, .) is the one difference from torch, which returns NaN where rounding makes v - ga^2 slightly negative.
+ * momentum_buf: n floats, required iff momentum > 0; grad_avg: n floats, required iff centered; clip_coef: one device float
+ * (out2 + 1 of the norm call below) or NULL; state: two device int32 as for pa_rmsprop_step_state (required).  With momentum 0,
+ * weight_decay 0, centered 0 and clip_coef NULL the call is pa_rmsprop_step_state, bit for bit.  Half-precision build: a step whose
+ * gradient holds inf / NaN leaves param, square_avg, momentum_buf and grad_avg untouched and counts once in state.
+ * Errors (non-zero, pa_last_error set, nothing launched): a NULL opts / param / grad / square_avg / state, a missing or superfluous
+ * momentum_buf / grad_avg, momentum < 0, weight_decay < 0. */
+typedef struct pa_rmsprop_opts { float lr, alpha, eps, momentum, weight_decay; int32_t centered; } pa_rmsprop_opts;
+int pa_rmsprop_step_opts(const pa_rmsprop_opts* o, float* param, const float* grad, float* square_avg, float* momentum_buf,
+                         float* grad_avg, size_t n, float gscale, const float* clip_coef, int32_t* state, void* stream);
+/* out2 (device) = {norm of gscale * grad, min(1, max_norm / (norm + 1e-6))}: squares summed in double, two launches, no atomics (the
+ * same input gives the same bits), no host synchronisation.  workspace: pa_grad_norm_workspace_bytes(n) bytes on the device, 8-byte
+ * aligned.  Errors: a NULL grad / workspace / out2, max_norm <= 0. */
+size_t pa_grad_norm_workspace_bytes(size_t n);
+int pa_grad_norm(const float* grad, size_t n, float gscale, float max_norm, void* workspace, float* out2, void* stream);
+
 /* ---------------------------------------------------------------- operator level ---------- */
 /* One residual bottleneck block _Residual(C, C) (models/asn_stacked_hg.py:11-49), forward + backward,
  * NCHW fp32 in/out, parameters in the block's own state_dict order (flat fp32).  Used by the parity

@@ -61,6 +61,11 @@ def build(verbose=False):
 
 _vp, _i, _f, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 
+
+class RmspropOpts(C.Structure):
+    """pa_rmsprop_opts of include/poseadv.h (pass C.byref of it to pa_rmsprop_step_opts)"""
+    _fields_ = [('lr', _f), ('alpha', _f), ('eps', _f), ('momentum', _f), ('weight_decay', _f), ('centered', C.c_int32)]
+
 _PROTOS = {
     'pa_last_error': (C.c_char_p, []),
     'pa_version': (_i, []),
@@ -96,6 +101,9 @@ _PROTOS = {
     'pa_rmsprop_skipped_steps': (_i, [_vp, _vp]),
     'pa_rmsprop_step_state': (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _f, _vp, _vp]),
     'pa_rmsprop_skipped_steps_state': (_i, [_vp, _vp, _vp]),
+    'pa_rmsprop_step_opts': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
+    'pa_grad_norm_workspace_bytes': (_sz, [_sz]),
+    'pa_grad_norm': (_i, [_vp, _sz, _f, _f, _vp, _vp, _vp]),
     'pa_residual_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'pa_residual_fwd_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'pa_conv2d_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -154,6 +154,26 @@ int pa_rmsprop_skipped_steps_state(const int32_t* state, long long* count, void*
     if (!count || !state) return 1;
     TRY(pa_rmsprop_skipped(state, count, ST(s))); return 0;
 }
+// torch.optim.RMSprop's other options and clip_grad_norm_'s coefficient (the reference trains with all of them off, stack-hg.py:51-52:
+// no reference counterpart beyond torch's option set).  An argument error launches nothing.
+int pa_rmsprop_step_opts(const pa_rmsprop_opts* o, float* p, const float* g, float* v, float* buf, float* ga, size_t n, float gscale,
+                         const float* clip_coef, int32_t* state, void* s) {
+    g_err[0] = 0;
+    if (!o || !p || !g || !v || !state) { pa_set_error_msg("pa_rmsprop_step_opts: opts, param, grad, square_avg or state is NULL"); return 1; }
+    if (!(o->momentum >= 0.f) || !(o->weight_decay >= 0.f)) { pa_set_error_msg("pa_rmsprop_step_opts: momentum and weight_decay must be >= 0"); return 1; }
+    if ((o->momentum > 0.f) != (buf != nullptr)) { pa_set_error_msg("pa_rmsprop_step_opts: momentum_buf is required when momentum > 0 and must be NULL otherwise"); return 1; }
+    if ((o->centered != 0) != (ga != nullptr)) { pa_set_error_msg("pa_rmsprop_step_opts: grad_avg is required when centered and must be NULL otherwise"); return 1; }
+    const PaRmspropOpts k = {o->lr, o->alpha, o->eps, o->momentum, o->weight_decay};
+    TRY(pa_launch_rmsprop_opts(k, o->centered != 0, p, g, v, buf, ga, n, gscale, clip_coef, state, ST(s))); return 0;
+}
+size_t pa_grad_norm_workspace_bytes(size_t n) { return pa_grad_norm_workspace_size(n); }
+int pa_grad_norm(const float* g, size_t n, float gscale, float max_norm, void* workspace, float* out2, void* s) {
+    g_err[0] = 0;
+    if (!g || !workspace || !out2) { pa_set_error_msg("pa_grad_norm: grad, workspace or out2 is NULL"); return 1; }
+    if (!(max_norm > 0.f)) { pa_set_error_msg("pa_grad_norm: max_norm must be > 0"); return 1; }
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) { pa_set_error_msg("pa_grad_norm: workspace must be 8-byte aligned (double partial sums)"); return 1; }
+    TRY(pa_launch_grad_norm(g, n, gscale, max_norm, workspace, out2, ST(s))); return 0;
+}
 int pa_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, void* s) {
     TRY(pa_launch_nchw_f32_to_nhwc_bf16(src, reinterpret_cast<bf16*>(dst), B, C, H, W, ST(s))); return 0;
 }

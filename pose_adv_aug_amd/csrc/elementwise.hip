@@ -952,6 +952,154 @@ int pa_launch_rmsprop(float* p, const float* g, float* v, size_t n, float lr, fl
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// The other options of torch.optim.RMSprop (momentum, centered, weight_decay: torch 2.10 _single_tensor_rmsprop) and the coefficient
+// of torch.nn.utils.clip_grad_norm_, beside the kernels above (the reference itself trains with all of them off, stack-hg.py:51-52).
+// Per element, every operation in fp32 and in this order:
+//   gr  = (g * gscale) * coef            coef: ONE device float (pa_launch_grad_norm's out[1]); no multiply without a clip pointer
+//   gr  = gr + wd * p                    only when wd != 0 (a "+ 0 * p" would already turn -0 into +0)
+//   v'  = rmsprop_v(v, gr, alpha)
+//   ga' = alpha ga + (1 - alpha) gr      centered
+//   den = sqrtf(centered ? fmaxf(0, v' - ga' ga') : v') + eps
+//   momentum > 0:  buf' = mom buf + gr / den ;  p' = p - lr buf'          else  p' = p - lr (gr / den)  (rmsprop_p when not centered)
+// fmaxf(0, .) is the ONE deliberate difference from torch: v' - ga'^2 is >= 0 in exact arithmetic (a weighted mean of squares against
+// the square of the same weighted mean), rounding can make it slightly negative, and torch then takes the root of it and returns NaN.
+// The alignment padding of a flat array (p = g = v = buf = ga = 0) stays exactly 0: every term above is then 0 and den = eps > 0.
+// Half-precision build: `state` is the optimizer's {flag, skipped} pair behind the same reset + grad_check_kernel scan as above; a
+// skipped step leaves p, v, buf and ga untouched.
+template <bool MOMENTUM, bool CENTERED>
+__device__ __forceinline__ void rmsprop_opts_update(float& p, float g, float& v, float& buf, float& ga, const PaRmspropOpts& o, float gscale,
+                                                    bool clip, float coef) {
+    float gr = g * gscale;
+    if (clip) gr = gr * coef;
+    if (o.wd != 0.f) gr = gr + o.wd * p;
+    v = rmsprop_v(v, gr, o.alpha);
+    if (!MOMENTUM && !CENTERED) { p = rmsprop_p(p, v, gr, o.lr, o.eps); return; }
+    float den;
+    if (CENTERED) {
+        ga = o.alpha * ga + (1.f - o.alpha) * gr;
+        den = sqrtf(fmaxf(0.f, v - ga * ga)) + o.eps;
+    } else {
+        den = sqrtf(v) + o.eps;
+    }
+    if (MOMENTUM) {
+        buf = o.mom * buf + gr / den;
+        p = p - o.lr * buf;
+    } else {
+        p = p - o.lr * (gr / den);
+    }
+}
+
+template <bool MOMENTUM, bool CENTERED>
+__global__ void rmsprop_opts_kernel(float* p, const float* g, float* v, float* buf, float* ga, size_t n, PaRmspropOpts o, float gscale,
+                                    const float* clip_coef, int* state) {
+#ifdef PA_FP16
+    if (state[0]) {                         // uniform over the grid: every thread reads the same word
+        if (blockIdx.x == 0 && threadIdx.x == 0) state[1] += 1;
+        return;
+    }
+#endif
+    const bool clip = clip_coef != nullptr;
+    const float coef = clip ? clip_coef[0] : 1.f;
+    size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) {
+        f32x4 gg = *reinterpret_cast<const f32x4*>(g + i), vv = *reinterpret_cast<f32x4*>(v + i), pp = *reinterpret_cast<f32x4*>(p + i);
+        f32x4 bb = {0.f, 0.f, 0.f, 0.f}, aa = {0.f, 0.f, 0.f, 0.f};
+        if (MOMENTUM) bb = *reinterpret_cast<f32x4*>(buf + i);
+        if (CENTERED) aa = *reinterpret_cast<f32x4*>(ga + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pj = pp[j], vj = vv[j], bj = bb[j], aj = aa[j];
+            rmsprop_opts_update<MOMENTUM, CENTERED>(pj, gg[j], vj, bj, aj, o, gscale, clip, coef);
+            pp[j] = pj; vv[j] = vj; bb[j] = bj; aa[j] = aj;
+        }
+        *reinterpret_cast<f32x4*>(v + i) = vv;
+        *reinterpret_cast<f32x4*>(p + i) = pp;
+        if (MOMENTUM) *reinterpret_cast<f32x4*>(buf + i) = bb;
+        if (CENTERED) *reinterpret_cast<f32x4*>(ga + i) = aa;
+    }
+    for (; i < n && i + 3 >= n; ++i) {          // tail (at most 3 elements, one thread)
+        float pj = p[i], vj = v[i], bj = MOMENTUM ? buf[i] : 0.f, aj = CENTERED ? ga[i] : 0.f;
+        rmsprop_opts_update<MOMENTUM, CENTERED>(pj, g[i], vj, bj, aj, o, gscale, clip, coef);
+        p[i] = pj; v[i] = vj;
+        if (MOMENTUM) buf[i] = bj;
+        if (CENTERED) ga[i] = aj;
+    }
+}
+
+// buf is used iff o.mom > 0, ga iff centered (the C ABI checks that the pointers match).  With every option off and no clip pointer
+// this IS pa_launch_rmsprop: the same launch, hence the same bits.
+int pa_launch_rmsprop_opts(const PaRmspropOpts& o, bool centered, float* p, const float* g, float* v, float* buf, float* ga, size_t n,
+                           float gscale, const float* clip_coef, int* state, hipStream_t st) {
+    if (n == 0) return 0;
+    const bool mom = o.mom > 0.f;
+    if (!mom && !centered && o.wd == 0.f && !clip_coef) return pa_launch_rmsprop(p, g, v, n, o.lr, o.alpha, o.eps, gscale, state, st);
+    const int blocks = pa_grid_for(n / 4, 256, 2048);
+#ifdef PA_FP16
+    hipLaunchKernelGGL(grad_check_reset_kernel, dim3(1), dim3(1), 0, st, state);
+    hipLaunchKernelGGL(grad_check_kernel, dim3(blocks), dim3(256), 0, st, g, n, state);
+#endif
+    const dim3 grid(blocks), block(256);
+    if (mom && centered) hipLaunchKernelGGL((rmsprop_opts_kernel<true, true>), grid, block, 0, st, p, g, v, buf, ga, n, o, gscale, clip_coef, state);
+    else if (mom) hipLaunchKernelGGL((rmsprop_opts_kernel<true, false>), grid, block, 0, st, p, g, v, buf, ga, n, o, gscale, clip_coef, state);
+    else if (centered) hipLaunchKernelGGL((rmsprop_opts_kernel<false, true>), grid, block, 0, st, p, g, v, buf, ga, n, o, gscale, clip_coef, state);
+    else hipLaunchKernelGGL((rmsprop_opts_kernel<false, false>), grid, block, 0, st, p, g, v, buf, ga, n, o, gscale, clip_coef, state);
+    return (int)hipGetLastError();
+}
+
+// Norm of gscale * g and the clip coefficient, in two launches, without floating-point atomics: the same inputs give the same bits.
+//   1. grad_sqsum_kernel: every workgroup of the capped grid sums ((double)g[i] * (double)gscale)^2 over its grid-stride share in
+//      double (the product of two fp32 values is exact in double) and writes ONE partial;
+//   2. grad_norm_finish_kernel: one workgroup adds the partials in a fixed order, out[0] = (float)sqrt(sum), and
+//      out[1] = fminf(1, max_norm / (out[0] + 1e-6f)) in fp32: the coefficient of torch.nn.utils.clip_grad_norm_.
+// The step kernel reads out[1] on the device: no host synchronisation.
+__device__ __forceinline__ double block_sum_double(double s, double* lds) {     // 256 threads; the result is valid in thread 0
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sqsum_kernel(const float* g, size_t n, float gscale, double* partial) {
+    __shared__ double lds[4];
+    const double sc = (double)gscale;
+    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * 256 * 4;
+    double s = 0.0;
+    for (; i + 3 < n; i += stride) {
+        const f32x4 gg = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const double t = (double)gg[j] * sc; s += t * t; }
+    }
+    for (; i < n && i + 3 >= n; ++i) { const double t = (double)g[i] * sc; s += t * t; }
+    s = block_sum_double(s, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* partial, int nparts, float max_norm, float* out) {
+    __shared__ double lds[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += partial[i];
+    s = block_sum_double(s, lds);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(s);
+        out[0] = norm;
+        out[1] = fminf(1.f, max_norm / (norm + 1e-6f));
+    }
+}
+
+size_t pa_grad_norm_workspace_size(size_t n) { return (size_t)pa_grid_for(n / 4, 256, 2048) * sizeof(double); }
+
+int pa_launch_grad_norm(const float* g, size_t n, float gscale, float max_norm, void* workspace, float* out2, hipStream_t st) {
+    const int blocks = pa_grid_for(n / 4, 256, 2048);
+    double* partial = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(grad_sqsum_kernel, dim3(blocks), dim3(256), 0, st, g, n, gscale, partial);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, st, partial, blocks, max_norm, out2);
+    return (int)hipGetLastError();
+}
+
 // plain streaming copy, 16 bytes per lane, 4 independent loads per thread and iteration: what "just moving the bytes" reaches on this
 // part at a given size (bench.py roofline.floor calibrates with it instead of a framework kernel)
 __global__ __launch_bounds__(256) void copy16_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {

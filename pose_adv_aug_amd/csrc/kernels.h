@@ -134,6 +134,14 @@ int pa_launch_stem_wgrad_reduce(const float* part, int splits, float* dst, hipSt
 
 // ---- optimizer / weight preparation
 int pa_launch_rmsprop(float* p, const float* g, float* v, size_t n, float lr, float alpha, float eps, float gscale, int* state, hipStream_t st);   // state: the optimizer's own {flag, skipped} device pair or NULL (process-wide pair)
+// the step with torch.optim.RMSprop's other options (momentum buffer iff mom > 0, grad_avg iff centered) and an optional clip coefficient
+// read from the device; all off and clip_coef NULL: the launch of pa_launch_rmsprop.  state as above, never NULL in the half-precision build.
+struct PaRmspropOpts { float lr, alpha, eps, mom, wd; };
+int pa_launch_rmsprop_opts(const PaRmspropOpts& o, bool centered, float* p, const float* g, float* v, float* buf, float* ga, size_t n,
+                           float gscale, const float* clip_coef, int* state, hipStream_t st);
+// out2 = {norm of gscale * g, fminf(1, max_norm / (norm + 1e-6f))}: two deterministic launches, double partial sums in workspace
+size_t pa_grad_norm_workspace_size(size_t n);
+int pa_launch_grad_norm(const float* g, size_t n, float gscale, float max_norm, void* workspace, float* out2, hipStream_t st);
 int pa_launch_loss_out(float* acc, float* keep, float* out, float* total, int n, hipStream_t st);      // per-stack losses + their sum out, accumulators cleared
 int pa_launch_copy16(void* dst, const void* src, size_t bytes, hipStream_t st, int form = 0);      // plain 16-B/lane streaming copy (bandwidth calibration)
 int pa_rmsprop_skipped(const int* state, long long* out, hipStream_t st);     // half-precision build: steps skipped for a non-finite gradient

@@ -1,4 +1,4 @@
-"""options/train_options.py of the reference (same flags and defaults)."""
+"""options/train_options.py of the reference (same flags and defaults), and the optimizer options beyond its recipe."""
 from .base_options import BaseOptions, _bool
 
 
@@ -8,6 +8,12 @@ class TrainOptions(BaseOptions):
         p = self.parser
         p.add_argument('--lr', type=float, default=2.5e-4, help='initial learning rate')
         p.add_argument('--agent_lr', type=float, default=5.0e-5, help='initial agent learning rate')
+        # torch.optim.RMSprop's other options and gradient-norm clipping (0 = off: the reference's recipe, stack-hg.py:51-52); the pose
+        # net's and the agent's optimizers get the same values (utils/optim.py)
+        p.add_argument('--momentum', type=float, default=0., help='RMSprop momentum (0: off)')
+        p.add_argument('--weight_decay', type=float, default=0., help='RMSprop weight decay (0: off)')
+        p.add_argument('--centered', type=int, default=0, help='1: centered RMSprop (0: off)')
+        p.add_argument('--clip_grad_norm', type=float, default=0., help='clip the gradient to this 2-norm before the step (0: off)')
         p.add_argument('--bs', type=int, default=12, help='mini-batch size')
         p.add_argument('--load_checkpoint', type=_bool, default=False, help='resume from checkpoint model')
         p.add_argument('--load_checkpoint_pose', type=_bool, default=False, help='use checkpoint model')

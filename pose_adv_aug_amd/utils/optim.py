@@ -1,7 +1,12 @@
 """RMSprop on the engine's flat parameter buffer (reference: torch.optim.RMSprop(net.parameters(),
 lr, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0), stack-hg.py:51-52) with the data-parallel
 gradient exchange folded in: ONE all-reduce of the flat gradient over RCCL per step (replaces
-nn.DataParallel's broadcast/gather/reduce_add, stack-hg.py:49)."""
+nn.DataParallel's broadcast/gather/reduce_add, stack-hg.py:49).
+
+Beyond the reference's recipe: torch.optim.RMSprop's momentum, weight_decay and centered, and the gradient-norm clipping of
+torch.nn.utils.clip_grad_norm_ (max_grad_norm), all inside the engine's own launches (pa_rmsprop_step_opts, pa_grad_norm).  With
+every one of them off, step() is the one pa_rmsprop_step_state call it has always been."""
+import ctypes as C
 import os
 
 import torch
@@ -17,20 +22,40 @@ def _dist_on():
     return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get('POSEADV_FORCE_DIST') == '1')
 
 
+def optim_options(opt):
+    """RMSprop keyword arguments from the command line (options/train_options.py: --momentum --weight_decay --centered
+    --clip_grad_norm, 0 = off)"""
+    clip = float(getattr(opt, 'clip_grad_norm', 0) or 0)
+    return dict(momentum=float(getattr(opt, 'momentum', 0) or 0), weight_decay=float(getattr(opt, 'weight_decay', 0) or 0),
+                centered=bool(getattr(opt, 'centered', 0)), max_grad_norm=clip if clip > 0 else None)
+
+
 class RMSprop(object):
-    def __init__(self, net, lr=2.5e-4, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0, overlap=False):
-        """overlap (pose net, world > 1 only): exchange the gradients of a stack's hourglass (one contiguous 42 % of a 2-stack
+    def __init__(self, net, lr=2.5e-4, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0, centered=False, max_grad_norm=None, overlap=False):
+        """momentum, weight_decay, centered: torch.optim.RMSprop's (torch 2.10 _single_tensor_rmsprop), except that the centered
+        variance max(0, square_avg - grad_avg^2) is clamped where torch returns NaN for a difference that rounding made negative.
+        They live in param_groups[0] and are read at every step, like lr.  max_grad_norm (None = off): the gradient is multiplied by
+        min(1, max_grad_norm / (norm + 1e-6)) as by torch.nn.utils.clip_grad_norm_; the norm is computed on the device and the step
+        reads the coefficient there (no host synchronisation); last_grad_norm() is the device float for logging.
+        overlap (pose net, world > 1 only): exchange the gradients of a stack's hourglass (one contiguous 42 % of a 2-stack
         net) on a communication stream as soon as that stack's backward pass is enqueued, while the earlier stacks and the stem
         still run; the rest follows at the end.  Same sums, same result as the single all-reduce (off by default)."""
-        if momentum != 0 or weight_decay != 0:
-            raise ValueError('the reference uses momentum=0, weight_decay=0')
+        if momentum < 0 or weight_decay < 0:
+            raise ValueError('momentum and weight_decay must be >= 0')
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError('max_grad_norm must be > 0 (None: no clipping)')
         self.net = net
         self._works, self._comm, self._ranges = [], None, {}
         if overlap and hasattr(net, 'num_stacks'):
             net.on_stack_done = self._exchange_stack
         net._ensure_table()
-        self.param_groups = [{'lr': lr, 'alpha': alpha, 'eps': eps, 'momentum': 0, 'weight_decay': 0, 'centered': False}]
+        self.param_groups = [{'lr': lr, 'alpha': alpha, 'eps': eps, 'momentum': momentum, 'weight_decay': weight_decay, 'centered': bool(centered)}]
+        self.max_grad_norm = max_grad_norm
         self.square_avg = torch.zeros_like(net.flat_params)
+        # flat like square_avg, allocated when their option is on (_ensure_state); the norm's scratch and its {norm, coefficient} output
+        self.momentum_buffer = self.grad_avg = self._norm_ws = self._norm_out = None
+        self._clipped = False
+        self._ensure_state(self.param_groups[0])
         # fp16 build: {this gradient is non-finite, steps skipped so far} of THIS optimizer (the pose net's and the agent's step on
         # different streams in the joint stage; a process-wide flag would let one see the other's overflow)
         self._skip_state = torch.zeros(2, dtype=torch.int32, device=net.flat_params.device)
@@ -50,7 +75,6 @@ class RMSprop(object):
         """hook of HourglassNet.loss_and_backward: the backward pass of `stack` has just been enqueued"""
         if not _dist_on():
             return
-        import ctypes as C
         net = self.net
         h = net._net(net._last_B)
         if stack not in self._ranges:
@@ -83,30 +107,69 @@ class RMSprop(object):
         self._works = []
         return 1.0 / dist.get_world_size()
 
+    def _ensure_state(self, g):
+        """momentum_buffer / grad_avg of the options that are on in the param group g (zeros, as torch creates them at the first step)"""
+        if g.get('momentum', 0) > 0 and self.momentum_buffer is None:
+            self.momentum_buffer = torch.zeros_like(self.net.flat_params)
+        if g.get('centered', False) and self.grad_avg is None:
+            self.grad_avg = torch.zeros_like(self.net.flat_params)
+
     def step(self):
         g = self.param_groups[0]
         world_scale = self._finish_exchange() if self._works else self.allreduce_grads()
         gscale = world_scale / _lib.grad_scale()                    # 1/world, and the fp16 build's gradient scale divided out
         n = self.net.flat_params.numel()
-        check(lib().pa_rmsprop_step_state(ptr(self.net.flat_params), ptr(self.net.flat_grads), ptr(self.square_avg), n,
-                                          float(g['lr']), float(g['alpha']), float(g['eps']), float(gscale), ptr(self._skip_state), stream()),
-              'pa_rmsprop_step_state')
+        mom, wd, centered = float(g.get('momentum', 0)), float(g.get('weight_decay', 0)), bool(g.get('centered', False))
+        if mom == 0 and wd == 0 and not centered and self.max_grad_norm is None:          # the reference's recipe: one launch, as ever
+            check(lib().pa_rmsprop_step_state(ptr(self.net.flat_params), ptr(self.net.flat_grads), ptr(self.square_avg), n,
+                                              float(g['lr']), float(g['alpha']), float(g['eps']), float(gscale), ptr(self._skip_state), stream()),
+                  'pa_rmsprop_step_state')
+        else:
+            self._step_opts(g, mom, wd, centered, n, gscale)
         self.steps += 1
         self.net.weights_changed()
         self.net._net(self.net._last_B or self.net.default_batch)      # refresh the bf16 weight copies now
 
+    def _step_opts(self, g, mom, wd, centered, n, gscale):
+        """norm and clip coefficient of the exchanged gradient (max_grad_norm), then the step that reads the coefficient on the device"""
+        self._ensure_state(g)
+        grads, coef = self.net.flat_grads, None
+        if self.max_grad_norm is not None:
+            if self._norm_out is None:
+                self._norm_ws = torch.empty(int(lib().pa_grad_norm_workspace_bytes(n)) // 8, dtype=torch.float64, device=grads.device)
+                self._norm_out = torch.zeros(2, dtype=torch.float32, device=grads.device)
+            check(lib().pa_grad_norm(ptr(grads), n, float(gscale), float(self.max_grad_norm), ptr(self._norm_ws), ptr(self._norm_out), stream()),
+                  'pa_grad_norm')
+            coef = ptr(self._norm_out[1:])
+            self._clipped = True
+        o = _lib.RmspropOpts(float(g['lr']), float(g['alpha']), float(g['eps']), mom, wd, int(centered))
+        check(lib().pa_rmsprop_step_opts(C.byref(o), ptr(self.net.flat_params), ptr(grads), ptr(self.square_avg),
+                                         ptr(self.momentum_buffer) if mom > 0 else None, ptr(self.grad_avg) if centered else None,
+                                         n, float(gscale), coef, ptr(self._skip_state), stream()), 'pa_rmsprop_step_opts')
+
+    def last_grad_norm(self):
+        """The norm of the (averaged, unscaled) gradient of the last step taken with max_grad_norm, before clipping: a 0-dim tensor on
+        the device, so reading it is the caller's synchronisation (at print time); None before the first such step."""
+        return self._norm_out[0] if self._clipped else None
+
     def skipped_steps(self):
         """fp16 build: optimizer steps the engine skipped because the (scaled) gradient held inf / NaN; 0 in the bf16 build"""
-        import ctypes as C
         n = C.c_longlong(0)
         check(lib().pa_rmsprop_skipped_steps_state(ptr(self._skip_state), C.byref(n), stream()), 'pa_rmsprop_skipped_steps_state')
         return int(n.value)
+
+    def _option_state(self, g):
+        self._ensure_state(g)
+        return ([('momentum_buffer', self.momentum_buffer)] if g.get('momentum', 0) > 0 else []) + \
+            ([('grad_avg', self.grad_avg)] if g.get('centered', False) else [])
 
     # torch.optim-compatible (de)serialisation: per-parameter state keyed by index, in parameters() order
     def state_dict(self):
         state = {}
         for i, (name, shape, off, numel, kind) in enumerate(t for t in self.net._table if t[4] == 0):
             state[i] = {'step': self.steps, 'square_avg': self.square_avg[off:off + numel].view(shape).clone()}
+            for key, flat in self._option_state(self.param_groups[0]):          # torch's keys, present when the option is on
+                state[i][key] = flat[off:off + numel].view(shape).clone()
         pg = dict(self.param_groups[0])
         pg['params'] = list(range(len(state)))
         return {'state': state, 'param_groups': [pg]}
@@ -114,9 +177,17 @@ class RMSprop(object):
     def load_state_dict(self, sd):
         """Accepts this class's own files and torch.optim.RMSprop's: `state` is keyed by the entries of
         param_groups[0]['params'] (positions 0..n-1 in current torch, object ids in the reference's torch 0.3), in
-        parameters() order either way.  A missing or mis-shaped entry is reported, never silently dropped."""
+        parameters() order either way.  A missing or mis-shaped entry is reported, never silently dropped.  momentum_buffer and
+        grad_avg are read when the file's param group (else this optimizer's) has the option on; a file without them (written with
+        the option off) leaves them zero, with a warning."""
         import warnings
         params = [t for t in self.net._table if t[4] == 0]
+        group = dict(self.param_groups[0])
+        group.update((k, v) for k, v in sd['param_groups'][0].items() if k != 'params')
+        extra = self._option_state(group)
+        loaded = dict((key, 0) for key, _ in extra)
+        for _, flat in extra:
+            flat.zero_()
         state = sd.get('state', {})
         keys = list(sd['param_groups'][0].get('params', range(len(params))))
         if len(keys) != len(params):
@@ -135,6 +206,14 @@ class RMSprop(object):
                 continue
             self.square_avg[off:off + numel] = v.reshape(-1).to(self.square_avg.device, torch.float32)
             self.steps = int(st.get('step', self.steps))
+            for ekey, flat in extra:
+                e = st.get(ekey)
+                if e is not None and torch.as_tensor(e).numel() == numel:
+                    flat[off:off + numel] = torch.as_tensor(e).reshape(-1).to(flat.device, torch.float32)
+                    loaded[ekey] += 1
+        for ekey, _ in extra:
+            if loaded[ekey] < len(params):
+                warnings.warn('optimizer state: %d of %d parameters had no %s entry (left at zero)' % (len(params) - loaded[ekey], len(params), ekey))
         if missing and state:
             warnings.warn('optimizer state: %d of %d parameters had no square_avg entry (left at their current value)' % (missing, len(params)))
         for k, v in sd['param_groups'][0].items():
