@@ -33,6 +33,12 @@ dz * (x - mean) * invstd, bn_eval_kernel), with u = 2^-24 and these rules (class
       - the finalize over R partial rows: the launch form chains ceil(R / 64) rows per slice, then two 16-wide levels (+ 20); the
         consumer-prologue form (R <= 128) is 8 + 4 deep.  R is at most the statistics capacity max(512, ceil(n / 64)), four times
         that for the backward rows of bn3 in the up blocks (Residual::b3_rows_scale).
+    At C = 512 (the chan-512 legs; re-derived from launch_plan.h, kernels.h and bn_fin.h, nothing changes in D): C / 8 = 64 channel
+    groups fill a wave, so flush_stats shuffles over no level at all (<= 6) and the workgroups tried (512 / 256; 384, 192 and 128 are
+    no multiples of 64) have <= 8 waves (<= 16); the item count per thread is the same formula in C; the row capacity
+    pa_max_stat_rows = max(512, ceil(n / 64)) does not depend on C; and the consumer-prologue finalize, which pa_conv_takes_fin does not
+    admit above 256 input channels, is replaced by the launch form, whose order for R <= 128 rows is the prologue's own (8 + 4 deep,
+    reduce_partial_rows) and for more rows ceil(R / 64) + 20 as above.
   * the backward sum of dz * xhat is written in two forms: per term dz * (x - mean) * invstd (epilogue8, Bwd8, pa_conv_epilogue),
     or per partial row invstd * (sum dz x - mean sum dz) (pa_conv_epilogue_lds_bwd, pa_conv_epilogue_lds_up), which cancels when
     |mean| >> sigma.  The bound covers both: the rounding terms are taken over |dz| (|x - mean| + 2 |mean|), which bounds
@@ -534,11 +540,27 @@ def _child_kw(args):
     return kw
 
 
+def _child_stored(args):
+    """(the arguments without it, run_leg's stored_expected or None) of an optional 'stored=x2' / 'stored=x2,x3' / 'stored=' argument:
+    the kinds a leg expects some block to have stored (x2: dz2, x3: dz3), for the sizes at which no launch stores one of them"""
+    rest = [a for a in args if not a.startswith('stored=')]
+    opt = [a[len('stored='):] for a in args if a.startswith('stored=')]
+    if not opt:
+        return rest, None
+    kinds = [k for k in opt[-1].split(',') if k]
+    assert all(k in ('x2', 'x3') for k in kinds), opt
+    return rest, tuple({'x2': '.x2', 'x3': ''}[k] for k in kinds)
+
+
 if __name__ == '__main__':          # the fp16 legs: tests/test_gpu_bn_exact.py runs this with POSEADV_DTYPE=fp16
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from pose_adv_aug_amd._lib import lib as _l
     assert _l().pa_dtype() == 1, 'run with POSEADV_DTYPE=fp16'
-    worst, fails = run_leg(*[int(a) for a in sys.argv[1:6]], log=lambda s: print(s, flush=True), **_child_kw(sys.argv[6:]))
+    _rest, _stored = _child_stored(sys.argv[6:])
+    _kw = _child_kw(_rest)
+    if _stored is not None:
+        _kw['stored_expected'] = _stored
+    worst, fails = run_leg(*[int(a) for a in sys.argv[1:6]], log=lambda s: print(s, flush=True), **_kw)
     print('FAILURES %d %s' % (len(fails), fails[:20]))
     print('FP16 BN EXACT ' + ('PASSED' if not fails else 'FAILED'), flush=True)
     sys.exit(1 if fails else 0)

@@ -22,7 +22,9 @@ Depth D: the most additions any product passes through.  The release kernels kee
 MFMAs over the reduction (conv_igemm.hip:194/323, conv1x1_tile.hip:195, conv3x3_tile.hip:334/379, conv_wgrad.hip:195,
 conv_wgrad_tile.hip:157/171, pose_ops.hip:137): no split of the reduction across waves.
   * forward and data gradient: D = 32 + ceil(K / 32) + A, where K = Cin * taps (Cout * taps for the data gradient) over the padded
-    channel counts (multiples of 64; 256 for the stem's 7 x 7 x 4 patch) and A the epilogue adds (bias, add1, add2).
+    channel counts (multiples of 64; 256 for the stem's 7 x 7 x 4 patch) and A the epilogue adds (bias, add1, add2).  Nothing in it
+    depends on the channel count beyond K: at chan 512 the generic kernel chains 16 MFMAs (K = 512) or 72 (the 3 x 3 layer, K = 2304)
+    into the same single accumulator (conv_igemm.hip:194), whichever of its tiles <64,64> ... <128,128> the launch takes.
   * weight gradient: a split owns a contiguous (conv_wgrad.hip: steps of 64 / 128 pixels) or strided (conv_wgrad_tile.hip: tiles of
     128 pixels) share of the ceil(M / P) tiles of P <= 128 pixels, at most M / S + 2 P pixels, one MFMA per 32 of them; the slabs of the S
     splits are then chained in split order (wgrad_reduce.h; the stem's reducer: four slices of S / 4 plus three adds, stem_wgrad_reduce_kernel):

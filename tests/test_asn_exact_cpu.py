@@ -295,7 +295,7 @@ def test_loss_bound_holds_and_catches_a_missing_workgroup(B, H):
 def test_oracle_conditioning():
     """the oracle alone stays far inside the degenerate threshold (|mean| / sigma about 10) on the small legs; the figures of all legs
     are recorded in tests/asn_exact.py"""
-    for key in ((128, 4, 256, 53, False), (128, 2, 256, 55, True)):
+    for key in ((128, 4, 256, 53, False), (128, 2, 256, 55, True), (512, 2, 256, 60, False), (512, 2, 256, 61, True)):
         v = A.oracle_conditioning(*key)
         assert abs(v - A.LARGEST_MEAN_OVER_SIGMA[key]) < 0.05 and v < 5.0, (key, v)
     assert max(A.LARGEST_MEAN_OVER_SIGMA.values()) < 5.0

@@ -23,6 +23,9 @@ SHAPES = [
     (3, 96, 96, 64, 256, 1),     # configs[4] geometry, B 3
     (3, 6, 6, 36, 256, 1),       # its masked 6 x 6 neck: one tile per image
     (2, 2, 2, 4, 128, 1),        # tiny maps: the 2 x 2 neck, one image per row
+    (8, 64, 64, 64, 512, 1),     # chan 512, B 8 at 64 x 64: the 64-pixel rows of the row-tile 1 x 1 forward (256 -> 512), beside the generic kernel's 128-pixel rows
+    (2, 32, 32, 16, 512, 4),     # chan 512 tiny maps, up1.x3: 32 rows of 64 pixels in a four-fold capacity; a quarter row dropped
+    (2, 2, 2, 4, 512, 1),        # chan 512 neck of the tiny maps
 ]
 C = 6
 
@@ -252,3 +255,17 @@ def test_masked_merge_checks_pass_the_emulation_and_report_each_defect(dtype, H)
     # the gradient of the masked copy is d merged itself: a ReLU mask there is reported
     r = _masked_checks(vs, vu, dm, M, dtype, dict(e, dmasked=e['dmasked'] * (vs > 0).float()))
     assert r['merge backward'] > 0
+
+
+def test_sum_depth_at_chan_512_and_the_child_arguments():
+    """D of the chan-512 legs is the formula's own (tests/bn_exact.py re-derives its parts for 64 channel groups): the 127-deep row tree
+    dominates the streaming chain at every leg's size, and the finalize part is 8 + 20 up to 32768 pixels.  The optional 'stored='
+    argument of the child-process entry points (which dz kinds a leg expects stored) parses to run_leg's stored_expected."""
+    for n in (2 * 32 * 32, 4 * 64 * 64, 8 * 64 * 64):
+        assert X.sum_depth(n, 512) == 127 + 8 + 20 and X.sum_depth(n, 512, 4) == 127 + 32 + 20
+    assert -(-8 * 64 * 64 * 512 // (8 * 65536)) + 26 == 58 < 127          # the streaming chain of the largest chan-512 map
+    assert X._child_stored(['warm', '370']) == (['warm', '370'], None)
+    assert X._child_stored(['stored=x2']) == ([], ('.x2',))
+    assert X._child_stored(['fresh', 'stored=x2,x3']) == (['fresh'], ('.x2', ''))
+    assert X._child_stored(['fresh', 'stored=']) == (['fresh'], ())
+    assert X._child_kw(X._child_stored(['fresh', '740', 'stored=x2'])[0]) == {'history': 'fresh', 'masks': 740}

@@ -65,7 +65,10 @@ def _data(B, C, N, H, k, seed):
 
 
 # (B, Cin, Cout, H, k): the residual blocks' convs at the net's levels, small batches
-LEVELS = [(2, 128, 128, 32, 3), (2, 256, 128, 16, 1), (2, 128, 256, 16, 1), (3, 128, 128, 24, 3), (2, 128, 128, 4, 3), (3, 128, 128, 6, 3)]
+LEVELS = [(2, 128, 128, 32, 3), (2, 256, 128, 16, 1), (2, 128, 256, 16, 1), (3, 128, 128, 24, 3), (2, 128, 128, 4, 3), (3, 128, 128, 6, 3),
+          # the layers of a chan-512 block: K = 512 (16 chunks of the MFMA's 32), 512 outputs, the 3 x 3 layer at K = 2304 (72 chunks)
+          # (32 wide: the dropped halo tap below sits on column 16)
+          (2, 512, 256, 8, 1), (2, 256, 512, 8, 1), (1, 256, 256, 32, 3)]
 
 
 def _fwd(x, w, b, **kw):
@@ -142,7 +145,7 @@ def emulate_wgrad(x, dy, k, S, drop_split=None, double_split=None, drop_image=No
     return out
 
 
-@pytest.mark.parametrize('B,C,N,H,k', [(2, 128, 128, 16, 3), (3, 128, 256, 24, 1), (2, 64, 64, 32, 1)])
+@pytest.mark.parametrize('B,C,N,H,k', [(2, 128, 128, 16, 3), (3, 128, 256, 24, 1), (2, 64, 64, 32, 1), (2, 512, 256, 16, 1), (2, 256, 256, 16, 3)])
 def test_wgrad_bound_holds_and_catches_a_split_and_an_image(B, C, N, H, k):
     g, x, _, _ = _data(B, C, N, H, k, seed=7 * H + k)
     dy = (torch.randn(B, N, H, H, generator=g, dtype=torch.float64) * 1e-2).to(BF).double()
@@ -198,6 +201,37 @@ def test_split_mirror_knows_the_net_layers_and_refuses_unknown_shapes():
         X.wgrad_splits(100, 10, 10, 96, 64, 1)
     with pytest.raises(ValueError):
         X.wgrad_splits(100, 10, 10, 64, 64, 4)
+
+
+@pytest.mark.parametrize('chan', (128, 512))
+def test_site_lists_name_every_conv_and_batchnorm_of_the_oracle(chan):
+    """What run_leg asserts on the GPU against the engine's state_dict (whose keys are the oracle's: tests/test_modules_cpu.py), here
+    against the oracle's own: conv_names / bn_sites name every conv and BatchNorm of a 2-stack net, at chan 512 as at 128; and the
+    shapes the chan-512 legs are there for -- 512 input channels, the 3 x 3 layer with 256, the inner head's 512 -> 512 and 16 -> 512."""
+    from oracle import model as om
+    from tests import bn_exact
+    sd = om.create_hg(2, 1, 16, chan).state_dict()
+    assert sorted(X.conv_names(2)) == sorted(k[:-len('.weight')] for k in sd if k.endswith('.weight') and sd[k].dim() == 4)
+    assert sorted(p for p, _ in bn_exact.bn_sites(2)) == sorted(k[:-len('.running_mean')] for k in sd if k.endswith('.running_mean'))
+    shape = lambda n: tuple(sd[n + '.weight'].shape)
+    assert shape('hg.0.skip1.0.conv1') == (chan // 2, chan, 1, 1) and shape('hg.1.neck.0.conv2') == (chan // 2, chan // 2, 3, 3)
+    assert shape('hg.0.up4.0.conv3') == (chan, chan // 2, 1, 1) and shape('residual3.adapter') == (chan, 128, 1, 1)
+    assert shape('forth_conv.0') == (chan, chan, 1, 1) and shape('in_conv.0') == (chan, 16, 1, 1) and shape('out_conv.1') == (16, chan, 1, 1)
+
+
+def test_the_chan_512_legs_meet_grouped_splits_and_the_plans_of_8_and_16_blocks():
+    """expect=('group',) of the chan-512 legs (tests/test_gpu_conv_exact.py) from the mirror alone, and the plans those legs are there
+    for: 8 channel blocks for the 1 x 1 layers of a block (128-channel blocks on both sides) and 16 for the head's 512 -> 512; for the
+    3 x 3 layer 16 blocks of 64 x 64 channels where the tile kernel takes the map (>= 48 tiles of 8 x 16) and 36 (2 x 18 blocks of 128
+    over taps * Cin) in the generic plan below that."""
+    assert X.wgrad_plan(2, 32, 32, 512, 256, 1).blocks == 8 and X.wgrad_plan(2, 32, 32, 256, 512, 1).blocks == 8
+    assert X.wgrad_plan(2, 32, 32, 512, 512, 1).blocks == 16
+    assert X.wgrad_plan(4, 64, 64, 256, 256, 9)[:1] + X.wgrad_plan(4, 64, 64, 256, 256, 9)[-1:] == ('tile', 16)
+    assert X.wgrad_plan(2, 32, 32, 256, 256, 9)[:1] + X.wgrad_plan(2, 32, 32, 256, 256, 9)[-1:] == ('generic', 36)
+    for B, H in ((2, 32), (4, 64), (8, 64), (2, 64)):           # the largest hourglass map of each leg
+        assert X.group_splits(B, H, H, 512, 256, 1) > 0 and X.group_splits(B, H, H, 256, 512, 1) > 0, (B, H)
+    assert X.group_splits(2, 32, 32, 256, 256, 9) == 0 and X.group_splits(4, 64, 64, 256, 256, 9) > 0
+    assert X.group_splits(2, 8, 8, 512, 256, 1) == 0            # below three 128-pixel tiles: the generic count
 
 
 def test_the_grouped_split_count_never_exceeds_the_count_of_the_layer_alone():

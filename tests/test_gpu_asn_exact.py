@@ -46,6 +46,28 @@ def test_occlusion_agent_is_exact_at_chan_128():
     _ok(A.run_mask_leg(128, 2, 55))
 
 
+# ---- chan 512: the agent's twelve blocks are 512 -> 256 -> 256 (3 x 3) -> 512 at every level, so every conv1 forward, every 3 x 3
+# launch and every conv3 / conv2 data gradient is the generic K-stepping kernel at K = 512 / 2304 (B 2: <64,64> tiles), every
+# 512-channel BatchNorm is finalized by a launch of its own, pooladd_fwd_kernel and the streaming backward launches run at 64 channel
+# groups, and the heads read 512 features (asn_head_fwd_kernel: C fmas per logit; the mask head: 8 fmas per lane).  No launch of the
+# agent stores dz2 / dz3 at this chan (stored_expected=()): no tile kernel takes these data gradients.
+def test_agent_is_exact_at_chan_512():
+    _ok(A.run_leg(512, 2, 256, 60, expect=('group',), stored_expected=()))
+
+
+def test_occlusion_agent_is_exact_at_chan_512():
+    _ok(A.run_mask_leg(512, 2, 61, expect=('group',), stored_expected=()))
+
+
+def test_agent_is_exact_at_chan_512_in_the_fp16_build():
+    env = dict(os.environ, POSEADV_DTYPE='fp16')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'asn_exact.py'), '512', '2', '256', '62', 'fresh', 'stored='], env=env,
+                       capture_output=True, text=True, timeout=900)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print(r.stdout)
+    assert r.returncode == 0 and 'FP16 ASN EXACT PASSED' in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
 # ---- a history in front of the checked agent step (tests/exact_history.py), at the smallest res the agent accepts
 @pytest.mark.parametrize('history', ('warm', 'after_eval'))
 def test_agent_is_exact_after_a_history(history):

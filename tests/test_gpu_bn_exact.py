@@ -9,7 +9,8 @@ configs[4] geometry (384 x 384: the 24 x 24 / 12 x 12 tiled 3 x 3 variants, the 
 8 values per channel: biased and unbiased variance differ by 14 %); and the IEEE-half build on the configs[4] geometry in a child process.
 Then the tiny-maps size at 1, 3 and 8 stacks (no inner head; a middle stack -- a plain xin<i> with a nonzero gradient arriving from the
 next stack; the configs[4] depth), 3 stacks behind a phased / warm history and in the IEEE-half build, and the step with occlusion masks
-(loss_and_backward(dropout_masks=...), the occlusion agent's training path) at 256 x 256, the smallest size with a 4 x 4 neck."""
+(loss_and_backward(dropout_masks=...), the occlusion agent's training path) at 256 x 256, the smallest size with a 4 x 4 neck.  Last,
+chan 512 (64 channel groups, separate finalize launches) at the sizes of tests/test_gpu_conv_exact.py's chan-512 legs."""
 import os
 import subprocess
 import sys
@@ -91,6 +92,43 @@ def test_every_bn_pool_and_merge_is_exact_in_the_step_after_a_masked_one():
 
 def test_every_bn_pool_merge_and_cell_mask_is_exact_in_a_masked_step_with_a_middle_stack():
     _leg(3, 128, 2, 256, 56, masks=560)
+
+
+# ---- chan 512: C / 8 = 64 channel groups, the most pa_stats_groups_ok admits -- a wave of a streaming kernel is exactly one pixel and
+# flush_stats has no lane left to shuffle with.  pa_conv_takes_fin returns false above 256 input channels, so the BatchNorm in front of
+# every conv1 (512 -> 256) and of every conv3 data gradient (512 gradient channels) is finalized by a launch of its own
+# (bn_finalize_kernel / the backward finalize, reduce_partial_rows in its <= 128-row order) where the nets above use the consumer
+# prologue; the statistics and BatchNorm-backward epilogues run in the generic conv kernel's tiles (tests/test_gpu_conv_exact.py names the
+# tier of each size).  Which blocks store dz2 / dz3: no tile instance takes 512 gradient channels or a 3 x 3 layer with 256, so only the
+# stem's blocks (64 and 128 channels at every chan) can -- their 3 x 3 tile launches at every size (dz2), residual1's conv3 data
+# gradient as a row-tile launch from 12288 pixels (dz3: the 256 x 256 legs, not the 128 x 128 ones).
+@pytest.mark.parametrize('history', ('fresh', 'warm'))
+def test_every_bn_pool_and_merge_is_exact_at_chan_512_on_tiny_maps(history):
+    """2 stacks, chan 512, B 2, 128 x 128: maps 32 x 32 ... 2 x 2, <= 32 partial rows everywhere in the hourglasses (the finalize
+    launches' small-row order), the inner head; 'warm': running estimates and weights from a non-initial state."""
+    _leg(2, 512, 2, 128, 71, stored_expected=('.x2',), history=history)
+
+
+def test_every_bn_pool_and_merge_is_exact_at_chan_512_on_the_64x128_tiles():
+    """1 stack, chan 512, B 4, 256 x 256: M = 16384 at 64 x 64, the generic kernel's <64,128> epilogues (256 rows: the finalize launches'
+    sliced order), streaming launches of 512-thread workgroups."""
+    _leg(1, 512, 4, 256, 72)
+
+
+def test_every_bn_pool_and_merge_is_exact_at_chan_512_on_the_128_row_tiles():
+    """1 stack, chan 512, B 8, 256 x 256: M = 32768 at 64 x 64, the <128,128> / <128,64> epilogues (128-pixel partial rows)."""
+    _leg(1, 512, 8, 256, 73)
+
+
+def test_every_bn_pool_merge_and_cell_mask_is_exact_at_chan_512_in_a_masked_step():
+    """2 stacks, chan 512, B 2, 256 x 256 with occlusion masks: the cell mask's forward and backward launches (with their statistics
+    epilogue) and the masked merges at 64 channel groups."""
+    _leg(2, 512, 2, 256, 74, masks=740)
+
+
+def test_every_bn_pool_and_merge_is_exact_at_chan_512_in_the_fp16_build():
+    """The IEEE-half library on the chan-512 tiny-maps leg, in a child process."""
+    _fp16_child(['2', '512', '2', '128', '75', 'stored=x2'])
 
 
 def _fp16_child(args):

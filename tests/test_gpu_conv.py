@@ -81,6 +81,18 @@ SHAPES = [
     # ... and maps up to 8 x 8 that are neither 8 x 8 nor 4 x 4 (the 6 x 6 necks of configs[4]): one masked 8 x 8 tile per image
     (16, 128, 128, 6, 6, 3),
     (3, 64, 64, 5, 7, 3),
+    # the layers of a chan-512 net: 512 input channels (the most pa_launch_conv admits: 8 K steps of the generic kernel, no tile or one-shot
+    # instance), 512 output channels, the 3 x 3 layer with 256 input channels (K = 2304, no tile instance), weight-gradient plans of 8 / 16
+    # channel blocks.  M < 16384: <64,64> tiles (the 256 -> 512 forward and the 512 -> 256 data gradient take the one-shot kernel)
+    (2, 512, 256, 16, 16, 1),
+    (2, 256, 512, 16, 16, 1),
+    (2, 256, 256, 16, 16, 3),
+    (1, 512, 512, 5, 7, 1),      # ragged M = 35
+    (2, 512, 512, 32, 32, 1),
+    (4, 512, 256, 64, 64, 1),    # M = 16384: <64,128>
+    (8, 512, 256, 64, 64, 1),    # M = 32768: <128,128>
+    (8, 256, 512, 64, 64, 1),    # forward: the row-tile kernel (256 input channels, 512 row tiles); data gradient <128,128>
+    (8, 256, 256, 64, 64, 3),    # <128,128>, nine taps
 ]
 
 

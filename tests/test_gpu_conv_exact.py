@@ -5,7 +5,8 @@ bias or addend or an 8-channel group with its neighbour's constants is a few per
 a failure.
 
 Legs (as tests/test_gpu_bn_exact.py): BASELINE configs[1] at full size; the configs[4] geometry (maps 96 / 48 / 24 / 12 / 6) at B 3; tiny
-maps; the IEEE-half build on the configs[4] geometry in a child process; 1, 3 and 8 stacks; the step with occlusion masks.  Then every shape of tests/test_gpu_conv.SHAPES through pa_conv2d
+maps; the IEEE-half build on the configs[4] geometry in a child process; 1, 3 and 8 stacks; the step with occlusion masks; chan 512 at
+the smallest batch that reaches each tile of the generic kernel.  Then every shape of tests/test_gpu_conv.SHAPES through pa_conv2d
 in all three modes, and the split-count mirror against the library's workspace sizes.
 
 What a leg guards is geometric only: it has the map sizes that conv3x3_tile.hip's dispatch sends to the tiled 24 x 24 / 12 x 12 and masked
@@ -93,6 +94,38 @@ def test_every_conv_is_exact_in_a_masked_step_with_a_middle_stack():
     _leg(3, 128, 2, 256, 66, expect=('group',), masks=660)
 
 
+# ---- chan 512 (C / 8 = 64 channel groups, the most the networks admit).  Not a wider run of the kernels above: no tile or one-shot
+# instance exists for 512 input channels or for a 3 x 3 layer with 256, so every 512 -> 256, 512 -> 512 and 64 -> 512 forward, every
+# 256 -> 512 and 256 -> 256 (3 x 3) data gradient and every 3 x 3 forward is a launch of the generic K-stepping kernel (conv_igemm.hip
+# launch_taps) with the net's BNRELU / LIN2 loads and statistics / BatchNorm-backward epilogues, at K = 512 (8 steps) or 2304; the
+# 256 -> 512 forward and the 512 -> 256 data gradient (256 input channels) take the one-shot kernel below 12288 pixels and the row-tile
+# kernel from there.  The weight-gradient plans have 8 (1 x 1) and 16 (3 x 3) channel blocks.  Each leg is the smallest batch that
+# reaches its tile of the generic kernel (pa_launch_conv: bigM = M >= 32768, <64,128> from M >= 16384 at Cout % 128 == 0); the stem
+# blocks (64 -> 128, 128 -> 128) run as at every chan.
+@pytest.mark.parametrize('history', ('fresh', 'warm'))
+def test_every_conv_is_exact_at_chan_512_on_tiny_maps(history):
+    """2 stacks, chan 512, B 2, 128 x 128: maps 32 x 32 ... 2 x 2, every generic launch on the <64,64> instance (M <= 2048), the inner
+    head (forth_conv 512 -> 512, in_conv 64 -> 512); 'warm': the weight copies repacked by optimizer steps."""
+    _leg(2, 512, 2, 128, 71, expect=('group',), history=history)
+
+
+def test_every_conv_is_exact_at_chan_512_on_the_64x128_tiles():
+    """1 stack, chan 512, B 4, 256 x 256: the 64 x 64 maps have M = 16384, the <64,128> instance of the generic kernel (bigN && M >= 64 * 256)."""
+    _leg(1, 512, 4, 256, 72, expect=('group',))
+
+
+def test_every_conv_is_exact_at_chan_512_on_the_128_row_tiles():
+    """1 stack, chan 512, B 8, 256 x 256: the 64 x 64 maps have M = 32768 (bigM), the <128,128> instance (and <128,64> for out_conv's
+    forward, 512 -> 64) with the net's load and epilogue modes; the 32 x 32 maps (M = 8192) stay on <64,64>."""
+    _leg(1, 512, 8, 256, 73, expect=('group',))
+
+
+def test_every_conv_is_exact_at_chan_512_in_a_masked_step():
+    """2 stacks, chan 512, B 2, 256 x 256 with occlusion masks: the <64,64> instance at M = 8192 behind the cell mask and the masked
+    merges at 64 channel groups; up4 reads maskedneck."""
+    _leg(2, 512, 2, 256, 74, expect=('group',), masks=740)
+
+
 def _fp16_child(args):
     env = dict(os.environ, POSEADV_DTYPE='fp16')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'conv_exact.py')] + args, env=env, capture_output=True, text=True, timeout=900)
@@ -108,6 +141,11 @@ def test_every_conv_is_exact_with_a_middle_stack_in_the_fp16_build():
 
 def test_every_conv_is_exact_in_a_masked_step_in_the_fp16_build():
     _fp16_child(['2', '128', '2', '256', '68', 'fresh', '680'])
+
+
+def test_every_conv_is_exact_at_chan_512_in_the_fp16_build():
+    """The IEEE-half library on the chan-512 tiny-maps leg (2 stacks, B 2, 128 x 128): the generic <64,64> instance at K = 512 / 2304."""
+    _fp16_child(['2', '512', '2', '128', '75'])
 
 
 def test_every_conv_is_exact_after_warm_steps_in_the_fp16_build():
@@ -183,7 +221,13 @@ _TABLES = [48, 56, 56]
     [(24, 256, 128, 64 >> j, 64 >> j, 1) for j in range(5)] + [(24, 128, 128, 64 >> j, 64 >> j, 3) for j in range(5)] +
     [(24, 128, 256, 64 >> j, 64 >> j, 1) for j in range(5)] + [(3, 256, 128, 96 >> j, 96 >> j, 1) for j in range(5)] +
     [(3, 128, 128, 96 >> j, 96 >> j, 3) for j in range(5)] + [(2, 64, 64, 32 >> j, 32 >> j, 3) for j in range(4)] +
-    [(24, 256, 64, 64, 64, 1), (24, 64, 256, 64, 64, 1), (3, 64, 256, 96, 96, 1), (2, 64, 128, 32, 32, 1)])))
+    [(24, 256, 64, 64, 64, 1), (24, 64, 256, 64, 64, 1), (3, 64, 256, 96, 96, 1), (2, 64, 128, 32, 32, 1)] +
+    # the layers of the chan-512 legs: B 2 at 32 x 32 ... 2 x 2, B 2 / 4 / 8 at 64 x 64 ... 4 x 4; residual3 (128 -> 256 -> 512, adapter
+    # 128 -> 512) and the head (512 -> 512, 512 -> 16 and 16 -> 512 padded to 64)
+    [(2, ci, co, 32 >> j, 32 >> j, k) for ci, co, k in ((512, 256, 1), (256, 256, 3), (256, 512, 1)) for j in range(5)] +
+    [(B, ci, co, 64 >> j, 64 >> j, k) for B in (2, 4, 8) for ci, co, k in ((512, 256, 1), (256, 256, 3), (256, 512, 1)) for j in range(5)] +
+    [(B, ci, co, H, H, 1) for B, H in ((2, 32), (2, 64), (4, 64), (8, 64))
+     for ci, co in ((128, 256), (128, 512), (512, 512), (512, 64), (64, 512))])))
 def test_split_mirror_matches_the_library(B, Cin, Cout, H, W, k):
     """S of tests/conv_exact.py (wgrad_plan, the mirror of pa_wgrad_plan) against the split counts the library's workspace sizes reveal:
     pa_conv2d_workspace_bytes lays the layer out without a batch (no grouped split: PaWgradPlan::splits), pa_wgrad_group_workspace_bytes

@@ -55,6 +55,13 @@ def test_two_module_chains_are_exact_in_a_masked_step():
     _leg(2, 2, 128, 2, 256, 84, expect=('group',), masks=840)
 
 
+def test_two_module_chains_are_exact_at_chan_512():
+    """1 stack, 2 modules, chan 512, B 2, 128 x 128: block 1 of every chain reads a 512-channel tensor with a pending BatchNorm that has
+    two readers and no consumer prologue (pa_conv_takes_fin: not above 256 input channels) -- a finalize launch of its own; the generic
+    <64,64> kernel at K = 512 / 2304.  Only the stem's 3 x 3 tile launches store a gradient at this size (dz2)."""
+    _leg(1, 2, 512, 2, 128, 90, expect=('group',), stored_expected=('.x2',))
+
+
 def test_three_module_chains_are_exact_in_the_fp16_build():
     """the 256 x 256 leg in the IEEE-half library, in a child process (one storage type per process)"""
     env = dict(os.environ, POSEADV_DTYPE='fp16')

@@ -446,6 +446,36 @@ def test_network_step_stays_inside_its_workspace():
     L.pa_net_destroy(hp); L.pa_net_destroy(ha)
 
 
+def test_chan_512_network_step_stays_inside_its_workspace():
+    """The layout at chan 512 against its own size query: a 2-stack pose net (chan 512, 128 x 128, B = 2) runs one forward and backward
+    pass inside exactly pa_net_workspace_bytes with 64 MB guard regions on both sides -- the partial rows of the separate finalize
+    launches (no consumer prologue above 256 input channels), the pool-gradient buffers every hourglass level falls back to (no pool
+    routing at 256 gradient channels), the weight-gradient slabs of the 8- / 16-block plans.  The guards stay untouched and every
+    gradient is finite."""
+    from pose_adv_aug_amd._lib import lib, check, ptr, stream
+    L = lib()
+    B, res, chan = 2, 128, 512
+    SL = 64 << 20
+    hp = L.pa_hg_create(2, 16, chan, B, res)
+    assert hp, L.pa_last_error()
+    nws = L.pa_net_workspace_bytes(hp)
+    big = torch.zeros(nws + 2 * SL, dtype=torch.uint8, device='cuda')
+    big[:SL] = 0x5A; big[SL + nws:] = 0x5A
+    P = torch.rand(L.pa_net_param_floats(hp), device='cuda') * 0.1
+    G = torch.zeros_like(P)
+    Bf = torch.ones(max(1, L.pa_net_buffer_floats(hp)), device='cuda')
+    check(L.pa_net_bind(hp, ptr(P), ptr(G), ptr(Bf), C.c_void_p(big.data_ptr() + SL), stream()), 'pa_net_bind')
+    img = torch.rand(B, 3, res, res, device='cuda')
+    pts = (torch.rand(B, 16, 2, device='cuda', dtype=torch.float64) * 28 + 2)
+    loss = torch.empty(2, device='cuda')
+    check(L.pa_hg_forward(hp, ptr(img), None, ptr(pts), 1, ptr(loss)), 'pa_hg_forward')
+    check(L.pa_hg_backward(hp), 'pa_hg_backward')
+    torch.cuda.synchronize()
+    assert bool((big[:SL] == 0x5A).all()) and bool((big[SL + nws:] == 0x5A).all())
+    assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(G).all()) and float(G.abs().max()) > 0
+    L.pa_net_destroy(hp)
+
+
 def test_augmentation_one_step_ahead_changes_nothing():
     """stack_hg.train / bench.py enqueue the NEXT batch's augmentation on a side stream one step ahead (data.AugmentAhead):
     same draws, same crops, same parameters after 4 steps -- bitwise -- as augmenting in front of every step."""

@@ -4,8 +4,9 @@ the first block of the skip branch beside a pool reads the pool's gradient throu
 pool backward kernels recompute (first maximum in scan order, strict >, on the same fp32 values), and the epilogue redoes the one bf16
 rounding of the stored tensor, so the two forms must agree BIT FOR BIT: every comparison here is on the raw bits (NaN-safe), no tolerance.
 
-Chan 256 everywhere, so that the instances of the benchmark run: the one-shot 1x1 kernel below 12288 pixels (every case but the last), the
-row-tile 1x1 kernel from 12288 pixels (B = 3 at 64 x 64: 192 tiles of 64 rows)."""
+Chan 256, so that the instances of the benchmark run: the one-shot 1x1 kernel below 12288 pixels (every case but the last), the
+row-tile 1x1 kernel from 12288 pixels (B = 3 at 64 x 64: 192 tiles of 64 rows).  One case at chan 512, where only the stem's pool can be
+routed and the hourglass pools fall back to a launch each."""
 import ctypes as C
 
 import pytest
@@ -46,13 +47,13 @@ def _images(kind, seed, B, res):
     return img
 
 
-def _train(route, B, res, stacks, modules=1, masks=None, kind='random', want=()):
+def _train(route, B, res, stacks, modules=1, masks=None, kind='random', want=(), chan=256):
     """STEPS training steps from one seed; returns the final state, the last step's gradients and heat maps, and the debug views `want`
     ((name, view) pairs, each read TWICE) of the last step"""
     from pose_adv_aug_amd import _lib
     from pose_adv_aug_amd.models.asn_stacked_hg import create_hg
     from pose_adv_aug_amd.utils.optim import RMSprop
-    net = create_hg(stacks, modules, 16, 256, res=res, default_batch=B); net.reset_parameters(seed=7); net.train()
+    net = create_hg(stacks, modules, 16, chan, res=res, default_batch=B); net.reset_parameters(seed=7); net.train()
     h = net._net(B)
     _lib.check(_lib.lib().pa_net_set_pool_route(h, 1 if route else 0), 'pa_net_set_pool_route')
     opt = RMSprop(net, lr=2.5e-4)
@@ -145,6 +146,28 @@ def test_requested_tensors_are_what_the_unrouted_step_stored(res, stacks):
     # the routed gradient is three quarters zero at least: at most one position of a window takes it (level 2: no addend)
     g = on['views'][1][0]
     assert float((g != 0).float().mean()) <= 0.25
+
+
+def test_chan_512_routes_the_stem_pool_only_and_gives_the_same_bits():
+    """The mixed state: 1 stack, chan 512, B 2, 256 x 256.  The hourglass pools cannot be routed -- the skip block's conv1 data gradient has
+    256 gradient channels and pa_conv_pool_route_supported needs 128 (Hourglass::route_ok) -- so each level falls back to a pool backward
+    launch into poolgrad<k>, although the forward pools still store their arg-max maps; the stem's pool is routed as at every chan
+    (residual1 is 64 -> 128).  Every compared tensor is bit-identical, and hg0.poolgrad1..4, which the routed step stored itself here,
+    equal what the unrouted step stored."""
+    want = [('hg0.poolgrad%d' % k, 2) for k in (1, 2, 3, 4)] + [('res1', 1), ('res1', 3), ('res1', 4)]
+    c = dict(B=2, res=256, stacks=1, chan=512, want=want)
+    off, on = _train(False, **c), _train(True, **c)
+    # pa_net_design_bytes: Net::stem_route_ok holds at this size whatever the chan -- residual1's conv3 data gradient (128 gradient channels,
+    # 64 outputs, 2 * 128 * 128 = 32768 pixels = 512 row tiles >= 192) is a launch pa_conv_pool_in_supported admits, and the pool's statistics
+    # launch is planned over 128 channels -- so the routed step skips the write and the re-read of residual1's full-resolution gradient and
+    # _compare's STRICT assertion applies (read and written bytes both smaller), as for the cases above; 'not greater' would be the
+    # assertion of a size whose stem pool is not routed either (res 128).
+    _compare(off, on)
+    for (name, view), (o1, o2), (r1, r2) in zip(want, off['views'], on['views']):
+        assert _same(o1, o2) and _same(r1, r2), '%s: a second request returned something else' % name
+        assert _same(o1, r1), '%s differs (%d of %d elements)' % (name, int((_bits(o1) != _bits(r1)).sum()), o1.numel())
+        assert float(o1.abs().max()) > 0, name
+    assert float((on['views'][1][0] != 0).float().mean()) <= 0.25          # level 2: no addend, one position of a window at the most
 
 
 def test_routed_step_stays_inside_its_workspace():

@@ -55,7 +55,8 @@ def _table(L, h):
     return rows
 
 
-@pytest.mark.parametrize('stacks,modules,chan,entries', [(1, 2, 128, 671), (2, 3, 128, 1860), (2, 2, 256, 1272)])
+@pytest.mark.parametrize('stacks,modules,chan,entries', [(1, 2, 128, 671), (2, 3, 128, 1860), (2, 2, 256, 1272), (1, 2, 512, 671),
+                                                        (2, 1, 512, 684)])
 def test_tensor_table_is_the_oracles_state_dict(stacks, modules, chan, entries):
     """names, shapes and order of pa_net_tensor_info == the oracle's state_dict (the reference's registration order: the blocks
     <site>.0 .. <site>.<modules-1> of a site one after the other); the parameter count is the oracle's, rounded up to 4."""
