@@ -40,6 +40,11 @@ int pa_gaussian_heatmap(const double* pts, float* out, int B, int J, int H, int 
 /* Criterion.weighted_L2 (pylib/Criterion.py:12-18); weight may be NULL (== 1), which is the inline
  * loss term of stack-hg.py:156-159.  *loss (fp32, device) is ACCUMULATED into: zero it first. */
 int pa_weighted_l2(const float* pred, const float* gt, const float* weight, size_t n, float* loss, void* stream);
+/* d/dpred of pa_weighted_l2: dpred[e] = 2 * (weight ? weight[e] : 1) * (pred[e] - gt[e]) * (*gout_dev) / n ;
+ * gout_dev: ONE device float (the gradient arriving at the loss; no host synchronisation).  dpred is overwritten; it may be pred
+ * itself.  pred, gt, gout_dev or dpred == NULL is an error. */
+int pa_weighted_l2_grad(const float* pred, const float* gt, const float* weight, size_t n, const float* gout_dev,
+                        float* dpred, void* stream);
 
 /* Evaluation.get_preds (pylib/Evaluation.py:6-23): maps [B][J][H][W] fp32 -> preds [B][J][2]
  * (1-based x, y; zero where the maximum is <= 0).  maxval [B][J] may be NULL. */
@@ -361,6 +366,21 @@ int pa_hg_train_step(pa_net* net, const void* img4, const double* pts, int train
  * sum_stacks loss there -- `loss = sum(criterion(o, target))` of stack-hg.py:156-159 as one device scalar, so that the caller needs no
  * reduction launch of its own between the backward pass and the optimizer. */
 int pa_hg_set_loss_total(pa_net* net, float* total_dev);
+
+/* The backward pass from heat-map gradients of the caller's own loss (any loss of the heat maps: weighted, mined, distilled ...)
+ * instead of the built-in MSE against the Gaussian target.
+ * layout 0: [B][16][H][W] fp32 (what pa_hg_heatmap_nchw returns); 1: [B][H*W][16] fp32 (pa_hg_heatmap_nhwc's).
+ * grads_host: HOST array of num_stacks DEVICE pointers, copied at the call; a NULL entry = zero gradient for that stack;
+ * grads_host == NULL switches the door off (the built-in MSE gradient again).
+ * Sticky, like pa_hg_set_dropout_masks: while set, pa_hg_backward and every pa_hg_backward_phase form stack i's heat-map gradient as
+ *   storage(G_i * pa_grad_scale() (+ in_conv's data gradient for an inner stack))
+ * in one launch per stack (the launch the MSE gradient takes otherwise) and run the unchanged backward pass from there; the gradients
+ * are passed UNSCALED (the half-precision build applies its scale here; a value that leaves half's range becomes inf and the optimizer
+ * skips that step like any overflow).  The joints (`pts`) are not read: a forward pass without them is enough.  The buffers are read in
+ * stream order by the backward pass: keep them alive until it has run.  Works in train and eval mode and together with dropout masks.
+ * Errors (nothing changes): an agent, a layout other than 0 / 1, every entry NULL, a pointer that is not 16-byte aligned; and
+ * pa_hg_train_step(use_graph != 0) is refused while gradients are set. */
+int pa_hg_set_heat_grads(pa_net* net, const float* const* grads_host, int layout);
 
 /* Half-hourglass forward (models/asn_stacked_hg.py:300-304 with is_half_hg): stem + the down path of
  * hg[0] up to the neck -- everything the agent reads.  train != 0 updates the BatchNorm running

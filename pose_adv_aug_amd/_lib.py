@@ -73,6 +73,7 @@ _PROTOS = {
     'pa_dtype': (_i, []),
     'pa_gaussian_heatmap': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'pa_weighted_l2': (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    'pa_weighted_l2_grad': (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     'pa_get_preds': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'pa_final_preds': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'pa_get_preds_nhwc': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
@@ -138,6 +139,7 @@ _PROTOS = {
     'pa_hg_bucket_wait': (_i, [_vp, _i, _vp]),
     'pa_hg_train_step': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     'pa_hg_set_loss_total': (_i, [_vp, _vp]),
+    'pa_hg_set_heat_grads': (_i, [_vp, C.POINTER(_vp), _i]),
     'pa_hg_accuracy': (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     'pa_hg_forward_half': (_i, [_vp, _vp, _vp, _i]),
     'pa_asn_forward': (_i, [_vp, _vp, _i, _vp, _vp]),

@@ -566,6 +566,30 @@ int pa_hg_set_dropout_masks(pa_net* net, const float* masks) {
     return 0;
 }
 
+int pa_hg_set_heat_grads(pa_net* net, const float* const* grads_host, int layout) {
+    g_err[0] = 0;
+    Net& n = net->n;
+    if (n.is_agent) { pa_set_error_msg("pa_hg_set_heat_grads: not a pose net"); return 1; }
+    if (!grads_host) { n.heat_grads_on = false; n.heat_grads.clear(); return 0; }
+    if (layout != 0 && layout != 1) { pa_set_error_msg("pa_hg_set_heat_grads: layout must be 0 ([B][16][H][W]) or 1 ([B][H*W][16])"); return 1; }
+    bool any = false;
+    for (int i = 0; i < n.stacks; ++i) {
+        any = any || grads_host[i] != nullptr;
+        if (reinterpret_cast<uintptr_t>(grads_host[i]) & 15) { pa_set_error_msg("pa_hg_set_heat_grads: every gradient must be 16-byte aligned"); return 1; }
+    }
+    if (!any) { pa_set_error_msg("pa_hg_set_heat_grads: every entry is NULL (pass grads_host == NULL to switch the given gradients off)"); return 1; }
+    n.heat_grads.assign(grads_host, grads_host + n.stacks);
+    n.heat_grads_layout = layout;
+    n.heat_grads_on = true;
+    return 0;
+}
+
+int pa_weighted_l2_grad(const float* pred, const float* gt, const float* weight, size_t n, const float* gout_dev, float* dpred, void* s) {
+    g_err[0] = 0;
+    if (!pred || !gt || !gout_dev || !dpred) { pa_set_error_msg("pa_weighted_l2_grad: pred, gt, gout_dev and dpred must not be NULL"); return 1; }
+    TRY(pa_launch_weighted_l2_grad(pred, gt, weight, n, gout_dev, dpred, ST(s))); return 0;
+}
+
 int pa_hg_forward_half(pa_net* net, const float* img, const void* img4, int train) {
     g_err[0] = 0;
     if (!img && !img4) { pa_set_error_msg("pa_hg_forward_half: need img or img4"); return 1; }
@@ -687,6 +711,8 @@ int pa_hg_train_step(pa_net* net, const void* img4, const double* pts, int train
     g_err[0] = 0;
     Net& n = net->n;
     if (!img4 || !pts) { pa_set_error_msg("pa_hg_train_step: img4 and pts are required"); return 1; }
+    // (a captured graph holds the pointers of its capture: the same rule as for dropout masks, refused before anything is enqueued)
+    if (use_graph && n.heat_grads_on) { pa_set_error_msg("pa_hg_train_step: no captured graph while heat-map gradients are set (pa_hg_set_heat_grads)"); return 1; }
     if (!use_graph) {
         TRY(n.forward_pose(nullptr, reinterpret_cast<const bf16*>(img4), pts, train != 0, loss_per_stack));
         return n.backward_pose();

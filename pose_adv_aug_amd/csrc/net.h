@@ -254,6 +254,11 @@ struct Net {
     // occlusion (dropout) branch, reference :172-190: [B][16] cell masks (caller-owned device memory) applied to the neck and the
     // four skip tensors of every stack in forward_pose / backward_pose; nullptr = off
     const float* drop_mask = nullptr;
+    // d loss / d heat given by the caller (pa_hg_set_heat_grads): while on, backward_stack(i) takes heat_grads[i] (caller-owned device
+    // memory, nullptr = zero) through pa_launch_heat_inject instead of the built-in MSE gradient (heat_grad_kernel); pts_dev is not read
+    std::vector<const float*> heat_grads;
+    int heat_grads_layout = 0;                  // 0: [B][16][H][W], 1: [B][H*W][16]
+    bool heat_grads_on = false;
 
     // ---- declaration helpers
     size_t add_param(const std::string& name, std::initializer_list<int> shape);

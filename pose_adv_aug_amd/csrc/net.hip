@@ -642,6 +642,10 @@ template <class... A> static int c_heat_grad(Net& n, const float* heat, const do
     const double M = (double)n.B * (n.res / 4) * (n.res / 4); n.cnt(M * 16 * 4 + (din ? M * 64 * 2 : 0.0), M * 64 * 2);
     return pa_launch_heat_grad(heat, pts, din, rest...);
 }
+template <class... A> static int c_heat_inject(Net& n, const float* G, int layout, const bf16* din, A... rest) {
+    const double M = (double)n.B * (n.res / 4) * (n.res / 4); n.cnt((G ? M * 16 * 4 : 0.0) + (din ? M * 64 * 2 : 0.0), M * 64 * 2);
+    return pa_launch_heat_inject(G, layout, din, rest...);
+}
 
 // ------------------------------------------------------------------------------------------------
 // a scope whose launches go to stream `s` (a side branch)
@@ -1035,7 +1039,11 @@ int Net::backward_stack(int i) {
         TRY(conv_dgrad(inc[i], gx, B, Hh, Hh, pa_none(), pa_none(), ep_plain(), dheat_in[i]));
         TRY(conv_wgrad(forth[i], gx, op(lin_out[i]), B, Hh, Hh));
     }
-    TRY(c_heat_grad(*this, heat[i], pts_dev, inner ? dheat_in[i] : nullptr, dheat64[i], gscale, B, Hh, Hh, st));
+    if (heat_grads_on) {        // the caller's gradient (pa_hg_set_heat_grads), unscaled: only the half-precision build's PA_GRAD_SCALE is applied
+        TRY(c_heat_inject(*this, heat_grads[i], heat_grads_layout, inner ? dheat_in[i] : nullptr, dheat64[i], PA_GRAD_SCALE, B, Hh, Hh, st));
+    } else {
+        TRY(c_heat_grad(*this, heat[i], pts_dev, inner ? dheat_in[i] : nullptr, dheat64[i], gscale, B, Hh, Hh, st));
+    }
     const PaOperand gh = pa_plain(dheat64[i]);
     TRY(conv_wgrad(outc[i], gh, op(lin_out[i]), B, Hh, Hh));
     if (inner) {

@@ -8,6 +8,9 @@ int pa_launch_head_fwd(const PaOperand& in, const bf16* w16, const float* bias, 
                        const double* pts, float* loss, int B, int H, int W, int Cin, hipStream_t st);
 int pa_launch_heat_grad(const float* heat, const double* pts, const bf16* add64, bf16* dheat64, float gscale,
                         int B, int H, int W, hipStream_t st);
+// G: the caller's d loss / d heat (layout 0 [B][16][H][W], 1 [B][H*W][16]; nullptr = zero), 16-byte aligned; layout 0 needs H * W % 256 == 0
+int pa_launch_heat_inject(const float* G, int layout, const bf16* add64, bf16* dheat64, float scale, int B, int H, int W, hipStream_t st);
+int pa_launch_weighted_l2_grad(const float* pred, const float* gt, const float* w, size_t n, const float* gout, float* dpred, hipStream_t st);
 int pa_launch_argmax(const float* maps, long sb, long sj, long sp, int B, int J, int H, int W, float* preds, float* maxval,
                      hipStream_t st);
 int pa_launch_final_preds(const float* maps, long sb, long sj, long sp, const float* coords, const float* center, const float* scale,

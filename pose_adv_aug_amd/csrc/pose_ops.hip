@@ -212,6 +212,122 @@ int pa_launch_heat_grad(const float* heat, const double* pts, const bf16* add64,
     return (int)hipGetLastError();
 }
 
+// d loss / d heat GIVEN by the caller (pa_hg_set_heat_grads) in place of the built-in MSE gradient: the same output as heat_grad_kernel,
+// dheat64[m][0..15] = storage(G * scale (+ add64)), channels 16..63 untouched; G == nullptr is a zero gradient.  No atomics, every element
+// is written by one thread from its own operands: the same input gives the same bits.
+// Joint-minor G [B][H*W][16] (the layout of the engine's own heat maps): heat_grad_kernel's mapping, one 16-byte load per lane.
+__global__ void heat_inject_nhwc_kernel(const float* G, const bf16* add64, bf16* dheat64, float scale, int M) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < (size_t)M * 4; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t m = t >> 2;
+        const int q = (int)(t & 3);
+        f32x4 gv = {0.f, 0.f, 0.f, 0.f};
+        if (G) gv = *reinterpret_cast<const f32x4*>(G + m * 16 + q * 4);
+        bf16x4 o;
+        bf16x4 ad;
+        if (add64) ad = *reinterpret_cast<const bf16x4*>(add64 + m * 64 + q * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float g = gv[j] * scale;
+            if (add64) g += (float)ad[j];
+            o[j] = (bf16)g;
+        }
+        *reinterpret_cast<bf16x4*>(dheat64 + m * 64 + q * 4) = o;
+    }
+}
+
+// Planar G [B][16][H*W] (what pa_hg_heatmap_nchw returns).  The four joints of a lane of the mapping above would lie H*W floats apart (64
+// different lines per load of a wave), so the tile is read the way it is stored: one workgroup = 256 consecutive pixels of ONE sample (H*W is
+// a multiple of 256: a tile never crosses a sample), wave w reads the planes of joints w, w + 4, w + 8, w + 12 -- per plane 64 lanes x 16 bytes
+// = 1 KiB of consecutive x -- and stores them to LDS as read ([16][256] floats, ds_write_b128 at consecutive addresses).  Then thread p owns
+// pixel p: 16 reads down a column of the tile (consecutive lanes on consecutive banks), the addend as two 16-byte loads, the 16 joints
+// as two 16-byte stores.
+#define PA_INJECT_TILE 256
+__global__ __launch_bounds__(PA_INJECT_TILE) void heat_inject_nchw_kernel(const float* G, const bf16* add64, bf16* dheat64, float scale, int HW) {
+    __shared__ __attribute__((aligned(16))) float tile[16][PA_INJECT_TILE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t m0 = (size_t)blockIdx.x * PA_INJECT_TILE;          // first pixel of the tile, over all samples
+    const size_t b = m0 / HW, p0 = m0 - b * HW;
+    if (G) {
+        f32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(G + (b * 16 + u * 4 + wave) * HW + p0 + lane * 4);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<f32x4*>(&tile[u * 4 + wave][lane * 4]) = v[u];
+        __syncthreads();
+    }
+    const size_t m = m0 + threadIdx.x;
+    bf16x8 ad[2];
+    if (add64) {
+        ad[0] = *reinterpret_cast<const bf16x8*>(add64 + m * 64);
+        ad[1] = *reinterpret_cast<const bf16x8*>(add64 + m * 64 + 8);
+    }
+    bf16x8 o[2];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        float g = (G ? tile[j][threadIdx.x] : 0.f) * scale;
+        if (add64) g += (float)ad[j >> 3][j & 7];
+        o[j >> 3][j & 7] = (bf16)g;
+    }
+    *reinterpret_cast<bf16x8*>(dheat64 + m * 64) = o[0];
+    *reinterpret_cast<bf16x8*>(dheat64 + m * 64 + 8) = o[1];
+}
+
+int pa_launch_heat_inject(const float* G, int layout, const bf16* add64, bf16* dheat64, float scale, int B, int H, int W, hipStream_t st) {
+    const int HW = H * W;
+    const size_t M = (size_t)B * HW;
+    if ((reinterpret_cast<uintptr_t>(G) & 15) != 0) { pa_set_error_msg("pa_launch_heat_inject: the gradient must be 16-byte aligned"); return 1; }
+    if (layout == 1) {
+        int blocks = (int)((M * 4 + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(heat_inject_nhwc_kernel, dim3(blocks), dim3(256), 0, st, G, add64, dheat64, scale, (int)M);
+        return (int)hipGetLastError();
+    }
+    if (layout != 0 || HW % PA_INJECT_TILE != 0) { pa_set_error_msg("pa_launch_heat_inject: layout 0 needs H * W % 256 == 0; layouts are 0 and 1"); return 1; }
+    hipLaunchKernelGGL(heat_inject_nchw_kernel, dim3((unsigned)(M / PA_INJECT_TILE)), dim3(PA_INJECT_TILE), 0, st, G, add64, dheat64, scale, HW);
+    return (int)hipGetLastError();
+}
+
+// d/dpred of weighted_l2_kernel's loss: dpred[e] = (w ? w[e] : 1) * (pred[e] - gt[e]) * coef, coef = 2 * gout / n formed once per thread
+// (the quotient in double, rounded once: n itself need not be an fp32 value).  Streaming, 16 bytes per lane; VEC = false (a buffer that
+// is not 16-byte aligned) runs the scalar loop over everything.
+template <bool VEC>
+__global__ void weighted_l2_grad_kernel(const float* pred, const float* gt, const float* w, size_t n, const float* gout, float* dpred) {
+    const float coef = (float)(2.0 * (double)gout[0] / (double)n);
+    if (VEC) {
+        size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+        const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
+        for (; i + 3 < n; i += stride) {
+            const f32x4 p = *reinterpret_cast<const f32x4*>(pred + i), g = *reinterpret_cast<const f32x4*>(gt + i);
+            f32x4 ww = {1.f, 1.f, 1.f, 1.f};
+            if (w) ww = *reinterpret_cast<const f32x4*>(w + i);
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const float d = p[j] - g[j]; o[j] = (w ? ww[j] * d : d) * coef; }
+            *reinterpret_cast<f32x4*>(dpred + i) = o;
+        }
+        for (; i < n && i + 3 >= n; ++i) {          // tail (at most 3 elements, one thread)
+            const float d = pred[i] - gt[i];
+            dpred[i] = (w ? w[i] * d : d) * coef;
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+            const float d = pred[i] - gt[i];
+            dpred[i] = (w ? w[i] * d : d) * coef;
+        }
+    }
+}
+
+int pa_launch_weighted_l2_grad(const float* pred, const float* gt, const float* w, size_t n, const float* gout, float* dpred, hipStream_t st) {
+    if (n == 0) return 0;
+    const bool vec = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(w) |
+                       reinterpret_cast<uintptr_t>(dpred)) & 15) == 0;
+    size_t blocks = ((vec ? (n + 3) / 4 : n) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (vec) hipLaunchKernelGGL(weighted_l2_grad_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, pred, gt, w, n, gout, dpred);
+    else hipLaunchKernelGGL(weighted_l2_grad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, gt, w, n, gout, dpred);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // arg-max (reference pylib/Evaluation.py:6-23) + quarter-pixel refinement and back-projection
 // (:169-211, :240-248).  One wavefront per (sample, joint) map; element (b,j,p) lives at

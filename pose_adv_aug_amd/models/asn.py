@@ -28,6 +28,7 @@ class ASN(_HipModule):
         B = x.shape[0] if x is not None else img4.shape[0]
         hp = pose._net(B)
         pose._last_B = B
+        pose._fwd_serial += 1                   # (the half forward overwrites the activations a pending forward_autograd would read)
         xin = x.contiguous().float() if x is not None else None
         mode = (1 if update_running else 2) if pose.training else 0
         check(lib().pa_hg_forward_half(hp, ptr(xin), ptr(img4), mode), 'pa_hg_forward_half')
@@ -62,6 +63,7 @@ class ASN(_HipModule):
         B = x.shape[0] if x is not None else img4.shape[0]
         hp, ha = pose._net(B), self._net(B)
         pose._last_B = B
+        pose._fwd_serial += 1                   # (the half forward overwrites the activations a pending forward_autograd would read)
         xin = x.contiguous().float() if x is not None else None
         check(lib().pa_hg_forward_half(hp, ptr(xin), ptr(img4), 1 if pose.training else 0), 'pa_hg_forward_half')
         if pose.training:

@@ -189,6 +189,31 @@ def _is_bn_name(name):
     return mod == '1' and '.linear.' in '.' + name        # linear.<i>.1 is the BatchNorm of the Sequential
 
 
+class _HeatMapsFunction(torch.autograd.Function):
+    """HourglassNet.forward_autograd: the engine's forward pass as ONE autograd node with num_stacks outputs.  `anchor` is the module's
+    private one-element leaf (requires_grad): it makes the outputs part of a graph; it gets no gradient -- the parameter gradients go
+    to net.flat_grads through HourglassNet.backward()."""
+
+    @staticmethod
+    def forward(ctx, anchor, net, x, img4, pts, dropout_masks):
+        outs = net._forward(x, img4, pts, dropout_masks)
+        ctx.net, ctx.serial, ctx.done = net, net._fwd_serial, False
+        ctx.set_materialize_grads(False)                # a stack the loss does not use arrives as None = zero, not as a tensor of zeros
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        net = ctx.net
+        if ctx.done:
+            raise RuntimeError('forward_autograd: backward ran a second time for the same forward pass (the engine keeps no graph to retain)')
+        if net._fwd_serial != ctx.serial:
+            raise RuntimeError('forward_autograd: another forward pass of this net has run since these heat maps were made; '
+                               'its stored activations are gone')
+        ctx.done = True
+        net.backward(grads)
+        return (None,) * 6
+
+
 class HourglassNet(_HipModule):
     """_Hourglass_Wrapper of the reference (models/asn_stacked_hg.py:215-342)."""
 
@@ -243,10 +268,15 @@ class HourglassNet(_HipModule):
         check(lib().pa_hg_set_dropout_masks(h, ptr(m)), 'pa_hg_set_dropout_masks')
         return m
 
+    _last_masks = None       # the dropout masks of the last forward pass (backward() sets them again around its pass)
+    _fwd_serial = 0          # counts the forward passes (whole or half) of this net: forward_autograd's backward needs ITS pass's activations
+
     def _forward(self, x, img4, pts, dropout_masks=None):
         B = x.shape[0] if x is not None else img4.shape[0]
         h = self._net(B)
         self._last_B = B
+        self._fwd_serial += 1
+        self._last_masks = dropout_masks
         p = pts.to(torch.float64).contiguous() if pts is not None else None
         losses = torch.empty(self.num_stacks, dtype=torch.float32, device=self.flat_params.device) if pts is not None else None   # (fully overwritten)
         keep = self._set_masks(h, dropout_masks)
@@ -289,6 +319,8 @@ class HourglassNet(_HipModule):
         B = x.shape[0] if x is not None else img4.shape[0]
         h = self._net(B)
         self._last_B = B
+        self._fwd_serial += 1
+        self._last_masks = dropout_masks
         p = pts.to(torch.float64).contiguous()
         losses = torch.empty(self.num_stacks, dtype=torch.float32, device=self.flat_params.device)      # the engine copies every entry
         self._last_losses = losses                                  # per-stack values of this step (the returned loss is their sum)
@@ -316,14 +348,8 @@ class HourglassNet(_HipModule):
                     self.after_forward_result = after_forward()
                 finally:
                     check(lib().pa_net_meters_async(h, 0), 'pa_net_meters_async')
-            if self.on_stack_done is not None:                  # the backward pass in phases: a finished stack's gradients can travel
-                for phase in range(self.num_stacks + 1):
-                    check(lib().pa_hg_backward_phase(h, phase), 'pa_hg_backward_phase')
-                    if phase < self.num_stacks:
-                        self.on_stack_done(self.num_stacks - 1 - phase)
-            else:
-                check(lib().pa_hg_backward(h), 'pa_hg_backward')
-            self._meter_keep = None                             # (the backward pass has enqueued the join: later users of these blocks are ordered behind the meters)
+            self._run_backward(h)
+            self._meter_keep = None                            # (the backward pass has enqueued the join: later users of these blocks are ordered behind the meters)
             outs = self.heatmaps(B) if want_outputs else None
         finally:
             lib().pa_hg_set_loss_total(h, None)
@@ -335,6 +361,69 @@ class HourglassNet(_HipModule):
                 torch.cuda.synchronize()
                 self._meter_keep = None
         return total.view(()), outs
+
+    def _run_backward(self, h):
+        if self.on_stack_done is not None:                  # the backward pass in phases: a finished stack's gradients can travel
+            for phase in range(self.num_stacks + 1):
+                check(lib().pa_hg_backward_phase(h, phase), 'pa_hg_backward_phase')
+                if phase < self.num_stacks:
+                    self.on_stack_done(self.num_stacks - 1 - phase)
+        else:
+            check(lib().pa_hg_backward(h), 'pa_hg_backward')
+
+    def backward(self, grad_outputs, layout='nchw'):
+        """The hand-written backward pass of the LAST forward pass from the caller's d loss / d heat maps (pa_hg_set_heat_grads) instead
+        of the built-in MSE gradient: any loss of the heat maps trains the net.  grad_outputs: a sequence of num_stacks fp32 GPU tensors
+        [B][16][res/4][res/4] ('nchw', the shape forward() returns) or [B][res/4][res/4][16] ('nhwc'); None = zero for that stack.
+        UNSCALED gradients (the engine applies _lib.grad_scale()); the parameter gradients land in flat_grads like loss_and_backward's,
+        in phases with on_stack_done when an overlapping optimizer is attached.  A wrong count, shape, dtype or device raises ValueError
+        before anything is launched."""
+        require_gpu()
+        if layout not in ('nchw', 'nhwc'):
+            raise ValueError("layout must be 'nchw' or 'nhwc', got %r" % (layout,))
+        grads = list(grad_outputs)
+        if len(grads) != self.num_stacks:
+            raise ValueError('backward: %d gradients for %d stacks' % (len(grads), self.num_stacks))
+        if self._last_B is None:
+            raise PoseAdvError('backward: no forward pass has run')
+        B, Hh = self._last_B, self.res // 4
+        want = (B, 16, Hh, Hh) if layout == 'nchw' else (B, Hh, Hh, 16)
+        dev = self.flat_params.device
+        for i, g in enumerate(grads):
+            if g is None:
+                continue
+            if not torch.is_tensor(g) or tuple(g.shape) != want or g.dtype != torch.float32 or g.device != dev:
+                raise ValueError('backward: gradient %d must be a float32 tensor %s on %s, got %s' % (
+                    i, want, dev, '%s %s on %s' % (g.dtype, tuple(g.shape), g.device) if torch.is_tensor(g) else type(g).__name__))
+        if all(g is None for g in grads):
+            raise ValueError('backward: every gradient is None')
+        h = self._net(B)
+        keep = [None if g is None else g.contiguous() for g in grads]       # referenced until the call returns (read in stream order)
+        for g in keep:
+            if g is not None and g.data_ptr() % 16:
+                raise ValueError('backward: gradients must be 16-byte aligned')
+        ptrs = (C.c_void_p * self.num_stacks)(*[None if g is None else g.data_ptr() for g in keep])
+        check(lib().pa_hg_set_heat_grads(h, ptrs, 0 if layout == 'nchw' else 1), 'pa_hg_set_heat_grads')
+        try:
+            masks = self._set_masks(h, self._last_masks)        # the occlusion masks of that forward pass: the backward pass goes through them
+            self._run_backward(h)
+        finally:
+            lib().pa_hg_set_heat_grads(h, None, 0)
+            if self._last_masks is not None:
+                self._set_masks(h, None)
+        del keep, masks
+
+    def forward_autograd(self, x=None, img4=None, pts=None, dropout_masks=None):
+        """forward() whose per-stack heat maps carry a grad_fn: `loss = my_loss(outs); loss.backward(); optimizer.step()`.
+        Returns a tuple of num_stacks tensors [B][16][res/4][res/4].  loss.backward() calls self.backward() once with the gradients autograd
+        delivers; the parameter gradients land in flat_grads (the project's convention: the parameter views carry no .grad), nothing flows
+        to the input image.  The engine keeps ONE forward pass's activations: backward a second time through the same outputs, or after
+        another forward pass of this net, raises RuntimeError.  pts is optional (accuracy() and _last_losses, as in forward());
+        dropout_masks as in forward(): the backward pass differentiates through the same masks."""
+        self._ensure_table()
+        if getattr(self, '_autograd_anchor', None) is None:
+            self._autograd_anchor = torch.zeros(1, dtype=torch.float32, device=self.flat_params.device, requires_grad=True)
+        return _HeatMapsFunction.apply(self._autograd_anchor, self, x, img4, pts, dropout_masks)
 
     def accuracy(self, idxs, stack=-1):
         """Evaluation.accuracy (pylib/Evaluation.py:54-75) of the last forward's heat maps against the

@@ -2,9 +2,38 @@
 from ._dev import lib, check, ptr, stream, dev, to_dev, torch
 
 
+def _loss(p, g, w, scale):
+    loss = torch.zeros(1, dtype=torch.float32, device=dev())
+    check(lib().pa_weighted_l2(ptr(p), ptr(g), ptr(w), p.numel(), ptr(loss), stream()), 'pa_weighted_l2')
+    return loss[0] * scale
+
+
+class _WeightedL2(torch.autograd.Function):
+    """weighted_L2 for a `pred` that requires grad: forward pa_weighted_l2, backward pa_weighted_l2_grad (the gradient arriving at the
+    loss stays a device float: no host synchronisation); gt and weight get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, p, g, w, scale):
+        ctx.p, ctx.g, ctx.w, ctx.scale = p, g, w, scale          # (p: pred's detached device copy, what the kernels read)
+        return _loss(p, g, w, scale)
+
+    @staticmethod
+    def backward(ctx, gout):
+        go = gout.detach().to(torch.float32).reshape(1)
+        if ctx.scale != 1.0:
+            go = go * ctx.scale
+        go = go.contiguous()
+        dpred = torch.empty_like(ctx.p)
+        check(lib().pa_weighted_l2_grad(ptr(ctx.p), ptr(ctx.g), ptr(ctx.w), ctx.p.numel(), ptr(go), ptr(dpred), stream()),
+              'pa_weighted_l2_grad')
+        return dpred, None, None, None, None
+
+
 def weighted_L2(pred, gt, weight):
     """((pred - gt)^2 * weight).sum() / numel  (pylib/Criterion.py:12-18).  `weight` may be a scalar
-    1 (the inline loss of stack-hg.py:156-159) or a tensor of pred's shape.  Returns a 0-d GPU tensor."""
+    1 (the inline loss of stack-hg.py:156-159) or a tensor of pred's shape.  Returns a 0-d GPU tensor.
+    Differentiable in `pred` (a GPU tensor that requires grad, e.g. a heat map of HourglassNet.forward_autograd): the result then
+    carries a grad_fn whose backward is the engine's kernel; gt and weight are constants."""
     p = to_dev(pred, torch.float32)
     g = to_dev(gt, torch.float32)
     w = None
@@ -13,6 +42,8 @@ def weighted_L2(pred, gt, weight):
     scale = 1.0
     if w is None:
         scale = float(weight) if not isinstance(weight, torch.Tensor) else float(weight.reshape(-1)[0])
-    loss = torch.zeros(1, dtype=torch.float32, device=dev())
-    check(lib().pa_weighted_l2(ptr(p), ptr(g), ptr(w), p.numel(), ptr(loss), stream()), 'pa_weighted_l2')
-    return loss[0] * scale
+    if isinstance(pred, torch.Tensor) and pred.requires_grad and torch.is_grad_enabled():
+        if pred.device != p.device or pred.dtype != torch.float32:
+            raise ValueError('weighted_L2: a pred that requires grad must be a float32 tensor on the HIP device')
+        return _WeightedL2.apply(pred, p, g, w, scale)
+    return _loss(p, g, w, scale)

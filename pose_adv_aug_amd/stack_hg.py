@@ -54,15 +54,27 @@ def broadcast_parameters(net):
         net.weights_changed()
 
 
-def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None):
+def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, criterion=None):
     """stack-hg.py:134-180 for one batch.  Returns device scalars (loss, pckh, pckh_origin_res).
-    data: the batch's augmented input if it was prepared ahead (data.AugmentAhead), else it is made here."""
+    data: the batch's augmented input if it was prepared ahead (data.AugmentAhead), else it is made here.
+    criterion: a callable (outs, data) -> 0-d loss tensor over the per-stack heat maps of net.forward_autograd (your own loss, e.g.
+    pylib.Criterion.weighted_L2 with per-joint weights): forward, criterion, loss.backward(), optimizer.step().  None (the default,
+    what every shipped loop passes): the built-in fused MSE step."""
     if data is None:
         data = augmenter.regular(batch)
     def meters():
         pckh = net.accuracy(PCK_IDX)                                                    # stack-hg.py:176
         pckh_o, _ = net.pckh_origin_res(data['c'], data['s'], data['r'], data['grnd_pts'], data['normalizer'])   # :178
         return pckh, pckh_o
+    if criterion is not None:
+        outs = net.forward_autograd(img4=data['img4'], pts=data['pts'])
+        loss = criterion(outs, data)
+        loss.backward()
+        optimizer.step()
+        if not want_pckh:
+            return loss.detach(), None, None
+        pckh, pckh_o = meters()
+        return loss.detach(), pckh[0], pckh_o[0]
     if want_pckh and not getattr(net, 'use_graph', False):
         # the meters read the forward pass's heat maps only: launched between the two passes they run beside the backward pass on the
         # engine's meter stream (100 us of short launches that otherwise sit between two steps); same values
