@@ -479,6 +479,22 @@ int pa_copy_probe_form(void* dst, const void* src, size_t bytes, int form, void*
  * caller-provided device workspace (>= 1 GiB for the benchmark's shapes); *ms_out = average milliseconds per launch over `iters`
  * launches (HIP events on `stream`). */
 int pa_conv2d_time(int mode, int variant, int B, int Cin, int Cout, int H, int W, int k, int iters, void* ws, float* ms_out, void* stream);
+/* Which kernel instance a forward / data-gradient convolution launch would take, as the launchers themselves plan it (csrc/conv_plan.h);
+ * read-only, no device call, so it answers on a machine without a GPU.  Modes: operand loads -1 none, 0 plain, 1 BatchNorm + ReLU,
+ * 2 BatchNorm backward, 3 pool-routed; epilogues 0 plain, 1 statistics, 2 BatchNorm backward (ep2: the second output's).  fin_rows: partial
+ * rows of a pending finalize of the input (0 none).  flags: 1 bias, 2 second output (upsample-add backward), 4 a dz buffer is offered,
+ * 8 in.map, 16 in.q, 32 ep2 scale / shift, 64 add2.map.  cus: compute units of the device (0 unknown).  Fills out[0..16) (HOST array, cap
+ * >= 16) and returns 16: {path (0 refused, 1 generic, 2 one-shot, 3 row tile, 4 row tile with the second output, 5 halo tile),
+ * instance id (tiling * 8 + variant, the enums of conv_plan.h), grid x, grid y, threads, channel blocks per workgroup, partial rows, partial
+ * rows of the second output, xcd bits, takes a finalize, stores dz, pool-routed addend, pool-routed input, the LDS BatchNorm-backward
+ * epilogue takes the launch, the instance cannot reach the kernels' trap for a launch that form does not take, the kernels' own copy of
+ * that LDS rule}.  A refused launch also sets pa_last_error() to the reason; an admitted one leaves the last error as it is. */
+int pa_conv_plan_describe(int B, int H, int W, int Cin, int Cout, int taps, int in_mode, int add1_mode, int add2_mode, int ep_mode,
+                          int ep2_mode, int fin_rows, int flags, int cus, int* out, int cap);
+/* Test hook: which convolution launches ran.  out == NULL clears the log and switches it on; every forward / data-gradient launch of this
+ * process is then noted once (at most 1024 distinct ones) as the first 14 arguments of pa_conv_plan_describe.  out != NULL copies up to cap
+ * launches of 14 ints each (HOST array), switches the log off and returns their number.  Not thread-safe; off by default. */
+int pa_conv_launch_log(int* out, int cap);
 
 /* The engine enqueues independent branches (hourglass skip blocks, weight gradients) on internal side
  * streams that fork from / join into the caller's stream by events.  on = 0 serialises everything on

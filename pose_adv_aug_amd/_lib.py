@@ -159,6 +159,8 @@ _PROTOS = {
     'pa_wgrad_group_workspace_bytes': (_sz, [_vp, _i]),
     'pa_wgrad_group': (_i, [_vp, _i, _i, _vp, _vp]),
     'pa_conv2d_time': (_i, [_i] * 9 + [_vp, C.POINTER(C.c_float), _vp]),
+    'pa_conv_plan_describe': (_i, [_i] * 14 + [C.POINTER(_i), _i]),
+    'pa_conv_launch_log': (_i, [C.POINTER(_i), _i]),
     'pa_net_profile_classes': (_i, [_vp, C.POINTER(C.c_int32), _i]),
     'pa_net_set_multi_stream': (_i, [_vp, _i]),
     'pa_hg_debug_tensor': (_i, [_vp, C.c_char_p, _i, _vp, C.POINTER(_i)]),

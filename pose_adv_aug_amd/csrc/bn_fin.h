@@ -15,11 +15,9 @@
 // s_i = r_i + r_(i+2), total = s_0 + s_1.  Sixteen independent chains keep many row loads in flight (the finalize is two L2 round
 // trips, not rows / 8 of them).  FOUR threads share a channel pair: thread g sums the chains g, g+4, g+8, g+12 and runs the first two
 // tree levels locally, the last two go through LDS.  The prologue and the launch give the same bits, so the choice between them
-// (Net::fin_rows_max, PA_FIN_PROLOGUE in tuning builds) never changes a result.
+// (Net::fin_rows_max, PA_FIN_PROLOGUE in tuning builds) never changes a result.  PA_FIN_SMALL_ROWS = 128: modes.h (the planner refuses more rows).
 #pragma once
 #include "common.h"
-
-#define PA_FIN_SMALL_ROWS 128
 
 // a pending finalize folded into the consumer (rows == 0: none; the operand's k0 / k1 / k2 pointers are used as they are)
 struct PaBnFin {

@@ -9,7 +9,7 @@
 //     so the input is not re-read per 128 output channels;
 //   * the weight slices [BN][64] are streamed with global_load_lds, double buffered (conv3x3_tile.hip);
 //   * two or three workgroups per CU (48-64 KB LDS): one stages while the others compute; 64-row tiles so that a
-//     24 x 64 x 64 map is 1536 workgroups = full rounds (row_bm below).
+//     24 x 64 x 64 map is 1536 workgroups = full rounds (conv_plan.h).
 // LDS images: activation tile [BM][CIN] and weight slice [BN][64] bf16, 16-byte slots XOR-swizzled by the
 // row so that the ds_read_b128 fragment reads are bank-conflict free.  Epilogue: conv_epilogue.h (forward modes through
 // an fp32 LDS tile with fully coalesced rows, BatchNorm-backward mode direct).
@@ -252,13 +252,11 @@ __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CI
 
 // LIN2_ONLY: an instance that only BatchNorm-backward inputs reach (the 128-row fallback of the 128-channel layers)
 template <int CIN, int BM, int BN, int KS = 64, bool LIN2_ONLY = false>
-static void launch_row_ld(const PaConvArgs& a0, dim3 grid, int nbw, hipStream_t st) {
-    PaConvArgs a = a0;
-    a.dbg = pa_tuning().conv1t_dbg;      // tuning builds: cycle stamps
+static void launch_row_ld(const PaConvArgs& a, int variant, dim3 grid, int nbw, hipStream_t st) {
     if constexpr (LIN2_ONLY) {
         hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_LIN2, KS>), grid, dim3(256), 0, st, a, nbw);
     } else {
-        switch (a.in.mode) {
+        switch (variant) {
             case PA_LD_PLAIN: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_PLAIN, KS>), grid, dim3(256), 0, st, a, nbw); break;
             case PA_LD_BNRELU: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_BNRELU, KS>), grid, dim3(256), 0, st, a, nbw); break;
             default: hipLaunchKernelGGL((conv1x1_tile_kernel<CIN, BM, BN, PA_LD_LIN2, KS>), grid, dim3(256), 0, st, a, nbw); break;
@@ -266,94 +264,28 @@ static void launch_row_ld(const PaConvArgs& a0, dim3 grid, int nbw, hipStream_t 
     }
 }
 
-// 64-row tiles also for 128 input channels: at B = 24, 64x64 maps the 768 tiles of 128 rows fill 256 CUs x 2
-// workgroups 1.5 times (the last round runs half empty); 1536 tiles of 64 rows at 3 workgroups/CU are 2 full rounds
-static int row_bm(int Cin) { return (Cin == 256 || Cin == 128) ? 64 : 128; }
-
-// the UP instance: 128 -> 256 (any multiple of 128) channels, BatchNorm backward on load, one plain addend, plain output, maps whose rows are
-// multiples of 32 pixels with an even row count, enough tiles for the row-tile kernel
-bool pa_conv1x1_tile_up_supported(const PaConvArgs& a) {
-    if (!a.out2 || a.taps != 1 || a.Cin != 128 || a.Cout % 128 != 0 || a.in.mode != PA_LD_LIN2 || a.bias || a.dz_out || a.fin.rows > 0) return false;
-    if (a.add1.mode != PA_LD_PLAIN || a.add2.mode != PA_LD_NONE || a.ep.mode != PA_OUT_PLAIN || a.ep2.mode != PA_OUT_BWD) return false;
-    if (a.W % 32 != 0 || a.H % 2 != 0) return false;
-    const long M = (long)a.B * a.H * a.W;
-    if ((size_t)M * (size_t)a.Cout >= ((size_t)1 << 31)) return false;
-    return M / 64 >= 192;
-}
-
-static int launch_conv1x1_tile_up(const PaConvArgs& a, hipStream_t st, int* stat_rows) {
-    const int M = a.B * a.H * a.W, tiles = M / 64;
-    if (stat_rows) *stat_rows = tiles;
-    if (a.ep2.rows_out) *a.ep2.rows_out = tiles;
-    const int nb = a.Cout / 128;
-    const int nbw = tiles >= 512 ? nb : 1;
-    hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, true>), dim3(tiles, nb / nbw), dim3(256), 0, st, a, nbw);
-    return (int)hipGetLastError();
-}
-
-// the POOL instance: 128 -> 128 k channels in 64-row tiles, BatchNorm backward on load, plain output or the LDS BatchNorm-backward epilogue
-static bool tile_pool_ok(const PaConvArgs& a) {
-    return a.Cin == 128 && a.Cout % 128 == 0 && a.in.mode == PA_LD_LIN2 && !a.bias && !a.out2 && a.fin.rows == 0 && a.H % 2 == 0 && a.W % 2 == 0 &&
-           (a.add1.mode == PA_LD_NONE || a.add1.mode == PA_LD_PLAIN || a.add1.mode == PA_LD_LIN2) &&
-           (a.ep.mode == PA_OUT_PLAIN || (a.ep.mode == PA_OUT_BWD && a.xcd < 2));
-}
-
-// the PIN instance: 128 -> 64 channels in 64-row tiles, the transformed tile stored, the table form of the BatchNorm-backward epilogue
-static bool tile_pool_in_ok(const PaConvArgs& a) {
-    return a.Cin == 128 && a.Cout % 64 == 0 && a.Cout % 128 != 0 && a.in.map && a.in.q && a.dz_out && !a.bias && !a.out2 && a.fin.rows == 0 &&
-           a.H % 2 == 0 && a.W % 2 == 0 && a.add1.mode == PA_LD_NONE && a.add2.mode == PA_LD_NONE &&
-           a.ep.mode == PA_OUT_BWD && a.xcd < 2 && a.ep2.scale && a.ep2.shift;
-}
-
-bool pa_conv1x1_tile_supported(const PaConvArgs& a) {
-    if (a.add2.mode == PA_LD_POOL && !tile_pool_ok(a)) return false;
-    if (a.in.mode == PA_LD_POOL && !tile_pool_in_ok(a)) return false;
-    if (a.taps != 1 || (a.Cin != 64 && a.Cin != 128 && a.Cin != 256) || a.Cout % 64 != 0) return false;
-    const int M = a.B * a.H * a.W;
-    if ((size_t)M * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;      // 32-bit element offsets in the epilogue
-    // (64 -> 64 channels: every instance carries the table form of the BatchNorm-backward epilogue only)
-    if (a.Cin == 64 && a.Cout % 128 != 0 && a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a)) return false;
-    return (M + row_bm(a.Cin) - 1) / row_bm(a.Cin) >= 192;          // smaller problems: generic kernel with 64x64 tiles
-}
-
-int pa_launch_conv1x1_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) {
-    if (a.out2) {
-        if (!pa_conv1x1_tile_up_supported(a)) { pa_set_error_msg("pa_launch_conv1x1_tile: not a launch of the 2 x 32-pixel instance (pa_conv1x1_tile_up_supported)"); return 1; }
-        return launch_conv1x1_tile_up(a, st, stat_rows);
+// the instance the plan names (conv_plan.h: which tiling takes which launch, and why); pa_launch_conv has set a.xcd, a.dz_out and the row counts
+int pa_launch_conv1x1_tile(const PaConvArgs& a0, const PaConvPlan& p, hipStream_t st) {
+    PaConvArgs a = a0; a.dbg = pa_tuning().conv1t_dbg;      // tuning builds: cycle stamps
+    const dim3 grid(p.gx, p.gy); const int v = p.variant(), nbw = p.nbw;
+    switch (p.tiling()) {
+        case PA_CT_R128_64_128_UP: hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, true>), grid, dim3(256), 0, st, a, nbw); break;
+        case PA_CT_R128_64_64_PIN: hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 64, PA_LD_LIN2, 64, false, PA_POOL_EP_NONE, true>), grid, dim3(256), 0, st, a, nbw); break;
+        case PA_CT_R256_64_128_K32: launch_row_ld<256, 64, 128, 32>(a, v, grid, nbw, st); break;
+        case PA_CT_R256_64_128: launch_row_ld<256, 64, 128>(a, v, grid, nbw, st); break;
+        case PA_CT_R256_64_64: launch_row_ld<256, 64, 64>(a, v, grid, nbw, st); break;
+        case PA_CT_R128_64_128:
+            if (v == PA_CV_POOL_BWD) hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, false, PA_POOL_EP_BWD>), grid, dim3(256), 0, st, a, nbw);
+            else if (v == PA_CV_POOL_PLAIN) hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, false, PA_POOL_EP_PLAIN>), grid, dim3(256), 0, st, a, nbw);
+            else launch_row_ld<128, 64, 128>(a, v, grid, nbw, st);
+            break;
+        case PA_CT_R128_64_64: launch_row_ld<128, 64, 64>(a, v, grid, nbw, st); break;
+        case PA_CT_R128_128_128: launch_row_ld<128, 128, 128, 64, true>(a, v, grid, nbw, st); break;
+        case PA_CT_R128_128_64: launch_row_ld<128, 128, 64, 64, true>(a, v, grid, nbw, st); break;
+        case PA_CT_R64_64_128: launch_row_ld<64, 64, 128>(a, v, grid, nbw, st); break;
+        case PA_CT_R64_128_128: launch_row_ld<64, 128, 128>(a, v, grid, nbw, st); break;
+        case PA_CT_R64_128_64: launch_row_ld<64, 128, 64>(a, v, grid, nbw, st); break;
+        default: pa_set_error_msg("pa_launch_conv1x1_tile: the plan names no instance of conv1x1_tile.hip"); return 1;
     }
-    if (!pa_conv1x1_tile_supported(a)) { pa_set_error_msg("pa_launch_conv1x1_tile: unsupported shape"); return 1; }
-    const int M = a.B * a.H * a.W;
-    int bm = row_bm(a.Cin);
-    // 64 input channels, 128 output channels: 64-row tiles at three workgroups per CU (the 128-row instance spills at 168 registers)
-    if (a.Cin == 64 && a.Cout % 128 == 0 && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a))) bm = 64;
-    // the 64-row, 128-channel BatchNorm-backward instance (3 workgroups per CU) has the LDS epilogue only
-    if (a.Cin == 128 && bm == 64 && a.in.mode == PA_LD_LIN2 && a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a) && a.add2.mode != PA_LD_POOL) bm = 128;
-    const int tiles = (M + bm - 1) / bm;
-    if (stat_rows) *stat_rows = tiles;
-    if (a.ep.rows_out) *a.ep.rows_out = tiles;
-    const bool bigN = a.Cout % 128 == 0;
-    const int nb = a.Cout / (bigN ? 128 : 64);
-    const int nbw = tiles >= 512 ? nb : 1;          // enough row tiles: loop over the channel blocks inside (input read once)
-    dim3 grid(tiles, nb / nbw);
-    // 256 channels: the three-workgroup instance (32-channel weight slices) unless the launch needs the direct BatchNorm-backward epilogue
-    const bool three = bigN && !(a.ep.mode == PA_OUT_BWD && !pa_bwd_epilogue_lds_ok(a));
-    if (a.in.mode == PA_LD_POOL) {                 // (tile_pool_in_ok: Cin = 128, bm = 64, 64-channel blocks)
-        PaConvArgs b = a;
-        b.dbg = pa_tuning().conv1t_dbg;
-        hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 64, PA_LD_LIN2, 64, false, PA_POOL_EP_NONE, true>), grid, dim3(256), 0, st, b, nbw);
-        return (int)hipGetLastError();
-    }
-    if (a.add2.mode == PA_LD_POOL) {               // (tile_pool_ok: Cin = 128, bm = 64, bigN)
-        PaConvArgs b = a;
-        b.dbg = pa_tuning().conv1t_dbg;
-        if (a.ep.mode == PA_OUT_BWD) hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, false, PA_POOL_EP_BWD>), grid, dim3(256), 0, st, b, nbw);
-        else hipLaunchKernelGGL((conv1x1_tile_kernel<128, 64, 128, PA_LD_LIN2, 64, false, PA_POOL_EP_PLAIN>), grid, dim3(256), 0, st, b, nbw);
-        return (int)hipGetLastError();
-    }
-    if (a.Cin == 256) { if (bigN && three) launch_row_ld<256, 64, 128, 32>(a, grid, nbw, st); else if (bigN) launch_row_ld<256, 64, 128>(a, grid, nbw, st); else launch_row_ld<256, 64, 64>(a, grid, nbw, st); }
-    else if (a.Cin == 128 && bm == 64) { if (bigN) launch_row_ld<128, 64, 128>(a, grid, nbw, st); else launch_row_ld<128, 64, 64>(a, grid, nbw, st); }
-    else if (a.Cin == 128) { if (bigN) launch_row_ld<128, 128, 128, 64, true>(a, grid, nbw, st); else launch_row_ld<128, 128, 64, 64, true>(a, grid, nbw, st); }      // (bm == 128 here: a.in.mode is LIN2)
-    else if (bm == 64) launch_row_ld<64, 64, 128>(a, grid, nbw, st);
-    else { if (bigN) launch_row_ld<64, 128, 128>(a, grid, nbw, st); else launch_row_ld<64, 128, 64>(a, grid, nbw, st); }
     return (int)hipGetLastError();
 }

@@ -407,93 +407,41 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
 
 // WITHFIN: this tiling also exists as a finalize-carrying instance (BatchNorm-on-load modes only), used when the launch brings one
 template <int CIN, int BN, int TW, int TH, int SPS, bool PF, bool WITHFIN = false, int NT = 256>
-static void launch_tile_ld(const PaConvArgs& a, dim3 grid, hipStream_t st) {
+static void launch_tile_ld(const PaConvArgs& a, int variant, dim3 grid, hipStream_t st) {
     if constexpr (WITHFIN) {
-        if (a.fin.rows > 0) {
-            if (a.in.mode == PA_LD_BNRELU) hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, BN, PA_LD_BNRELU, TW, TH, SPS, PF, NT, true>), grid, dim3(NT), 0, st, a);
-            else hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, BN, PA_LD_LIN2, TW, TH, SPS, PF, NT, true>), grid, dim3(NT), 0, st, a);
-            return;
-        }
+        if (variant == PA_CV_BNRELU_FIN) { hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, BN, PA_LD_BNRELU, TW, TH, SPS, PF, NT, true>), grid, dim3(NT), 0, st, a); return; }
+        if (variant == PA_CV_LIN2_FIN) { hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, BN, PA_LD_LIN2, TW, TH, SPS, PF, NT, true>), grid, dim3(NT), 0, st, a); return; }
     }
-    switch (a.in.mode) {
+    switch (variant) {
         case PA_LD_PLAIN: hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, BN, PA_LD_PLAIN, TW, TH, SPS, PF, NT>), grid, dim3(NT), 0, st, a); break;
         case PA_LD_BNRELU: hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, BN, PA_LD_BNRELU, TW, TH, SPS, PF, NT>), grid, dim3(NT), 0, st, a); break;
         default: hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, BN, PA_LD_LIN2, TW, TH, SPS, PF, NT>), grid, dim3(NT), 0, st, a); break;
     }
 }
 
-// The three tilings.  SPS: slices per K-loop step of the latency-bound variants (128 input channels): a whole tap for the 8x8 / 4x4 maps,
-// half a tap for the 16 x 4 tiles; 1 everywhere else (the 16 x 8 tiles of the big maps are throughput-bound and need their LDS for 2
-// workgroups per CU, and run the software-pipelined K loop).
-// 8 x 8 / 4 x 4 tiles: always 64-channel halves, 512 threads for 128 input channels
-template <int T>
-static void launch_small(const PaConvArgs& a, dim3 grid, hipStream_t st) {
-    if (a.Cin == 128) launch_tile_ld<128, 64, T, T, 4, false, true, 512>(a, grid, st);
-    else launch_tile_ld<64, 64, T, T, 1, false, true>(a, grid, st);
-}
-// 16 x 8 tiles
-static void launch_16x8(const PaConvArgs& a, dim3 grid, bool bigN, hipStream_t st) {
-    if (a.Cin == 128) { if (bigN) launch_tile_ld<128, 128, 16, 8, 1, true>(a, grid, st); else launch_tile_ld<128, 64, 16, 8, 1, true>(a, grid, st); }
-    else { if (bigN) launch_tile_ld<64, 128, 16, 8, 1, true>(a, grid, st); else launch_tile_ld<64, 64, 16, 8, 1, true, true>(a, grid, st); }
-}
-// 16 x 4 tiles (128 input channels, 64-channel halves): 512 threads when the launch is at most one workgroup per CU (the 16 x 16 maps: 192
-// workgroups, 12.0 -> 8.6 us); with two workgroups per CU (32 x 32) the 256-thread workgroups already overlap each other and 512 measured
-// slower (16.1 vs 18.2)
-static void launch_16x4(const PaConvArgs& a, dim3 grid, hipStream_t st) {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-        return n;
-    }();
-    if ((int)(grid.x * grid.y) <= cus) launch_tile_ld<128, 64, 16, 4, 2, false, true, 512>(a, grid, st);
-    else launch_tile_ld<128, 64, 16, 4, 2, false, true>(a, grid, st);
+int pa_conv_cus() {
+    static const int cus = [] { int dev = 0, n = 0; return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? n : 0; }();
+    return cus;
 }
 
-// does the instance the launcher below picks for this shape exist with the finalize prologue?  (pa_conv_takes_fin)
-bool pa_conv3x3_tile_takes_fin(const PaConvArgs& a) {
-    if (!pa_conv3x3_tile_supported(a)) return false;
-    const bool small = !(a.H % 8 == 0 && a.W % 16 == 0);
-    if (small) return true;                                                    // 8 x 8 / 4 x 4 maps: <128 | 64, 64, .., SPS 4 | 1>
-    const int tiles128 = a.B * (a.H / 8) * (a.W / 16);
-    if (a.Cin == 128) return tiles128 < 512;                                   // 16 x 4 tiles, half a tap per step
-    return a.Cout % 128 != 0;                                                  // 64 input channels: the 16 x 8 <64, 64> instance
-}
-
-// maps tiled by the 8 x 8 / 4 x 4 variants: sides multiples of 8 (that the 16 x 8 tiles do not take: W % 16 != 0) or of 4
-// (any map up to 8 x 8 -- the 6 x 6 necks of the 384 x 384 configuration -- is ONE 8 x 8 tile whose pixels outside the map are masked)
-static int small_tile(const PaConvArgs& a) { return (a.H % 8 == 0 && a.W % 8 == 0) ? 8 : ((a.H % 4 == 0 && a.W % 4 == 0) ? 4 : ((a.H <= 8 && a.W <= 8) ? 8 : 0)); }
-static bool small_map(const PaConvArgs& a) { return small_tile(a) != 0; }
-
-bool pa_conv3x3_tile_supported(const PaConvArgs& a) {
-    if (a.taps != 9 || (a.Cin != 64 && a.Cin != 128) || a.Cout % 64 != 0) return false;
-    if ((size_t)a.B * a.H * a.W * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;      // 32-bit element offsets in the epilogue
-    return (a.H % 8 == 0 && a.W % 16 == 0) || (!pa_tuning().conv3_nosmall && small_map(a));
-}
-
-int pa_launch_conv3x3_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows) {
-    if (!pa_conv3x3_tile_supported(a)) { pa_set_error_msg("pa_launch_conv3x3_tile: unsupported shape"); return 1; }
-    const bool small = !(a.H % 8 == 0 && a.W % 16 == 0);
-    const int st_ = small ? small_tile(a) : 0;                      // side of the small tile
-    const int img = small ? 128 / (st_ * st_) : 1;                  // sub-tiles per workgroup
-    // 16 x 4 pixel tiles (3 workgroups per CU) where 16 x 8 tiles would leave CUs idle: measured 64x64 maps (768 tiles)
-    // 39.8 vs 42.8 us in favour of 16 x 8, 32x32 maps (192 tiles) 17.6 vs 14.6 us in favour of 16 x 4
-    const int tiles128 = small ? 0 : a.B * (a.H / 8) * (a.W / 16);
-    const bool half = !small && a.Cin == 128 && tiles128 < 512;
-    const int tiles = small ? (a.B * ((a.H + st_ - 1) / st_) * ((a.W + st_ - 1) / st_) + img - 1) / img : a.B * (a.H / (half ? 4 : 8)) * (a.W / 16);
-    if (stat_rows) *stat_rows = tiles;
-    if (a.ep.rows_out) *a.ep.rows_out = tiles;
-    // the low-resolution levels have 3..12 pixel tiles: 64-channel halves double the number of workgroups
-    // ... and so do the 16 x 4 tiles (32 x 32 / 16 x 16 maps): 64-channel blocks halve the serial chain of a workgroup (weight pieces, MFMAs,
-    // epilogue) -- 32 x 32: 16.5 -> 16.1 / 19.3 -> 17.8 us (forward / data gradient), 16 x 16: see launch_16x4
-    const bool bigN = a.Cout % 128 == 0 && !small && !half;
-    dim3 grid(tiles, a.Cout / (bigN ? 128 : 64));
-    PaConvArgs b = a;
-    b.dbg = pa_tuning().conv3_dbg;                                  // tuning builds: phase ablation / tap rotation
-    // one contiguous range of tiles per XCD: +0.3 % on the step (halo re-reads served by the XCD's own L2)
-    b.xcd = (a.xcd & 2) | ((!pa_tuning().conv3_noxcd && !small && tiles % 8 == 0) ? 1 : 0);
-    if (half) launch_16x4(b, grid, st);
-    else if (!small) launch_16x8(b, grid, bigN, st);
-    else if (st_ == 8) launch_small<8>(b, grid, st);
-    else launch_small<4>(b, grid, st);
+// The three tilings (conv_plan.h: which launch takes which).  SPS: slices per K-loop step of the latency-bound variants (128 input channels):
+// a whole tap for the 8x8 / 4x4 maps, half a tap for the 16 x 4 tiles; 1 everywhere else (the 16 x 8 tiles of the big maps are
+// throughput-bound and need their LDS for 2 workgroups per CU, and run the software-pipelined K loop).  pa_launch_conv has set a.xcd / a.dz_out
+int pa_launch_conv3x3_tile(const PaConvArgs& a0, const PaConvPlan& p, hipStream_t st) {
+    PaConvArgs a = a0; a.dbg = pa_tuning().conv3_dbg;               // tuning builds: phase ablation / tap rotation
+    const dim3 grid(p.gx, p.gy); const int v = p.variant();
+    switch (p.tiling()) {
+        case PA_CT_T16x8_128_128: launch_tile_ld<128, 128, 16, 8, 1, true>(a, v, grid, st); break;
+        case PA_CT_T16x8_128_64: launch_tile_ld<128, 64, 16, 8, 1, true>(a, v, grid, st); break;
+        case PA_CT_T16x8_64_128: launch_tile_ld<64, 128, 16, 8, 1, true>(a, v, grid, st); break;
+        case PA_CT_T16x8_64_64: launch_tile_ld<64, 64, 16, 8, 1, true, true>(a, v, grid, st); break;
+        case PA_CT_T16x4_128_64_T512: launch_tile_ld<128, 64, 16, 4, 2, false, true, 512>(a, v, grid, st); break;
+        case PA_CT_T16x4_128_64: launch_tile_ld<128, 64, 16, 4, 2, false, true>(a, v, grid, st); break;
+        case PA_CT_TS8_128_64_T512: launch_tile_ld<128, 64, 8, 8, 4, false, true, 512>(a, v, grid, st); break;
+        case PA_CT_TS8_64_64: launch_tile_ld<64, 64, 8, 8, 1, false, true>(a, v, grid, st); break;
+        case PA_CT_TS4_128_64_T512: launch_tile_ld<128, 64, 4, 4, 4, false, true, 512>(a, v, grid, st); break;
+        case PA_CT_TS4_64_64: launch_tile_ld<64, 64, 4, 4, 1, false, true>(a, v, grid, st); break;
+        default: pa_set_error_msg("pa_launch_conv3x3_tile: the plan names no instance of conv3x3_tile.hip"); return 1;
+    }
     return (int)hipGetLastError();
 }

@@ -605,7 +605,7 @@ __device__ __forceinline__ void pa_conv_epilogue_lds_up(const PaConvArgs& a, f32
     }
 }
 
-// host side of the dispatch below: can the LDS variant of the BatchNorm-backward epilogue take this launch?
+// device side of PaConvPlan::bwd_lds (conv_plan.h; tests/test_conv_plan_cpu.py holds the two together on every mode combination): can the LDS variant of the BatchNorm-backward epilogue take this launch?
 __host__ __device__ inline bool pa_bwd_epilogue_lds_ok(const PaConvArgs& a) {
     return a.xcd < 2 && a.bias == nullptr && (a.add1.mode == PA_LD_NONE || a.add1.mode == PA_LD_PLAIN || a.add1.mode == PA_LD_LIN2) &&
            (a.add2.mode == PA_LD_NONE || a.add2.mode == PA_LD_PLAIN);
@@ -613,7 +613,7 @@ __host__ __device__ inline bool pa_bwd_epilogue_lds_ok(const PaConvArgs& a) {
 
 // forward epilogues through LDS (coalesced rows), backward epilogue direct; pix(wm, mi, p) as above
 // T: >= NT * 16 floats, or (TSMALL) >= NT * 8
-// POOL: an instance for launches whose second addend is pool-routed (pa_conv_pool_route_supported admits them): 1 with the LDS form of the
+// POOL: an instance for launches whose second addend is pool-routed (PaConvPlan::pool_route): 1 with the LDS form of the
 // BatchNorm-backward epilogue, 2 with plain output -- one epilogue per instance (each keeps its pixel offsets in registers across the kernel)
 template <int BN, int NI, int MI, bool BWD_LDS = true, bool TAB = false, int NT = 256, bool TSMALL = false, int POOL = 0, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue_auto(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
@@ -633,7 +633,7 @@ __device__ __forceinline__ void pa_conv_epilogue_auto(const PaConvArgs& a, f32x4
         if (lds_ok) {
             pa_conv_epilogue_lds_bwd<BN, NI, MI, TAB, NT, TSMALL, FUSE>(a, acc, n0, wm, wn, pix, T, stat_row, ctab);
         } else if constexpr (TAB || NT != 256) {
-            __builtin_trap();       // the 168-register / 512-thread kernels carry no direct epilogue: pa_bwd_epilogue_lds_ok() routes such launches elsewhere
+            __builtin_trap();       // the 168-register / 512-thread kernels carry no direct epilogue: pa_conv_plan routes such launches elsewhere
         } else {
             const int p = threadIdx.x & 15;
             pa_conv_epilogue<BN, NI, MI>(a, acc, n0, wm, wn, [&](int mi) { return pix(wm, mi, p); }, T, stat_row);

@@ -25,6 +25,7 @@ PA_STAMP_DECL(pa_conv1_clk, pa_debug_conv1_clocks)
 #define PA_STAMP1(i) PA_STAMP_AT(pa_conv1_clk, a.dbg & 64, i)
 #define PA_EPI_STAMP(i) PA_STAMP1(i)
 #include "conv_epilogue.h"
+#include <string.h>
 
 // STEM: the A operand is the 4-channel-padded input image and the kernel computes the 7x7 stride-2
 // stem conv (reference models/asn_stacked_hg.py:223) as a K=256 GEMM: k = ky*32 + kx*4 + c, i.e. one
@@ -331,140 +332,96 @@ __global__ __launch_bounds__(256, 2) void conv1x1_oneshot_kernel(PaConvArgs a) {
     PA_STAMP1(6);
 }
 
+// the variant of an instance id (conv_plan.h) picks the load mode, the finalize prologue and the pool-routed forms
 template <int NK>
-static void launch_oneshot(const PaConvArgs& a0, dim3 grid, hipStream_t st) {
-    PaConvArgs a = a0;
-    a.dbg = pa_tuning().conv1_dbg;      // tuning builds: cycle stamps
-    if (a.add2.mode == PA_LD_POOL) {     // (pa_conv_pool_route_supported: 128 input channels, BatchNorm backward on load, no pending finalize)
-        if constexpr (NK == 2) {
-            if (a.ep.mode == PA_OUT_BWD) hipLaunchKernelGGL((conv1x1_oneshot_kernel<2, PA_LD_LIN2, false, PA_POOL_EP_BWD>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv1x1_oneshot_kernel<2, PA_LD_LIN2, false, PA_POOL_EP_PLAIN>), grid, dim3(256), 0, st, a);
-        }
-        return;
+static void launch_oneshot(const PaConvArgs& a0, int variant, dim3 grid, hipStream_t st) {
+    PaConvArgs a = a0; a.dbg = pa_tuning().conv1_dbg;      // tuning builds: cycle stamps
+    if constexpr (NK == 2) {             // the pool-routed second addend: 128 input channels only
+        if (variant == PA_CV_POOL_BWD) { hipLaunchKernelGGL((conv1x1_oneshot_kernel<2, PA_LD_LIN2, false, PA_POOL_EP_BWD>), grid, dim3(256), 0, st, a); return; }
+        if (variant == PA_CV_POOL_PLAIN) { hipLaunchKernelGGL((conv1x1_oneshot_kernel<2, PA_LD_LIN2, false, PA_POOL_EP_PLAIN>), grid, dim3(256), 0, st, a); return; }
     }
-    if (a.fin.rows > 0) {
-        if (a.in.mode == PA_LD_BNRELU) hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_BNRELU, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_LIN2, true>), grid, dim3(256), 0, st, a);
-        return;
-    }
-    switch (a.in.mode) {
+    switch (variant) {
         case PA_LD_PLAIN: hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_PLAIN, false>), grid, dim3(256), 0, st, a); break;
         case PA_LD_BNRELU: hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_BNRELU, false>), grid, dim3(256), 0, st, a); break;
+        case PA_CV_BNRELU_FIN: hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_BNRELU, true>), grid, dim3(256), 0, st, a); break;
+        case PA_CV_LIN2_FIN: hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_LIN2, true>), grid, dim3(256), 0, st, a); break;
         default: hipLaunchKernelGGL((conv1x1_oneshot_kernel<NK, PA_LD_LIN2, false>), grid, dim3(256), 0, st, a); break;
     }
 }
 
 template <int BM, int BN, int TAPS>
-static void launch_ld(const PaConvArgs& a, dim3 grid, hipStream_t st) {
-    if constexpr (BM == 64 && BN == 64) {
-        if (a.fin.rows > 0) {          // (pa_conv_takes_fin admits BNRELU / LIN2 inputs only)
-            if (a.in.mode == PA_LD_BNRELU) hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, PA_LD_BNRELU, TAPS, false, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, PA_LD_LIN2, TAPS, false, true>), grid, dim3(256), 0, st, a);
-            return;
-        }
+static void launch_ld(const PaConvArgs& a, int variant, dim3 grid, hipStream_t st) {
+    if constexpr (BM == 64 && BN == 64) {      // the tier that exists with the finalize prologue
+        if (variant == PA_CV_BNRELU_FIN) { hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, PA_LD_BNRELU, TAPS, false, true>), grid, dim3(256), 0, st, a); return; }
+        if (variant == PA_CV_LIN2_FIN) { hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, PA_LD_LIN2, TAPS, false, true>), grid, dim3(256), 0, st, a); return; }
     }
-    switch (a.in.mode) {
+    switch (variant) {
         case PA_LD_PLAIN: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, PA_LD_PLAIN, TAPS>), grid, dim3(256), 0, st, a); break;
         case PA_LD_BNRELU: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, PA_LD_BNRELU, TAPS>), grid, dim3(256), 0, st, a); break;
         default: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, PA_LD_LIN2, TAPS>), grid, dim3(256), 0, st, a); break;
     }
 }
 
-template <int BM, int BN>
-static void launch_taps(const PaConvArgs& a, dim3 grid, hipStream_t st) {
-    if (a.taps == 1) launch_ld<BM, BN, 1>(a, grid, st);
-    else launch_ld<BM, BN, 9>(a, grid, st);
-}
-
 int pa_launch_stem_conv(const PaConvArgs& a, hipStream_t st, int* stat_rows) {
     // a.in.p = img4 [B][2H][2W][4]; a.w = [64][256]; a.Cin must be 256 (virtual), a.Cout 64
     if (a.Cin != 256 || a.Cout != 64 || a.in.mode != PA_LD_PLAIN) { pa_set_error_msg("pa_launch_stem_conv: bad arguments"); return 1; }
     const int M = a.B * a.H * a.W;
-    const int bm = (M >= 128 * 256) ? 128 : 64;
-    if (stat_rows) *stat_rows = (M + bm - 1) / bm;
-    if (a.ep.rows_out) *a.ep.rows_out = (M + bm - 1) / bm;
-    if (bm == 128)
-        hipLaunchKernelGGL((conv_igemm_kernel<128, 64, PA_LD_PLAIN, 1, true>), dim3((M + 127) / 128, 1), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_igemm_kernel<64, 64, PA_LD_PLAIN, 1, true>), dim3((M + 63) / 64, 1), dim3(256), 0, st, a);
+    const int bm = pa_conv_big_m(M) ? 128 : 64, rows = (M + bm - 1) / bm;
+    if (stat_rows) *stat_rows = rows; if (a.ep.rows_out) *a.ep.rows_out = rows;
+    if (bm == 128) hipLaunchKernelGGL((conv_igemm_kernel<128, 64, PA_LD_PLAIN, 1, true>), dim3(rows, 1), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_igemm_kernel<64, 64, PA_LD_PLAIN, 1, true>), dim3(rows, 1), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
-// mirrors the dispatch below: the row-tile 1x1 kernel carries no finalize prologue
-bool pa_conv_takes_fin(const PaConvArgs& a) {
-    if (a.in.mode != PA_LD_BNRELU && a.in.mode != PA_LD_LIN2) return false;
-    if (a.Cin > 256) return false;
-    if (!pa_tuning().conv3_old && pa_conv3x3_tile_supported(a)) return pa_conv3x3_tile_takes_fin(a);
-    if (!pa_tuning().conv1_old && pa_conv1x1_tile_supported(a)) return false;
-    // generic kernel: only its 64 x 64-tile instance carries the prologue (the dispatch below: small M, or 64-channel outputs)
-    const int M = a.B * a.H * a.W;
-    const bool bigM = M >= 128 * 256, bigN = a.Cout % 128 == 0;
-    return !bigM && !(bigN && M >= 64 * 256);
+static int g_log[1024][14], g_nlog = -1;      // test hook pa_conv_launch_log (-1: off): the distinct launches, as pa_conv_plan_describe takes them
+static void log_launch(const PaConvShape& s) {
+    const int r[14] = {s.B, s.H, s.W, s.Cin, s.Cout, s.taps, s.in_mode, s.add1_mode, s.add2_mode, s.ep_mode, s.ep2_mode, s.fin_rows,
+                       s.bias | s.out2 << 1 | s.want_dz << 2 | s.in_map << 3 | s.in_q << 4 | s.ep2_affine << 5 | s.add2_map << 6, s.cus};
+    int i = 0; while (i < g_nlog && memcmp(g_log[i], r, sizeof r)) ++i;
+    if (i == g_nlog && i < 1024) memcpy(g_log[g_nlog++], r, sizeof r);
 }
-
-// mirrors the dispatch below: does a launch with a pool-routed second addend (PA_LD_POOL) reach an instance that carries the mode -- the
-// row-tile kernel's (conv1x1_tile.hip) or the one-shot kernel's for 128 input channels?
-bool pa_conv_pool_route_supported(const PaConvArgs& a0) {
-    PaConvArgs a = a0;
-    a.add2.mode = PA_LD_POOL;
-    a.xcd = pa_tuning().epi_bwd_direct ? 2 : 0;
-    if (a.taps != 1 || a.Cin != 128 || a.Cout % 64 != 0 || a.in.mode != PA_LD_LIN2 || a.bias || a.out2 || a.fin.rows > 0 || (a.H & 1) || (a.W & 1)) return false;
-    if (a.add1.mode != PA_LD_NONE && a.add1.mode != PA_LD_PLAIN && a.add1.mode != PA_LD_LIN2) return false;
-    if (a.ep.mode != PA_OUT_PLAIN && !(a.ep.mode == PA_OUT_BWD && a.xcd < 2)) return false;
-    const size_t M = (size_t)a.B * a.H * a.W;
-    if (M * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;
-    if (!pa_tuning().conv1_old && pa_conv1x1_tile_supported(a)) return true;
-    return M < 128 * 256 && !(a.Cout % 128 == 0 && M >= 64 * 256) && pa_tuning().igemm_oneshot != 0;
-}
-
-// ... and a launch whose INPUT is pool-routed (BatchNorm backward on load with the routed dz as first operand): the row-tile kernel's PIN instance
-bool pa_conv_pool_in_supported(const PaConvArgs& a0) {
-    PaConvArgs a = a0;
-    a.in.mode = PA_LD_POOL;
-    a.xcd = pa_tuning().epi_bwd_direct ? 2 : 0;
-    if (a.taps != 1 || pa_tuning().conv1_old || pa_tuning().no_dz3) return false;
-    if ((size_t)a.B * a.H * a.W * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) return false;
-    return pa_conv1x1_tile_supported(a);
-}
-
-int pa_launch_conv(const PaConvArgs& a0, hipStream_t st, int* stat_rows) {
-    PaConvArgs a = a0;
-    a.xcd = pa_tuning().epi_bwd_direct ? 2 : 0;      // A/B: direct BatchNorm-backward epilogue
-    if (a.add1.mode == PA_LD_POOL || (a.in.mode == PA_LD_POOL && !pa_conv_pool_in_supported(a)) ||
-        (a.add2.mode == PA_LD_POOL && (!a.add2.map || !pa_conv_pool_route_supported(a)))) {
-        pa_set_error_msg("pa_launch_conv: a pool-routed operand is the second addend of a launch pa_conv_pool_route_supported() admits or the input of one pa_conv_pool_in_supported() admits");
-        return 1;
-    }
-    if ((a.taps != 1 && a.taps != 9) || a.Cin % 64 != 0 || a.Cout % 64 != 0 || a.Cin > 512) {
-        pa_set_error_msg("pa_launch_conv: channel counts must be multiples of 64 and taps 1 or 9");
-        return 1;
-    }
-    if ((size_t)a.B * a.H * a.W * (size_t)(a.Cin > a.Cout ? a.Cin : a.Cout) >= ((size_t)1 << 31)) {      // the epilogues index with 32 bits
-        pa_set_error_msg("pa_launch_conv: tensors of 2^31 elements or more are not supported (split the batch)");
-        return 1;
-    }
-    if (!pa_tuning().conv3_old && pa_conv3x3_tile_supported(a)) return pa_launch_conv3x3_tile(a, st, stat_rows);
-    if (!pa_tuning().conv1_old && pa_conv1x1_tile_supported(a)) {
-        if (a.fin.rows > 0) { pa_set_error_msg("pa_launch_conv: a pending finalize was handed to the row-tile 1x1 kernel (pa_conv_takes_fin)"); return 1; }
-        return pa_launch_conv1x1_tile(a, st, stat_rows);
-    }
-    if (a.fin.rows > 0 && (a.fin.rows > PA_FIN_SMALL_ROWS || a.Cin > 256 || (a.Cin & 1) || !pa_conv_takes_fin(a))) { pa_set_error_msg("pa_launch_conv: finalize prologue needs <= 128 partial rows, <= 256 channels and a launch pa_conv_takes_fin() admits"); return 1; }
-    const int M = a.B * a.H * a.W;
-    // small problems get the 64-row tile so that the grid still covers the 256 CUs
-    const bool bigM = M >= 128 * 256;
-    const bool bigN = (a.Cout % 128 == 0);
-    if (stat_rows) *stat_rows = bigM ? (M + 127) / 128 : (M + 63) / 64;
-    if (a.ep.rows_out) *a.ep.rows_out = bigM ? (M + 127) / 128 : (M + 63) / 64;
-    if (bigM && bigN) launch_taps<128, 128>(a, dim3((M + 127) / 128, a.Cout / 128), st);
-    else if (bigM) launch_taps<128, 64>(a, dim3((M + 127) / 128, a.Cout / 64), st);
-    else if (bigN && M >= 64 * 256) launch_taps<64, 128>(a, dim3((M + 63) / 64, a.Cout / 128), st);
-    else {
-        // 64 x 64 tiles: the 1x1 layers with 128 / 256 input channels take the one-shot kernel (PA_IGEMM_ONESHOT=0: the K-stepping one)
-        const bool oneshot = pa_tuning().igemm_oneshot != 0;
-        const dim3 grid((M + 63) / 64, a.Cout / 64);
-        if (oneshot && a.taps == 1 && a.Cin == 256) launch_oneshot<4>(a, grid, st);
-        else if (oneshot && a.taps == 1 && a.Cin == 128) launch_oneshot<2>(a, grid, st);
-        else launch_taps<64, 64>(a, grid, st);
+int pa_launch_conv(const PaConvArgs& a0, const PaConvPlan& p, hipStream_t st, int* stat_rows) {
+    if (p.path == PA_CVP_REFUSED) { pa_set_error_msg(p.why); return 1; }
+    if (g_nlog >= 0) log_launch(pa_conv_shape(a0));
+    PaConvArgs a = a0; a.xcd = p.xcd; if (!p.stores_dz) a.dz_out = nullptr;
+    if (stat_rows) *stat_rows = p.rows;
+    if (int* r = p.rows2 ? a.ep2.rows_out : a.ep.rows_out) *r = p.rows;      // (ROW_UP: the statistics are the second output's)
+    if (p.path == PA_CVP_TILE3) return pa_launch_conv3x3_tile(a, p, st);
+    if (p.path == PA_CVP_ROW || p.path == PA_CVP_ROW_UP) return pa_launch_conv1x1_tile(a, p, st);
+    const dim3 grid(p.gx, p.gy); const int v = p.variant();
+    switch (p.tiling()) {
+        case PA_CT_G128x128_1: launch_ld<128, 128, 1>(a, v, grid, st); break;
+        case PA_CT_G128x128_9: launch_ld<128, 128, 9>(a, v, grid, st); break;
+        case PA_CT_G128x64_1: launch_ld<128, 64, 1>(a, v, grid, st); break;
+        case PA_CT_G128x64_9: launch_ld<128, 64, 9>(a, v, grid, st); break;
+        case PA_CT_G64x128_1: launch_ld<64, 128, 1>(a, v, grid, st); break;
+        case PA_CT_G64x128_9: launch_ld<64, 128, 9>(a, v, grid, st); break;
+        case PA_CT_G64x64_1: launch_ld<64, 64, 1>(a, v, grid, st); break;
+        case PA_CT_G64x64_9: launch_ld<64, 64, 9>(a, v, grid, st); break;
+        case PA_CT_OS2: launch_oneshot<2>(a, v, grid, st); break;
+        case PA_CT_OS4: launch_oneshot<4>(a, v, grid, st); break;
+        default: pa_set_error_msg("pa_launch_conv: the plan names no instance of conv_igemm.hip"); return 1;
     }
     return (int)hipGetLastError();
+}
+
+// include/poseadv.h (diagnostics): the plan of a launch as integers.  No HIP call: it answers without a device (cus: the caller's count)
+extern "C" int pa_conv_plan_describe(int B, int H, int W, int Cin, int Cout, int taps, int in_mode, int add1_mode, int add2_mode, int ep_mode,
+                                     int ep2_mode, int fin_rows, int flags, int cus, int* out, int cap) {
+    if (!out || cap < 16) { pa_set_error_msg("pa_conv_plan_describe: out is NULL or holds fewer than 16 ints"); return -1; }
+    const PaConvPlan p = pa_conv_plan(PaConvShape{B, H, W, Cin, Cout, taps, in_mode, add1_mode, add2_mode, ep_mode, ep2_mode, fin_rows, bool(flags & 1),
+                                                  bool(flags & 2), bool(flags & 4), bool(flags & 8), bool(flags & 16), bool(flags & 32), bool(flags & 64), cus});
+    static const float some_bias = 0.f;
+    PaConvArgs a{};          // the kernels' own copy of the LDS-epilogue rule, for the test that holds the two together
+    a.xcd = p.xcd; a.add1.mode = add1_mode; a.add2.mode = add2_mode; a.bias = (flags & 1) ? &some_bias : nullptr;
+    const int v[16] = {p.path, p.inst, p.gx, p.gy, p.threads, p.nbw, p.rows, p.rows2, p.xcd, p.takes_fin, p.stores_dz, p.pool_route, p.pool_in,
+                       p.bwd_lds, p.path != PA_CVP_REFUSED && pa_conv_inst_cannot_trap(p.inst), pa_bwd_epilogue_lds_ok(a)};
+    memcpy(out, v, sizeof v); if (p.path == PA_CVP_REFUSED) pa_set_error_msg(p.why);      // (an admitted plan leaves the last error as it is)
+    return 16;
+}
+// out NULL: clear the launch log and switch it on; else copy up to cap launches of 14 ints (the first 14 arguments above), switch it off, return their number
+extern "C" int pa_conv_launch_log(int* out, int cap) {
+    const int n = !out || g_nlog < 0 ? 0 : g_nlog < cap ? g_nlog : cap;
+    if (out) memcpy(out, g_log, sizeof(int) * 14 * n);
+    g_nlog = out ? -1 : 0; return n;
 }

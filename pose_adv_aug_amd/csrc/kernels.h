@@ -4,6 +4,7 @@
 #include "bn_fin.h"
 #include "launch_plan.h"
 #include "wgrad_plan.h"
+#include "conv_plan.h"
 
 struct PaConvArgs {
     PaOperand in;        // [B][H][W][Cin] NHWC bf16
@@ -14,37 +15,31 @@ struct PaConvArgs {
     PaEpilogue ep;
     bf16* out;           // [M][Cout]
     int B, H, W, Cin, Cout, taps;
-    bf16* dz_out;        // optional (1x1 row-tile kernel, LIN2 input): the transformed input tile is also stored here [M][Cin] --
+    bf16* dz_out;        // optional (tile kernels, LIN2 input; PaConvPlan::stores_dz): the transformed input tile is also stored here [M][Cin] --
                          // later consumers of the same BatchNorm-backward gradient read ONE tensor instead of recomputing it from two
-    PaBnFin fin;         // pending BatchNorm finalize of `in`, done in the kernel's prologue (fin.rows > 0; only launches pa_conv_takes_fin() admits)
+    PaBnFin fin;         // pending BatchNorm finalize of `in`, done in the kernel's prologue (fin.rows > 0; only launches whose plan says takes_fin)
     int low_prio;        // != 0: a launch of a side branch (skip blocks beside the main chain): the kernel keeps wave priority 0 instead of PA_MAIN_PRIO
     int dbg;             // tuning builds only (0 in the release library): conv3x3_tile.hip phase ablation bits 1 / 2 / 4, bit 8 = per-workgroup tap rotation
-    int xcd;             // set by the launchers: workgroup i works on tile (i % 8) * (tiles / 8) + i / 8 (one contiguous range per XCD)
+    int xcd;             // set by the launchers from the plan: bit 0: workgroup i works on tile (i % 8) * (tiles / 8) + i / 8 (one contiguous range per XCD)
     // round 6 -- the LOW half of the upsample-add backward (reference models/asn_stacked_hg.py:192-203) folded into the 1x1 data gradient that
-    // produces d(merged) (pa_conv1x1_tile_up_supported): besides `out` = d(merged) [B][H][W][Cout] the launch stores
+    // produces d(merged) (conv_plan.h: PA_CVP_ROW_UP): besides `out` = d(merged) [B][H][W][Cout] the launch stores
     // out2 [B][H/2][W/2][Cout] = ep2(sum of the 2x2 block of d(merged)) with ep2's BatchNorm-backward mask and its two partial reductions
     PaEpilogue ep2;
     bf16* out2;          // nullptr = off
 };
-// the row-tile instance whose workgroups own 2 image rows x 32 columns and carry the epilogue above
-bool pa_conv1x1_tile_up_supported(const PaConvArgs& a);
-// stat_rows (optional) receives the number of partial-statistics rows the launch writes (= grid.x)
-int pa_launch_conv(const PaConvArgs& a, hipStream_t st, int* stat_rows = nullptr);
-// will pa_launch_conv send this launch to a kernel that carries the finalize prologue (generic kernel, 3x3 tile kernel)?
-bool pa_conv_takes_fin(const PaConvArgs& a);
-// may add2 of this launch be pool-routed (PA_LD_POOL: the gradient of a 2x2 max pool read through its arg-max map)?  Only instances of their own
-// carry the mode: the row-tile 1x1 kernel's and the one-shot 1x1 kernel's for 128 input channels
-bool pa_conv_pool_route_supported(const PaConvArgs& a);
-// ... and may its INPUT be pool-routed: a BatchNorm-backward load (k0 / k1 / k2, q) whose first operand is the routed, ReLU-masked gradient of a
-// 2x2 max pool (in.p: gradient of the pooled tensor, in.map; ep2.scale / shift: the mask's BatchNorm), stored transformed to dz_out?
-bool pa_conv_pool_in_supported(const PaConvArgs& a);
-// halo-tile 3x3 kernel (conv3x3_tile.hip); pa_launch_conv dispatches to it when the shape is supported
-bool pa_conv3x3_tile_supported(const PaConvArgs& a);
-bool pa_conv3x3_tile_takes_fin(const PaConvArgs& a);      // ... and the instance it would run exists with the finalize prologue
-int pa_launch_conv3x3_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows = nullptr);
-// row-tile 1x1 kernel (conv1x1_tile.hip), same dispatch rule
-bool pa_conv1x1_tile_supported(const PaConvArgs& a);
-int pa_launch_conv1x1_tile(const PaConvArgs& a, hipStream_t st, int* stat_rows = nullptr);
+// Which instance takes a launch, its grid, its partial rows and what it can carry: conv_plan.h ONLY.  pa_conv_shape: the planner's input of a launch
+int pa_conv_cus();       // compute units of the current device, asked once (0: unknown)
+inline PaConvShape pa_conv_shape(const PaConvArgs& a) {
+    return PaConvShape{a.B, a.H, a.W, a.Cin, a.Cout, a.taps, a.in.mode, a.add1.mode, a.add2.mode, a.ep.mode, a.ep2.mode, a.fin.rows, a.bias != nullptr,
+                       a.out2 != nullptr, a.dz_out != nullptr, a.in.map != nullptr, a.in.q != nullptr, a.ep2.scale && a.ep2.shift, a.add2.map != nullptr,
+                       pa_conv_cus()};
+}
+// Plans the launch (or takes the caller's plan of the same arguments) and runs the plan's instance; refused: message set, 1.  stat_rows: PaConvPlan::rows
+int pa_launch_conv(const PaConvArgs& a, const PaConvPlan& p, hipStream_t st, int* stat_rows = nullptr);
+inline int pa_launch_conv(const PaConvArgs& a, hipStream_t st, int* stat_rows = nullptr) { return pa_launch_conv(a, pa_conv_plan(pa_conv_shape(a)), st, stat_rows); }
+// the tile kernels, called by pa_launch_conv with the plan that chose them: halo-tile 3x3 (conv3x3_tile.hip), row-tile 1x1 (conv1x1_tile.hip)
+int pa_launch_conv3x3_tile(const PaConvArgs& a, const PaConvPlan& p, hipStream_t st);
+int pa_launch_conv1x1_tile(const PaConvArgs& a, const PaConvPlan& p, hipStream_t st);
 // upper bound of stat rows any conv / elementwise launch writes for a tensor with M pixels
 inline int pa_max_stat_rows(int M) { int r = (M + 63) / 64; return r < 512 ? 512 : r; }
 
@@ -110,7 +105,7 @@ int pa_launch_bn_bwd_finalize(const float* bstats, int rows, const float* scale,
 int pa_launch_maxpool_fwd(const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st, unsigned char* map = nullptr, bf16* xmax = nullptr);
 // The partial rows of pa_launch_maxpool_bwd(dout, in, none, ep, ...) with a BatchNorm-backward epilogue on the pooled tensor itself, same bits,
 // from dout and xmax alone (a quarter of the traffic, no output): for a pool whose routed gradient is formed by its reader
-// (pa_conv_pool_in_supported).  supported: both launches of the pool take their streaming kernels.
+// (PaConvPlan::pool_in).  supported: both launches of the pool take their streaming kernels.
 bool pa_pool_stats_route_supported(const PaOperand& in, const PaEpilogue& ep, int B, int H, int W, int C);
 int pa_launch_maxpool_bwd_stats(const bf16* dout, const bf16* xmax, const PaOperand& in, const PaEpilogue& ep, int B, int H, int W, int C,
                                 hipStream_t st, int* stat_rows = nullptr);

@@ -102,7 +102,7 @@ struct Residual {
     int bwd(Net& n, const Act& in, const PaOperand& extra, bool in_needs_grad);
     // round 6: `in` is the upsample-add output merged[k] of an hourglass and low_of_in the low-resolution tensor up[k].x3 under it -- conv1's data
     // gradient (which produces d merged) then also emits d up[k].x3 (2 x 2 sums, mask, reductions) where its tile kernel can
-    // (Net::conv_dgrad / pa_conv1x1_tile_up_supported); low_fused says whether it did
+    // (Net::conv_dgrad / conv_plan.h: PA_CVP_ROW_UP); low_fused says whether it did
     const Act* low_of_in = nullptr;
     bool low_fused = false;
     // the gradient of x3 arrives pool-routed (Net::stem_route_ok): conv3's data gradient forms dz from g3_pool (PA_LD_POOL) and g3_pool_ep's mask

@@ -373,11 +373,11 @@ int Net::finish_grad2(const Act& a, const Act& b) {
 bool Net::fin_consumer_ok(const ConvLayer& c, int B_, int H, int W, bool dgrad) const {
     if (fin_rows_max <= 0 || !train_bn || c.k == 7) return false;
     if ((long)B_ * H * W > 64L * PA_FIN_SMALL_ROWS) return false;          // (no producer tiling leaves <= 128 rows above that)
-    PaConvArgs a; memset(&a, 0, sizeof a);
-    a.B = B_; a.H = H; a.W = W; a.taps = c.taps();
-    a.Cin = dgrad ? c.pcout : c.pcin; a.Cout = dgrad ? c.pcin : c.pcout;
-    a.in.mode = dgrad ? PA_LD_LIN2 : PA_LD_BNRELU;
-    return pa_conv_takes_fin(a);
+    PaConvShape s{};
+    s.B = B_; s.H = H; s.W = W; s.taps = c.taps(); s.cus = pa_conv_cus();
+    s.Cin = dgrad ? c.pcout : c.pcin; s.Cout = dgrad ? c.pcin : c.pcout;
+    s.in_mode = dgrad ? PA_LD_LIN2 : PA_LD_BNRELU;
+    return pa_conv_plan(s).takes_fin;
 }
 
 PaBnFin Net::fin_fwd(const BNLayer& b, int M) const {
@@ -430,38 +430,25 @@ int Net::conv_dgrad(ConvLayer& c, const PaOperand& dy, int B_, int H, int W, con
     if (pending_in && pending_in->bfin_pending) { a.fin = fin_bwd(*pending_in, B_ * H * W); pending_in->bfin_pending = false; }
     a.in = dy; a.w = c.wb; a.bias = nullptr; a.add1 = add1; a.add2 = add2; a.out = out; a.ep = ep; a.low_prio = on_side ? 1 : 0;
     a.B = B_; a.H = H; a.W = W; a.Cin = c.pcout; a.Cout = c.pcin; a.taps = c.taps();
-    if (dz_done) *dz_done = false;
-    if (dy.mode == PA_LD_POOL) {                   // (Net::stem_route_ok checked pa_conv_pool_in_supported: the instance stores dz)
+    if (dy.mode == PA_LD_POOL) {                   // (Net::stem_route_ok read the plan: the instance stores dz)
         if (!pool_in_ep || !dz_out) { pa_set_error_msg("conv_dgrad: a pool-routed gradient needs its mask and a dz buffer"); return 1; }
-        a.ep2 = *pool_in_ep; a.dz_out = dz_out; if (dz_done) *dz_done = true;
+        a.ep2 = *pool_in_ep;
     }
-    if (dz_out && dy.mode == PA_LD_LIN2) {         // only the 1x1 row-tile kernel stores its transformed input
-        const PaTuning& t = pa_tuning();
-        const bool off = t.conv1_old || t.no_dz3, off3 = t.conv3_old || t.no_dz2;
-        if ((!off && a.taps == 1 && pa_conv1x1_tile_supported(a)) || (!off3 && a.taps == 9 && pa_conv3x3_tile_supported(a))) { a.dz_out = dz_out; if (dz_done) *dz_done = true; }
-    }
+    if (dy.mode == PA_LD_POOL || dy.mode == PA_LD_LIN2) a.dz_out = dz_out;      // stored where the plan's instance does (PaConvPlan::stores_dz)
+    // the low-resolution half of the upsample-add backward in this launch's epilogue (round 6): an instance of the row-tile 1x1 kernel
+    if (low && dy.mode != PA_LD_POOL && pa_tuning().upadd_fuse && low->bn && !drop_mask && !(ablate() & 1024)) { a.out2 = low->grad; a.ep2 = final_ep(*low); }
+    PaConvPlan p = pa_conv_plan(pa_conv_shape(a));
+    if (a.out2 && p.path != PA_CVP_ROW_UP) { a.out2 = nullptr; memset(&a.ep2, 0, sizeof a.ep2); p = pa_conv_plan(pa_conv_shape(a)); }      // not that instance's launch: on its own
+    const bool up = p.path == PA_CVP_ROW_UP; if (dz_done) *dz_done = p.stores_dz;
     double wb, wf; conv_work(B_ * H * W, c.Cin, c.Cout, c.taps(), false, wb, wf);
     ProfEntry* pe = prof.begin((long)B_ * H * W < PA_PROF_LOW_M ? PA_PROF_LOW_DGRAD : (c.k == 3 ? PA_PROF_DGRAD3 : PA_PROF_DGRAD1), wb, wf, st);
     if ((c.k == 3 && (ablate() & 8)) || (c.k == 1 && (ablate() & 16)) || ((ablate() & 256) && H <= ablate_h())) { if (a.ep.rows_out) *a.ep.rows_out = 1; prof.end(pe, st); return 0; }
-    if (dy.mode == PA_LD_POOL) {
-        { const double M = (double)B_ * H * W;
-          cnt(opb(dy, M * a.Cin) + 2.0 * M * a.Cout + 2.0 * a.Cout * a.taps * a.Cin, 2.0 * M * a.Cout + 2.0 * M * a.Cin); }
-        int rc = pa_launch_conv(a, st);
-        prof.end(pe, st);
-        return rc;
-    }
-    // the low-resolution half of the upsample-add backward in this launch's epilogue (round 6): an instance of the row-tile 1x1 kernel
-    const bool up_fuse = pa_tuning().upadd_fuse && !pa_tuning().conv1_old;
-    bool up = false;
-    if (low && up_fuse && low->bn && !drop_mask && !(ablate() & 1024)) {
-        a.out2 = low->grad; a.ep2 = final_ep(*low);
-        if (pa_conv1x1_tile_up_supported(a)) up = true; else { a.out2 = nullptr; memset(&a.ep2, 0, sizeof a.ep2); }
-    }
     { const double M = (double)B_ * H * W;
-      cnt(opb(dy, M * a.Cin) + opb(add1, M * a.Cout) + opb(add2, M * a.Cout) + (ep.mode == PA_OUT_BWD ? 2.0 * M * a.Cout : 0.0) + 2.0 * a.Cout * a.taps * a.Cin
-              + (up ? 2.0 * M * a.Cout / 4 : 0.0),
-          2.0 * M * a.Cout + (a.dz_out ? 2.0 * M * a.Cin : 0.0) + (up ? 2.0 * M * a.Cout / 4 : 0.0)); }
-    int rc = up ? pa_launch_conv1x1_tile(a, st) : pa_launch_conv(a, st);
+      if (dy.mode == PA_LD_POOL) cnt(opb(dy, M * a.Cin) + 2.0 * M * a.Cout + 2.0 * a.Cout * a.taps * a.Cin, 2.0 * M * a.Cout + 2.0 * M * a.Cin);
+      else cnt(opb(dy, M * a.Cin) + opb(add1, M * a.Cout) + opb(add2, M * a.Cout) + (ep.mode == PA_OUT_BWD ? 2.0 * M * a.Cout : 0.0) + 2.0 * a.Cout * a.taps * a.Cin
+                   + (up ? 2.0 * M * a.Cout / 4 : 0.0),
+               2.0 * M * a.Cout + (p.stores_dz ? 2.0 * M * a.Cin : 0.0) + (up ? 2.0 * M * a.Cout / 4 : 0.0)); }
+    int rc = pa_launch_conv(a, p, st);
     if (up && low_done) *low_done = true;
     prof.end(pe, st);
     return rc;
@@ -801,10 +788,10 @@ bool Hourglass::route_ok(Net& n, int k, const Act& x, const PaOperand& ex0) {
     if (ex0.mode != PA_LD_NONE && ex0.mode != PA_LD_PLAIN) return false;
     Residual& r = skip[k].head();
     if (r.has_adapter || r.low_of_in) return false;
-    PaConvArgs a; memset(&a, 0, sizeof a);
-    a.in = n.gradop(r.x1); a.add1 = pa_plain(r.dz3); a.add2 = pa_none(); a.ep = n.final_ep(x);
-    a.B = x.B; a.H = x.H; a.W = x.W; a.Cin = r.c1.pcout; a.Cout = r.c1.pcin; a.taps = r.c1.taps();
-    return pa_conv_pool_route_supported(a);
+    PaConvShape s{};
+    s.B = x.B; s.H = x.H; s.W = x.W; s.Cin = r.c1.pcout; s.Cout = r.c1.pcin; s.taps = r.c1.taps(); s.cus = pa_conv_cus();
+    s.in_mode = n.gradop(r.x1).mode; s.add1_mode = PA_LD_PLAIN; s.add2_mode = PA_LD_POOL; s.add2_map = true; s.ep_mode = n.final_ep(x).mode;
+    return pa_conv_plan(s).pool_route;
 }
 
 int Hourglass::fill_poolgrad(Net& n, int k, const Act& in) {
@@ -1102,11 +1089,11 @@ bool Net::stem_route_ok() {
     if (!(pool_route & 2) || !stem_map_written || (ablate() & (2048 | 16 | 4))) return false;
     const int H = res / 2;
     if (!pa_pool_stats_route_supported(op(res1.x3), final_ep(res1.x3), B, H, H, 128)) return false;
-    PaConvArgs a; memset(&a, 0, sizeof a);
-    a.in = gradop(res1.x3); a.in.map = stem_map; a.add1 = pa_none(); a.add2 = pa_none(); a.ep = final_ep(res1.x2); a.ep2 = final_ep(res1.x3);
-    a.dz_out = res1.dz3; a.out = res1.x2.grad;
-    a.B = B; a.H = H; a.W = H; a.Cin = res1.c3.pcout; a.Cout = res1.c3.pcin; a.taps = res1.c3.taps();
-    return pa_conv_pool_in_supported(a);
+    const PaEpilogue mask = final_ep(res1.x3); PaConvShape s{};
+    s.B = B; s.H = H; s.W = H; s.Cin = res1.c3.pcout; s.Cout = res1.c3.pcin; s.taps = res1.c3.taps(); s.cus = pa_conv_cus();
+    s.in_mode = PA_LD_POOL; s.in_map = stem_map != nullptr; s.in_q = gradop(res1.x3).q != nullptr; s.want_dz = res1.dz3 != nullptr;
+    s.add1_mode = s.add2_mode = PA_LD_NONE; s.ep_mode = final_ep(res1.x2).mode; s.ep2_affine = mask.scale && mask.shift;
+    return pa_conv_plan(s).pool_in;
 }
 
 int Net::fill_stem_grad() {

@@ -36,7 +36,7 @@ dz * (x - mean) * invstd, bn_eval_kernel), with u = 2^-24 and these rules (class
     At C = 512 (the chan-512 legs; re-derived from launch_plan.h, kernels.h and bn_fin.h, nothing changes in D): C / 8 = 64 channel
     groups fill a wave, so flush_stats shuffles over no level at all (<= 6) and the workgroups tried (512 / 256; 384, 192 and 128 are
     no multiples of 64) have <= 8 waves (<= 16); the item count per thread is the same formula in C; the row capacity
-    pa_max_stat_rows = max(512, ceil(n / 64)) does not depend on C; and the consumer-prologue finalize, which pa_conv_takes_fin does not
+    pa_max_stat_rows = max(512, ceil(n / 64)) does not depend on C; and the consumer-prologue finalize, which the plan's takes_fin does not
     admit above 256 input channels, is replaced by the launch form, whose order for R <= 128 rows is the prologue's own (8 + 4 deep,
     reduce_partial_rows) and for more rows ceil(R / 64) + 20 as above.
   * the backward sum of dz * xhat is written in two forms: per term dz * (x - mean) * invstd (epilogue8, Bwd8, pa_conv_epilogue),

@@ -78,10 +78,16 @@ def test_every_bn_pool_and_merge_is_exact_with_a_middle_stack_after_warm_steps_a
 
 # ---- the step with occlusion masks: 2 stacks, chan 128, B 2, 256 x 256 as the history legs above.  Which blocks store dz2 / dz3 does not
 # change under masks: Net::drop_mask switches x3_fin_ok off, which only moves x3's backward FINALIZE out of conv3's data-gradient prologue
-# into a launch of its own; whether that data gradient stores dz3 (dz2) is Net::conv_dgrad's pa_conv1x1_tile_supported /
-# pa_conv3x3_tile_supported over the shape alone (net.hip:425-429), and the 64 x 64 maps of these legs are taken by both.  So both kinds stay expected.
+# into a launch of its own; whether that data gradient stores dz3 (dz2) is the plan's stores_dz over shape and modes alone, which the
+# first leg asserts for residual1's maps (128 x 128: both) and the hourglass blocks' (64 x 64: dz2).  So both kinds stay expected.
+def _stores_dz(B, H, Cin, Cout, taps):
+    from tests import conv_plan_query as Q
+    return Q.plan(B, H, H, Cin, Cout, taps, in_=Q.LIN2, ep=Q.OUT_BWD, flags=Q.DZ)['stores_dz']
+
+
 @pytest.mark.parametrize('history', ('fresh', 'warm'))
 def test_every_bn_pool_merge_and_cell_mask_is_exact_in_a_masked_step(history):
+    assert _stores_dz(2, 128, 128, 64, 1) and _stores_dz(2, 128, 64, 64, 9) and _stores_dz(2, 64, 64, 64, 9) and not _stores_dz(2, 64, 128, 64, 1)
     _leg(2, 128, 2, 256, 54, history=history, masks=540)
 
 
@@ -95,7 +101,7 @@ def test_every_bn_pool_merge_and_cell_mask_is_exact_in_a_masked_step_with_a_midd
 
 
 # ---- chan 512: C / 8 = 64 channel groups, the most pa_stats_groups_ok admits -- a wave of a streaming kernel is exactly one pixel and
-# flush_stats has no lane left to shuffle with.  pa_conv_takes_fin returns false above 256 input channels, so the BatchNorm in front of
+# flush_stats has no lane left to shuffle with.  The plan's takes_fin is false above 256 input channels, so the BatchNorm in front of
 # every conv1 (512 -> 256) and of every conv3 data gradient (512 gradient channels) is finalized by a launch of its own
 # (bn_finalize_kernel / the backward finalize, reduce_partial_rows in its <= 128-row order) where the nets above use the consumer
 # prologue; the statistics and BatchNorm-backward epilogues run in the generic conv kernel's tiles (tests/test_gpu_conv_exact.py names the
@@ -106,6 +112,11 @@ def test_every_bn_pool_merge_and_cell_mask_is_exact_in_a_masked_step_with_a_midd
 def test_every_bn_pool_and_merge_is_exact_at_chan_512_on_tiny_maps(history):
     """2 stacks, chan 512, B 2, 128 x 128: maps 32 x 32 ... 2 x 2, <= 32 partial rows everywhere in the hourglasses (the finalize
     launches' small-row order), the inner head; 'warm': running estimates and weights from a non-initial state."""
+    from tests import conv_plan_query as Q
+    # no consumer prologue above 256 input channels: conv1's forward (512 -> 256) and conv3's data gradient (512 gradient channels); conv2's has one
+    assert not Q.plan(2, 32, 32, 512, 256, 1, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)['takes_fin']
+    assert not Q.plan(2, 32, 32, 512, 256, 1, in_=Q.LIN2, ep=Q.OUT_BWD, flags=Q.DZ)['takes_fin']
+    assert Q.plan(2, 32, 32, 256, 256, 9, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)['takes_fin']
     _leg(2, 512, 2, 128, 71, stored_expected=('.x2',), history=history)
 
 

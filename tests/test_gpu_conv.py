@@ -93,6 +93,12 @@ SHAPES = [
     (8, 512, 256, 64, 64, 1),    # M = 32768: <128,128>
     (8, 256, 512, 64, 64, 1),    # forward: the row-tile kernel (256 input channels, 512 row tiles); data gradient <128,128>
     (8, 256, 256, 64, 64, 3),    # <128,128>, nine taps
+    # the tilings no shape above reaches (tests/test_conv_plan_cpu.py asks the planner): the generic <128,64> tier with one and nine taps,
+    # <64,128> with nine taps, and the 16 x 8 halo tiles of 128 input channels with a 64-channel output block (512 tiles: B 16 at 64 x 64)
+    (8, 512, 64, 64, 64, 1),
+    (8, 256, 64, 64, 64, 3),
+    (4, 256, 128, 64, 64, 3),
+    (16, 128, 64, 64, 64, 3),
 ]
 
 

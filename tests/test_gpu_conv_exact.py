@@ -24,13 +24,16 @@ import torch
 from tests import conv_exact as X
 from tests import inputs
 from tests.test_gpu_conv import SHAPES, run_conv
+from tests import conv_plan_query as Q
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _leg(stacks, chan, B, res, seed, **kw):
-    worst, fails = X.run_leg(stacks, chan, B, res, seed, **kw)
+    # the engine's launch log: the leg still makes every convolution launch tests/test_conv_plan_cpu.py counts it for
+    with Q.launches('conv_exact %d stacks chan %d B %d res %d %s' % (stacks, chan, B, res, ' '.join('%s=%s' % (k, kw[k]) for k in sorted(kw) if k != 'expect'))):
+        worst, fails = X.run_leg(stacks, chan, B, res, seed, **kw)
     assert not fails, '%d checks outside their bound, first: %s (worst per kind: %s)' % (len(fails), fails[:12], worst)
 
 
@@ -100,23 +103,31 @@ def test_every_conv_is_exact_in_a_masked_step_with_a_middle_stack():
 # launch_taps) with the net's BNRELU / LIN2 loads and statistics / BatchNorm-backward epilogues, at K = 512 (8 steps) or 2304; the
 # 256 -> 512 forward and the 512 -> 256 data gradient (256 input channels) take the one-shot kernel below 12288 pixels and the row-tile
 # kernel from there.  The weight-gradient plans have 8 (1 x 1) and 16 (3 x 3) channel blocks.  Each leg is the smallest batch that
-# reaches its tile of the generic kernel (pa_launch_conv: bigM = M >= 32768, <64,128> from M >= 16384 at Cout % 128 == 0); the stem
-# blocks (64 -> 128, 128 -> 128) run as at every chan.
+# reaches its tile of the generic kernel, which the leg asserts through the planner's query (_tier); the stem blocks (64 -> 128,
+# 128 -> 128) run as at every chan.
+def _tier(B, H, Cin, Cout, taps=1):
+    """tiling of a forward launch of the net (BatchNorm + ReLU on load, statistics epilogue, bias) on an H x H map"""
+    return Q.plan(B, H, H, Cin, Cout, taps, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)['tiling']
+
+
 @pytest.mark.parametrize('history', ('fresh', 'warm'))
 def test_every_conv_is_exact_at_chan_512_on_tiny_maps(history):
     """2 stacks, chan 512, B 2, 128 x 128: maps 32 x 32 ... 2 x 2, every generic launch on the <64,64> instance (M <= 2048), the inner
     head (forth_conv 512 -> 512, in_conv 64 -> 512); 'warm': the weight copies repacked by optimizer steps."""
+    assert {_tier(2, H, 512, 256) for H in (32, 16, 8, 4, 2)} == {'G64x64_1'} and _tier(2, 32, 256, 256, 9) == 'G64x64_9'
     _leg(2, 512, 2, 128, 71, expect=('group',), history=history)
 
 
 def test_every_conv_is_exact_at_chan_512_on_the_64x128_tiles():
-    """1 stack, chan 512, B 4, 256 x 256: the 64 x 64 maps have M = 16384, the <64,128> instance of the generic kernel (bigN && M >= 64 * 256)."""
+    """1 stack, chan 512, B 4, 256 x 256: the 64 x 64 maps have M = 16384, the <64,128> instance of the generic kernel."""
+    assert (_tier(4, 64, 512, 256), _tier(4, 64, 256, 256, 9)) == ('G64x128_1', 'G64x128_9')
     _leg(1, 512, 4, 256, 72, expect=('group',))
 
 
 def test_every_conv_is_exact_at_chan_512_on_the_128_row_tiles():
     """1 stack, chan 512, B 8, 256 x 256: the 64 x 64 maps have M = 32768 (bigM), the <128,128> instance (and <128,64> for out_conv's
     forward, 512 -> 64) with the net's load and epilogue modes; the 32 x 32 maps (M = 8192) stay on <64,64>."""
+    assert (_tier(8, 64, 512, 256), _tier(8, 64, 512, 64), _tier(8, 64, 256, 256, 9), _tier(8, 32, 512, 256)) == ('G128x128_1', 'G128x64_1', 'G128x128_9', 'G64x64_1')
     _leg(1, 512, 8, 256, 73, expect=('group',))
 
 

@@ -57,8 +57,11 @@ def test_two_module_chains_are_exact_in_a_masked_step():
 
 def test_two_module_chains_are_exact_at_chan_512():
     """1 stack, 2 modules, chan 512, B 2, 128 x 128: block 1 of every chain reads a 512-channel tensor with a pending BatchNorm that has
-    two readers and no consumer prologue (pa_conv_takes_fin: not above 256 input channels) -- a finalize launch of its own; the generic
+    two readers and no consumer prologue (PaConvPlan::takes_fin: not above 256 input channels) -- a finalize launch of its own; the generic
     <64,64> kernel at K = 512 / 2304.  Only the stem's 3 x 3 tile launches store a gradient at this size (dz2)."""
+    from tests import conv_plan_query as Q
+    d = Q.plan(2, 32, 32, 512, 256, 1, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)
+    assert not d['takes_fin'] and d['tiling'] == 'G64x64_1' and Q.plan(2, 32, 32, 256, 256, 9, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)['tiling'] == 'G64x64_9'
     _leg(1, 2, 512, 2, 128, 90, expect=('group',), stored_expected=('.x2',))
 
 

@@ -58,11 +58,14 @@ def _train(route, B, res, stacks, modules=1, masks=None, kind='random', want=(),
     _lib.check(_lib.lib().pa_net_set_pool_route(h, 1 if route else 0), 'pa_net_set_pool_route')
     opt = RMSprop(net, lr=2.5e-4)
     pts = torch.from_numpy(inputs.heat_pts(17, B, res=res // 4)).cuda()
-    for i in range(STEPS):
-        img = _images(kind, 30 + i, B, res).cuda()
-        loss, outs = net.loss_and_backward(img, pts, want_outputs=True, dropout_masks=masks)
-        if i + 1 < STEPS:
-            opt.step()
+    from tests import conv_plan_query as Q
+    # (the engine's launch log: tests/test_conv_plan_cpu.py counts the routed launches of these steps as covered)
+    with Q.launches('pool_route route %d B %d res %d stacks %d modules %d chan %d masks %s' % (route, B, res, stacks, modules, chan, masks is not None)):
+        for i in range(STEPS):
+            img = _images(kind, 30 + i, B, res).cuda()
+            loss, outs = net.loss_and_backward(img, pts, want_outputs=True, dropout_masks=masks)
+            if i + 1 < STEPS:
+                opt.step()
     design = (C.c_double * 2)()
     _lib.check(_lib.lib().pa_net_design_bytes(h, design), 'pa_net_design_bytes')
     views = [(_dbg(h, n, v), _dbg(h, n, v)) for n, v in want]
@@ -150,15 +153,18 @@ def test_requested_tensors_are_what_the_unrouted_step_stored(res, stacks):
 
 def test_chan_512_routes_the_stem_pool_only_and_gives_the_same_bits():
     """The mixed state: 1 stack, chan 512, B 2, 256 x 256.  The hourglass pools cannot be routed -- the skip block's conv1 data gradient has
-    256 gradient channels and pa_conv_pool_route_supported needs 128 (Hourglass::route_ok) -- so each level falls back to a pool backward
+    256 gradient channels and the plan's pool_route needs 128 (Hourglass::route_ok; asserted below) -- so each level falls back to a pool backward
     launch into poolgrad<k>, although the forward pools still store their arg-max maps; the stem's pool is routed as at every chan
     (residual1 is 64 -> 128).  Every compared tensor is bit-identical, and hg0.poolgrad1..4, which the routed step stored itself here,
     equal what the unrouted step stored."""
     want = [('hg0.poolgrad%d' % k, 2) for k in (1, 2, 3, 4)] + [('res1', 1), ('res1', 3), ('res1', 4)]
     c = dict(B=2, res=256, stacks=1, chan=512, want=want)
+    from tests.conv_plan_query import plan, PLAIN, LIN2, POOL, OUT_BWD, DZ, IN_MAP, IN_Q, EP2_AFFINE, ADD2_MAP
+    assert not any(plan(2, H, H, 256, 512, 1, in_=LIN2, a1=PLAIN, a2=POOL, ep=OUT_BWD, flags=ADD2_MAP)['pool_route'] for H in (64, 32, 16, 8))
+    assert plan(2, 128, 128, 128, 64, 1, in_=POOL, ep=OUT_BWD, flags=DZ | IN_MAP | IN_Q | EP2_AFFINE)['pool_in']
     off, on = _train(False, **c), _train(True, **c)
     # pa_net_design_bytes: Net::stem_route_ok holds at this size whatever the chan -- residual1's conv3 data gradient (128 gradient channels,
-    # 64 outputs, 2 * 128 * 128 = 32768 pixels = 512 row tiles >= 192) is a launch pa_conv_pool_in_supported admits, and the pool's statistics
+    # 64 outputs, 2 * 128 * 128 pixels) is a launch whose plan says pool_in (asserted above), and the pool's statistics
     # launch is planned over 128 channels -- so the routed step skips the write and the re-read of residual1's full-resolution gradient and
     # _compare's STRICT assertion applies (read and written bytes both smaller), as for the cases above; 'not greater' would be the
     # assertion of a size whose stem pool is not routed either (res 128).
