@@ -247,6 +247,34 @@ int pa_rmsprop_step_opts(const pa_rmsprop_opts* o, float* param, const float* gr
 size_t pa_grad_norm_workspace_bytes(size_t n);
 int pa_grad_norm(const float* grad, size_t n, float gscale, float max_norm, void* workspace, float* out2, void* stream);
 
+/* torch.optim.Adam / AdamW (with AMSGrad) as one fused step on flat fp32 arrays.  The reference trains with RMSprop only: these calls have
+ * no reference counterpart beyond torch's option set.  Per element, in fp32 and in this order (torch 2.10 _single_tensor_adam,
+ * non-capturable branch):
+ *   gr = (grad * gscale) * clip_coef[0];   coupled decay (decoupled 0, weight_decay != 0): gr += weight_decay * param;
+ *   decoupled decay (decoupled 1, weight_decay != 0): param *= (float)(1.0 - (double)lr * (double)weight_decay);
+ *   m = m + (gr - m) * (1.f - beta1);  v = beta2 v + ((1.f - beta2) gr) gr;  vmax = max(vmax, v) (amsgrad);
+ *   den = sqrtf(amsgrad ? vmax : v) / bc2s + eps;  param -= step_size * (m / den)
+ * with bc1 = (float)(1.0 - pow((double)beta1, (double)t)), bc2 likewise, bc2s = sqrtf(bc2), step_size = lr / bc1, t = the number of
+ * steps TAKEN including this one.  t lives on the device, in `state`, because the half-precision build decides on the device whether
+ * a step is taken (a gradient that holds inf / NaN: the step is skipped, every array untouched): a host counter would drift from the
+ * moments after the first skipped step.
+ * state: 32 bytes on the device, 16-byte aligned, zeroed once by the caller and owned by ONE optimizer.  flag / skipped are the pair
+ * of pa_rmsprop_step_state (pa_rmsprop_skipped_steps_state may be pointed at it); step = steps taken so far; bc1, bc2, step_size,
+ * bc2s = the constants the last TAKEN step used.  A one-thread launch in front of the step advances `step` and writes the constants,
+ * or, with the flag set, counts a skipped step and leaves them.
+ * exp_avg, exp_avg_sq: n floats; max_exp_avg_sq: n floats, required iff amsgrad; clip_coef: one device float (out2 + 1 of
+ * pa_grad_norm) or NULL.
+ * Errors (non-zero, pa_last_error set, nothing launched): a NULL opts / param / grad / exp_avg / exp_avg_sq / state, a missing or
+ * superfluous max_exp_avg_sq, beta1 or beta2 outside [0, 1), eps <= 0, weight_decay < 0, a state that is not 16-byte aligned. */
+typedef struct pa_adam_opts  { float lr, beta1, beta2, eps, weight_decay; int32_t amsgrad, decoupled; } pa_adam_opts;
+typedef struct pa_adam_state { int32_t flag, skipped, step, reserved; float bc1, bc2, step_size, bc2s; } pa_adam_state;
+int pa_adam_step(const pa_adam_opts* o, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                 float* max_exp_avg_sq, size_t n, float gscale, const float* clip_coef, pa_adam_state* state, void* stream);
+/* *steps = steps taken, *skipped = steps skipped so far (either may be NULL); synchronises `stream`.  Errors: a NULL or misaligned state. */
+int pa_adam_steps(const pa_adam_state* state, long long* steps, long long* skipped, void* stream);
+/* state->step = steps, on `stream` (load_state_dict); the other words stay.  Errors: a NULL or misaligned state, steps < 0 or > INT32_MAX. */
+int pa_adam_set_steps(pa_adam_state* state, long long steps, void* stream);
+
 /* ---------------------------------------------------------------- operator level ---------- */
 /* One residual bottleneck block _Residual(C, C) (models/asn_stacked_hg.py:11-49), forward + backward,
  * NCHW fp32 in/out, parameters in the block's own state_dict order (flat fp32).  Used by the parity

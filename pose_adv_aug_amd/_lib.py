@@ -66,6 +66,12 @@ class RmspropOpts(C.Structure):
     """pa_rmsprop_opts of include/poseadv.h (pass C.byref of it to pa_rmsprop_step_opts)"""
     _fields_ = [('lr', _f), ('alpha', _f), ('eps', _f), ('momentum', _f), ('weight_decay', _f), ('centered', C.c_int32)]
 
+
+class AdamOpts(C.Structure):
+    """pa_adam_opts of include/poseadv.h (pass C.byref of it to pa_adam_step)"""
+    _fields_ = [('lr', _f), ('beta1', _f), ('beta2', _f), ('eps', _f), ('weight_decay', _f), ('amsgrad', C.c_int32), ('decoupled', C.c_int32)]
+
+
 _PROTOS = {
     'pa_last_error': (C.c_char_p, []),
     'pa_version': (_i, []),
@@ -105,6 +111,9 @@ _PROTOS = {
     'pa_rmsprop_step_opts': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
     'pa_grad_norm_workspace_bytes': (_sz, [_sz]),
     'pa_grad_norm': (_i, [_vp, _sz, _f, _f, _vp, _vp, _vp]),
+    'pa_adam_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
+    'pa_adam_steps': (_i, [_vp, _vp, _vp, _vp]),
+    'pa_adam_set_steps': (_i, [_vp, C.c_longlong, _vp]),
     'pa_residual_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'pa_residual_fwd_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'pa_conv2d_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -174,6 +174,39 @@ int pa_grad_norm(const float* g, size_t n, float gscale, float max_norm, void* w
     if (reinterpret_cast<uintptr_t>(workspace) & 7) { pa_set_error_msg("pa_grad_norm: workspace must be 8-byte aligned (double partial sums)"); return 1; }
     TRY(pa_launch_grad_norm(g, n, gscale, max_norm, workspace, out2, ST(s))); return 0;
 }
+// torch.optim.Adam / AdamW (no reference counterpart beyond torch's option set); the step count and the bias-correction constants live in
+// the optimizer's device state.  An argument error launches nothing.
+static_assert(sizeof(pa_adam_state) == 32 && sizeof(PaAdamState) == 32, "pa_adam_state is 32 bytes");
+static bool adam_state_ok(const char* who, const void* state) {
+    if (state && !(reinterpret_cast<uintptr_t>(state) & 15)) return true;
+    pa_set_error_msg((std::string(who) + (state ? ": state must be 16-byte aligned" : ": state is NULL (a pa_adam_state on the device)")).c_str());
+    return false;
+}
+int pa_adam_step(const pa_adam_opts* o, float* p, const float* g, float* m, float* v, float* vmax, size_t n, float gscale,
+                 const float* clip_coef, pa_adam_state* state, void* s) {
+    g_err[0] = 0;
+    if (!o || !p || !g || !m || !v) { pa_set_error_msg("pa_adam_step: opts, param, grad, exp_avg or exp_avg_sq is NULL"); return 1; }
+    if (!adam_state_ok("pa_adam_step", state)) return 1;
+    if ((o->amsgrad != 0) != (vmax != nullptr)) { pa_set_error_msg("pa_adam_step: max_exp_avg_sq is required when amsgrad and must be NULL otherwise"); return 1; }
+    if (!(o->beta1 >= 0.f && o->beta1 < 1.f) || !(o->beta2 >= 0.f && o->beta2 < 1.f)) { pa_set_error_msg("pa_adam_step: beta1 and beta2 must be in [0, 1)"); return 1; }
+    if (!(o->eps > 0.f)) { pa_set_error_msg("pa_adam_step: eps must be > 0"); return 1; }
+    if (!(o->weight_decay >= 0.f)) { pa_set_error_msg("pa_adam_step: weight_decay must be >= 0"); return 1; }
+    const PaAdamOpts k = {o->lr, o->beta1, o->beta2, o->eps, o->weight_decay, (float)(1.0 - (double)o->lr * (double)o->weight_decay),
+                          1.f - o->beta1, 1.f - o->beta2};
+    const int decay = o->weight_decay != 0.f ? (o->decoupled ? 2 : 1) : 0;
+    TRY(pa_launch_adam(k, o->amsgrad != 0, decay, p, g, m, v, vmax, n, gscale, clip_coef, reinterpret_cast<PaAdamState*>(state), ST(s))); return 0;
+}
+int pa_adam_steps(const pa_adam_state* state, long long* steps, long long* skipped, void* s) {
+    g_err[0] = 0;
+    if (!adam_state_ok("pa_adam_steps", state)) return 1;
+    TRY(pa_adam_read_steps(reinterpret_cast<const PaAdamState*>(state), steps, skipped, ST(s))); return 0;
+}
+int pa_adam_set_steps(pa_adam_state* state, long long steps, void* s) {
+    g_err[0] = 0;
+    if (!adam_state_ok("pa_adam_set_steps", state)) return 1;
+    if (steps < 0 || steps > 2147483647LL) { pa_set_error_msg("pa_adam_set_steps: steps must be in 0 .. 2^31 - 1"); return 1; }
+    TRY(pa_launch_adam_set_steps(reinterpret_cast<PaAdamState*>(state), (int)steps, ST(s))); return 0;
+}
 int pa_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, void* s) {
     TRY(pa_launch_nchw_f32_to_nhwc_bf16(src, reinterpret_cast<bf16*>(dst), B, C, H, W, ST(s))); return 0;
 }

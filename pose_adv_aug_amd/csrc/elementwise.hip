@@ -1048,6 +1048,124 @@ int pa_launch_rmsprop_opts(const PaRmspropOpts& o, bool centered, float* p, cons
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// torch.optim.Adam / AdamW with AMSGrad (torch 2.10 _single_tensor_adam, non-capturable branch), in the shape of the kernels above.
+// Per element, every operation in fp32 and in this order:
+//   gr  = (g * gscale) * coef            coef as above; no multiply without a clip pointer
+//   DECAY 1 (coupled):    gr = gr + wd * p          DECAY 2 (decoupled):  p = p * c_dec,  c_dec = (float)(1.0 - (double)lr * (double)wd)
+//   m'  = m + (gr - m) * (1.f - beta1)              (torch's lerp_ with a weight < 0.5)
+//   v'  = beta2 * v + ((1.f - beta2) * gr) * gr
+//   vmax' = fmaxf(vmax, v')                         AMSGRAD; vhat = AMSGRAD ? vmax' : v'
+//   den = sqrtf(vhat) / bc2s + eps ;  p' = p - step_size * (m' / den)
+// DECAY 0 computes neither decay (a "+ 0 * p" would turn -0 into +0, see rmsprop_opts_update); AMSGRAD off loads and stores no vmax.
+// bc1 = (float)(1.0 - pow((double)beta1, (double)t)), bc2 likewise, bc2s = sqrtf(bc2), step_size = lr / bc1, t = steps TAKEN including
+// this one: t lives in the optimizer's device state (PaAdamState), because the half-precision build decides on the device whether the
+// step is taken.  adam_prologue_kernel (one thread) advances it and writes the constants, or counts a skipped step; the step kernel
+// reads flag, bc2s and step_size, uniform over the grid, and returns at once when the flag is set.
+// The alignment padding of a flat array (p = g = m = v = vmax = 0) stays exactly 0: every term is 0, den = eps > 0, the decoupled
+// decay multiplies 0.
+__global__ void adam_prologue_kernel(PaAdamState* s, float lr, float beta1, float beta2) {
+    if (s->flag) { s->skipped += 1; return; }
+    const int t = s->step + 1;
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+    const float bc2 = (float)(1.0 - pow((double)beta2, (double)t));
+    s->step = t;
+    s->bc1 = bc1;
+    s->bc2 = bc2;
+    s->step_size = lr / bc1;
+    s->bc2s = sqrtf(bc2);
+}
+
+__global__ void adam_set_steps_kernel(PaAdamState* s, int steps) { s->step = steps; }
+
+template <bool AMSGRAD, int DECAY>
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float& vmax, const PaAdamOpts& o, float gscale,
+                                            bool clip, float coef, float bc2s, float step_size) {
+    float gr = g * gscale;
+    if (clip) gr = gr * coef;
+    if (DECAY == 1) gr = gr + o.wd * p;
+    if (DECAY == 2) p = p * o.c_dec;
+    m = m + (gr - m) * o.om_b1;
+    v = o.beta2 * v + (o.om_b2 * gr) * gr;
+    float vhat = v;
+    if (AMSGRAD) { vmax = fmaxf(vmax, v); vhat = vmax; }
+    const float den = sqrtf(vhat) / bc2s + o.eps;
+    p = p - step_size * (m / den);
+}
+
+template <bool AMSGRAD, int DECAY>
+__global__ void adam_kernel(float* p, const float* g, float* m, float* v, float* vmax, size_t n, PaAdamOpts o, float gscale,
+                            const float* clip_coef, const PaAdamState* state) {
+    if (state->flag) return;                // uniform over the grid: every thread reads the same word (the prologue has counted the skip)
+    const float bc2s = state->bc2s, step_size = state->step_size;
+    const bool clip = clip_coef != nullptr;
+    const float coef = clip ? clip_coef[0] : 1.f;
+    size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) {
+        f32x4 gg = *reinterpret_cast<const f32x4*>(g + i), mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i),
+              pp = *reinterpret_cast<f32x4*>(p + i);
+        f32x4 xx = {0.f, 0.f, 0.f, 0.f};
+        if (AMSGRAD) xx = *reinterpret_cast<f32x4*>(vmax + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pj = pp[j], mj = mm[j], vj = vv[j], xj = xx[j];
+            adam_update<AMSGRAD, DECAY>(pj, gg[j], mj, vj, xj, o, gscale, clip, coef, bc2s, step_size);
+            pp[j] = pj; mm[j] = mj; vv[j] = vj; xx[j] = xj;
+        }
+        *reinterpret_cast<f32x4*>(m + i) = mm;
+        *reinterpret_cast<f32x4*>(v + i) = vv;
+        *reinterpret_cast<f32x4*>(p + i) = pp;
+        if (AMSGRAD) *reinterpret_cast<f32x4*>(vmax + i) = xx;
+    }
+    for (; i < n && i + 3 >= n; ++i) {          // tail (at most 3 elements, one thread)
+        float pj = p[i], mj = m[i], vj = v[i], xj = AMSGRAD ? vmax[i] : 0.f;
+        adam_update<AMSGRAD, DECAY>(pj, g[i], mj, vj, xj, o, gscale, clip, coef, bc2s, step_size);
+        p[i] = pj; m[i] = mj; v[i] = vj;
+        if (AMSGRAD) vmax[i] = xj;
+    }
+}
+
+template <bool AMSGRAD>
+static void adam_launch_decay(int decay, dim3 grid, dim3 block, hipStream_t st, float* p, const float* g, float* m, float* v, float* vmax,
+                              size_t n, const PaAdamOpts& o, float gscale, const float* clip_coef, const PaAdamState* state) {
+    if (decay == 1) hipLaunchKernelGGL((adam_kernel<AMSGRAD, 1>), grid, block, 0, st, p, g, m, v, vmax, n, o, gscale, clip_coef, state);
+    else if (decay == 2) hipLaunchKernelGGL((adam_kernel<AMSGRAD, 2>), grid, block, 0, st, p, g, m, v, vmax, n, o, gscale, clip_coef, state);
+    else hipLaunchKernelGGL((adam_kernel<AMSGRAD, 0>), grid, block, 0, st, p, g, m, v, vmax, n, o, gscale, clip_coef, state);
+}
+
+// vmax is used iff amsgrad (the C ABI checks that the pointer matches).  bf16 build: prologue -> step (the flag is never set);
+// half-precision build: the reset + grad_check_kernel scan of the RMSprop steps in front, on the state's first two words.
+int pa_launch_adam(const PaAdamOpts& o, bool amsgrad, int decay, float* p, const float* g, float* m, float* v, float* vmax, size_t n,
+                   float gscale, const float* clip_coef, PaAdamState* state, hipStream_t st) {
+    if (n == 0) return 0;
+    const int blocks = pa_grid_for(n / 4, 256, 2048);
+#ifdef PA_FP16
+    hipLaunchKernelGGL(grad_check_reset_kernel, dim3(1), dim3(1), 0, st, &state->flag);
+    hipLaunchKernelGGL(grad_check_kernel, dim3(blocks), dim3(256), 0, st, g, n, &state->flag);
+#endif
+    hipLaunchKernelGGL(adam_prologue_kernel, dim3(1), dim3(1), 0, st, state, o.lr, o.beta1, o.beta2);
+    const dim3 grid(blocks), block(256);
+    if (amsgrad) adam_launch_decay<true>(decay, grid, block, st, p, g, m, v, vmax, n, o, gscale, clip_coef, state);
+    else adam_launch_decay<false>(decay, grid, block, st, p, g, m, v, vmax, n, o, gscale, clip_coef, state);
+    return (int)hipGetLastError();
+}
+
+int pa_adam_read_steps(const PaAdamState* state, long long* steps, long long* skipped, hipStream_t st) {
+    PaAdamState h;
+    hipError_t e = hipMemcpyAsync(&h, state, sizeof h, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    if (steps) *steps = h.step;
+    if (skipped) *skipped = h.skipped;
+    return 0;
+}
+
+int pa_launch_adam_set_steps(PaAdamState* state, int steps, hipStream_t st) {
+    hipLaunchKernelGGL(adam_set_steps_kernel, dim3(1), dim3(1), 0, st, state, steps);
+    return (int)hipGetLastError();
+}
+
 // Norm of gscale * g and the clip coefficient, in two launches, without floating-point atomics: the same inputs give the same bits.
 //   1. grad_sqsum_kernel: every workgroup of the capped grid sums ((double)g[i] * (double)gscale)^2 over its grid-stride share in
 //      double (the product of two fp32 values is exact in double) and writes ONE partial;

@@ -137,6 +137,15 @@ int pa_launch_rmsprop_opts(const PaRmspropOpts& o, bool centered, float* p, cons
 // out2 = {norm of gscale * g, fminf(1, max_norm / (norm + 1e-6f))}: two deterministic launches, double partial sums in workspace
 size_t pa_grad_norm_workspace_size(size_t n);
 int pa_launch_grad_norm(const float* g, size_t n, float gscale, float max_norm, void* workspace, float* out2, hipStream_t st);
+// torch.optim.Adam / AdamW step (elementwise.hip).  decay: 0 none, 1 coupled (gr += wd p), 2 decoupled (p *= c_dec); om_b1 / om_b2 =
+// 1.f - beta in fp32.  PaAdamState is pa_adam_state of include/poseadv.h: a one-thread prologue advances step and writes the four
+// constants (or counts a skipped step when flag is set), the step kernel reads flag, bc2s and step_size from it.
+struct PaAdamOpts { float lr, beta1, beta2, eps, wd, c_dec, om_b1, om_b2; };
+struct PaAdamState { int flag, skipped, step, reserved; float bc1, bc2, step_size, bc2s; };
+int pa_launch_adam(const PaAdamOpts& o, bool amsgrad, int decay, float* p, const float* g, float* m, float* v, float* vmax, size_t n,
+                   float gscale, const float* clip_coef, PaAdamState* state, hipStream_t st);
+int pa_adam_read_steps(const PaAdamState* state, long long* steps, long long* skipped, hipStream_t st);
+int pa_launch_adam_set_steps(PaAdamState* state, int steps, hipStream_t st);
 int pa_launch_loss_out(float* acc, float* keep, float* out, float* total, int n, hipStream_t st);      // per-stack losses + their sum out, accumulators cleared
 int pa_launch_copy16(void* dst, const void* src, size_t bytes, hipStream_t st, int form = 0);      // plain 16-B/lane streaming copy (bandwidth calibration)
 int pa_rmsprop_skipped(const int* state, long long* out, hipStream_t st);     // half-precision build: steps skipped for a non-finite gradient

@@ -152,7 +152,7 @@ def main(argv=None):
     from .stack_hg import broadcast_parameters, init_distributed, make_feeds, validate
     from .utils.checkpoint import Checkpoint
     from .utils.logger import Logger
-    from .utils.optim import RMSprop, optim_options
+    from .utils.optim import make_optimizer
     from .utils.util import ASNTrainHistory, PoseTrainHistory, adjust_lr
     from .utils.visualizer import Visualizer
     opt = TrainOptions().parse(argv)
@@ -174,7 +174,7 @@ def main(argv=None):
     log = (lambda m: (print(m), vis.write_log(m))) if rank == 0 else (lambda m: None)
 
     hg = create_hg(num_stacks=2, num_modules=opt.num_modules, num_classes=16, chan=256, default_batch=opt.bs)          # :61-62
-    optimizer_hg = RMSprop(hg, lr=opt.lr, alpha=0.99, eps=1e-8, **optim_options(opt))
+    optimizer_hg = make_optimizer(opt, hg, opt.lr)
     train_history_pose, checkpoint_hg = PoseTrainHistory(), Checkpoint()
     if opt.load_checkpoint:                                                                   # resume the joint stage (:72-74)
         checkpoint_hg.load_prefix = joint_dir + '/' + opt.load_prefix_pose[0:-1]
@@ -190,7 +190,7 @@ def main(argv=None):
 
     agent_sr = create_asn(chan_in=256, chan_out=256, scale_num=len(SCALE_MEANS), rotation_num=len(ROT_MEANS), is_aug=True,
                           default_batch=opt.bs)                                               # :87-90
-    optimizer_sr = RMSprop(agent_sr, lr=opt.agent_lr, alpha=0.99, eps=1e-8, **optim_options(opt))
+    optimizer_sr = make_optimizer(opt, agent_sr, opt.agent_lr)
     train_history_sr, checkpoint_sr = ASNTrainHistory(), Checkpoint()
     if opt.load_checkpoint:                                                                   # :99-101
         checkpoint_sr.load_prefix = joint_dir + '/' + opt.load_prefix_sr[0:-1]

@@ -14,6 +14,14 @@ class TrainOptions(BaseOptions):
         p.add_argument('--weight_decay', type=float, default=0., help='RMSprop weight decay (0: off)')
         p.add_argument('--centered', type=int, default=0, help='1: centered RMSprop (0: off)')
         p.add_argument('--clip_grad_norm', type=float, default=0., help='clip the gradient to this 2-norm before the step (0: off)')
+        # the optimizer itself (utils/optim.py make_optimizer; rmsprop: the reference's).  adam / adamw: torch.optim.Adam's formula,
+        # --weight_decay coupled (adam) or decoupled (adamw) and passed as given, --clip_grad_norm as above; --momentum and --centered
+        # are RMSprop's and refused with them
+        p.add_argument('--optimizer', type=str, default='rmsprop', choices=('rmsprop', 'adam', 'adamw'), help='optimizer of the pose net and the agent')
+        p.add_argument('--beta1', type=float, default=0.9, help='Adam / AdamW: decay of the first moment')
+        p.add_argument('--beta2', type=float, default=0.999, help='Adam / AdamW: decay of the second moment')
+        p.add_argument('--adam_eps', type=float, default=1e-8, help='Adam / AdamW: eps added to the denominator')
+        p.add_argument('--amsgrad', type=int, default=0, help='1: Adam / AdamW with AMSGrad (0: off)')
         p.add_argument('--bs', type=int, default=12, help='mini-batch size')
         p.add_argument('--load_checkpoint', type=_bool, default=False, help='resume from checkpoint model')
         p.add_argument('--load_checkpoint_pose', type=_bool, default=False, help='use checkpoint model')
@@ -33,3 +41,11 @@ class TrainOptions(BaseOptions):
         p.add_argument('--display_freq', type=int, default=10, help='display figures every n iterations')
         p.add_argument('--pose_gpu_id', type=int, default=0, help='gpu ids')
         p.add_argument('--asn_gpu_id', type=int, default=1, help='gpu ids')
+
+    def parse(self, args=None):
+        if not self.initialized:
+            self.initialize()
+        o = self.parser.parse_args(args)
+        if o.optimizer != 'rmsprop' and (o.momentum != 0 or o.centered):
+            self.parser.error('--momentum and --centered are RMSprop options: not with --optimizer %s' % o.optimizer)
+        return BaseOptions.parse(self, args)

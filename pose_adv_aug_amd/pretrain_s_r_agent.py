@@ -139,7 +139,7 @@ def main(argv=None):
     from .options.train_options import TrainOptions
     from .stack_hg import make_feeds
     from .utils.checkpoint import Checkpoint
-    from .utils.optim import RMSprop, optim_options
+    from .utils.optim import make_optimizer
     from .utils.logger import Logger
     from .utils.util import ASNTrainHistory
     from .models.asn_stacked_hg import create_hg, create_asn
@@ -153,7 +153,7 @@ def main(argv=None):
         ck.load_checkpoint(hg)
     agent = create_asn(chan_in=256, chan_out=256, scale_num=len(SCALE_MEANS), rotation_num=len(ROT_MEANS), is_aug=True,
                        default_batch=opt.bs)
-    optimizer = RMSprop(agent, lr=opt.lr, alpha=0.99, eps=1e-8, **optim_options(opt))                              # :93-94 (opt.lr, not agent_lr)
+    optimizer = make_optimizer(opt, agent, opt.lr)                              # :93-94 (opt.lr, not agent_lr)
     history, ckpt = ASNTrainHistory(), Checkpoint()
     if opt.load_prefix_sr != '':                                                              # resume (:64-70)
         ckpt.load_prefix = sr_dir + '/' + opt.load_prefix_sr[0:-1]

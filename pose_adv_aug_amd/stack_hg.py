@@ -12,7 +12,7 @@ import torch.distributed as dist
 
 from .data import AugmentAhead, Augmenter, BatchFeed, DeviceBatch, num_samples, with_next
 from .models.asn_stacked_hg import create_hg
-from .utils.optim import RMSprop, optim_options
+from .utils.optim import make_optimizer
 from .utils.util import AverageMeter, DeviceMeters, PoseTrainHistory, adjust_lr
 
 PCK_IDX = [0, 1, 2, 3, 4, 5, 10, 11, 14, 15]            # stack-hg.py:89
@@ -202,7 +202,7 @@ def main(argv=None):
     opt = TrainOptions().parse(argv)
     rank, world, _ = init_distributed()
     net = create_hg(num_stacks=2, num_modules=opt.num_modules, num_classes=16, chan=256, default_batch=opt.bs)     # stack-hg.py:40-41
-    optimizer = RMSprop(net, lr=opt.lr, alpha=0.99, eps=1e-8, **optim_options(opt))
+    optimizer = make_optimizer(opt, net, opt.lr)
     history, ckpt = PoseTrainHistory(), Checkpoint()
     exp_dir = os.path.join(opt.exp_dir, opt.exp_id)
     if opt.load_prefix_pose != '':

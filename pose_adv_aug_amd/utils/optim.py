@@ -1,11 +1,13 @@
-"""RMSprop on the engine's flat parameter buffer (reference: torch.optim.RMSprop(net.parameters(),
-lr, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0), stack-hg.py:51-52) with the data-parallel
-gradient exchange folded in: ONE all-reduce of the flat gradient over RCCL per step (replaces
-nn.DataParallel's broadcast/gather/reduce_add, stack-hg.py:49).
+"""Optimizers on the engine's flat parameter buffer, with the data-parallel gradient exchange folded in: ONE all-reduce of the flat
+gradient over RCCL per step (replaces nn.DataParallel's broadcast/gather/reduce_add, stack-hg.py:49).
 
+RMSprop (reference: torch.optim.RMSprop(net.parameters(), lr, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0), stack-hg.py:51-52).
 Beyond the reference's recipe: torch.optim.RMSprop's momentum, weight_decay and centered, and the gradient-norm clipping of
 torch.nn.utils.clip_grad_norm_ (max_grad_norm), all inside the engine's own launches (pa_rmsprop_step_opts, pa_grad_norm).  With
-every one of them off, step() is the one pa_rmsprop_step_state call it has always been."""
+every one of them off, step() is the one pa_rmsprop_step_state call it has always been.
+
+Adam / AdamW (torch.optim.Adam's formula with weight decay coupled or decoupled, AMSGrad, the same clipping): one fused step
+(pa_adam_step) whose step count and bias-correction constants live on the device.  make_optimizer picks one from the command line."""
 import ctypes as C
 import os
 
@@ -30,18 +32,11 @@ def optim_options(opt):
                 centered=bool(getattr(opt, 'centered', 0)), max_grad_norm=clip if clip > 0 else None)
 
 
-class RMSprop(object):
-    def __init__(self, net, lr=2.5e-4, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0, centered=False, max_grad_norm=None, overlap=False):
-        """momentum, weight_decay, centered: torch.optim.RMSprop's (torch 2.10 _single_tensor_rmsprop), except that the centered
-        variance max(0, square_avg - grad_avg^2) is clamped where torch returns NaN for a difference that rounding made negative.
-        They live in param_groups[0] and are read at every step, like lr.  max_grad_norm (None = off): the gradient is multiplied by
-        min(1, max_grad_norm / (norm + 1e-6)) as by torch.nn.utils.clip_grad_norm_; the norm is computed on the device and the step
-        reads the coefficient there (no host synchronisation); last_grad_norm() is the device float for logging.
-        overlap (pose net, world > 1 only): exchange the gradients of a stack's hourglass (one contiguous 42 % of a 2-stack
-        net) on a communication stream as soon as that stack's backward pass is enqueued, while the earlier stacks and the stem
-        still run; the rest follows at the end.  Same sums, same result as the single all-reduce (off by default)."""
-        if momentum < 0 or weight_decay < 0:
-            raise ValueError('momentum and weight_decay must be >= 0')
+class _FlatOptimizer(object):
+    """What every optimizer on the engine's flat arrays does around its own step launch: the gradient exchange (one all-reduce, or the
+    overlapped per-stack buckets), gscale, the gradient norm and clip coefficient on the device, and the refresh of the 16-bit weight
+    copies after the step."""
+    def _attach(self, net, max_grad_norm, overlap):
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError('max_grad_norm must be > 0 (None: no clipping)')
         self.net = net
@@ -49,17 +44,9 @@ class RMSprop(object):
         if overlap and hasattr(net, 'num_stacks'):
             net.on_stack_done = self._exchange_stack
         net._ensure_table()
-        self.param_groups = [{'lr': lr, 'alpha': alpha, 'eps': eps, 'momentum': momentum, 'weight_decay': weight_decay, 'centered': bool(centered)}]
         self.max_grad_norm = max_grad_norm
-        self.square_avg = torch.zeros_like(net.flat_params)
-        # flat like square_avg, allocated when their option is on (_ensure_state); the norm's scratch and its {norm, coefficient} output
-        self.momentum_buffer = self.grad_avg = self._norm_ws = self._norm_out = None
+        self._norm_ws = self._norm_out = None           # the norm's scratch and its {norm, coefficient} output
         self._clipped = False
-        self._ensure_state(self.param_groups[0])
-        # fp16 build: {this gradient is non-finite, steps skipped so far} of THIS optimizer (the pose net's and the agent's step on
-        # different streams in the joint stage; a process-wide flag would let one see the other's overflow)
-        self._skip_state = torch.zeros(2, dtype=torch.int32, device=net.flat_params.device)
-        self.steps = 0
 
     def zero_grad(self):
         self.net.zero_grad()
@@ -107,6 +94,61 @@ class RMSprop(object):
         self._works = []
         return 1.0 / dist.get_world_size()
 
+    def _exchanged_gscale(self):
+        """finish the gradient exchange; 1/world, and the fp16 build's gradient scale divided out"""
+        world_scale = self._finish_exchange() if self._works else self.allreduce_grads()
+        return world_scale / _lib.grad_scale()
+
+    def _clip_coef(self, n, gscale):
+        """norm and clip coefficient of the exchanged gradient (max_grad_norm): the pointer of the device float the step reads, or None"""
+        if self.max_grad_norm is None:
+            return None
+        grads = self.net.flat_grads
+        if self._norm_out is None:
+            self._norm_ws = torch.empty(int(lib().pa_grad_norm_workspace_bytes(n)) // 8, dtype=torch.float64, device=grads.device)
+            self._norm_out = torch.zeros(2, dtype=torch.float32, device=grads.device)
+        check(lib().pa_grad_norm(ptr(grads), n, float(gscale), float(self.max_grad_norm), ptr(self._norm_ws), ptr(self._norm_out), stream()),
+              'pa_grad_norm')
+        self._clipped = True
+        return ptr(self._norm_out[1:])
+
+    def _weights_stepped(self):
+        self.net.weights_changed()
+        self.net._net(self.net._last_B or self.net.default_batch)      # refresh the bf16 weight copies now
+
+    def last_grad_norm(self):
+        """The norm of the (averaged, unscaled) gradient of the last step taken with max_grad_norm, before clipping: a 0-dim tensor on
+        the device, so reading it is the caller's synchronisation (at print time); None before the first such step."""
+        return self._norm_out[0] if self._clipped else None
+
+    def _params(self):
+        """(name, shape, offset, numel, kind) of the parameters, in parameters() order"""
+        return [t for t in self.net._table if t[4] == 0]
+
+
+class RMSprop(_FlatOptimizer):
+    def __init__(self, net, lr=2.5e-4, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0, centered=False, max_grad_norm=None, overlap=False):
+        """momentum, weight_decay, centered: torch.optim.RMSprop's (torch 2.10 _single_tensor_rmsprop), except that the centered
+        variance max(0, square_avg - grad_avg^2) is clamped where torch returns NaN for a difference that rounding made negative.
+        They live in param_groups[0] and are read at every step, like lr.  max_grad_norm (None = off): the gradient is multiplied by
+        min(1, max_grad_norm / (norm + 1e-6)) as by torch.nn.utils.clip_grad_norm_; the norm is computed on the device and the step
+        reads the coefficient there (no host synchronisation); last_grad_norm() is the device float for logging.
+        overlap (pose net, world > 1 only): exchange the gradients of a stack's hourglass (one contiguous 42 % of a 2-stack
+        net) on a communication stream as soon as that stack's backward pass is enqueued, while the earlier stacks and the stem
+        still run; the rest follows at the end.  Same sums, same result as the single all-reduce (off by default)."""
+        if momentum < 0 or weight_decay < 0:
+            raise ValueError('momentum and weight_decay must be >= 0')
+        self._attach(net, max_grad_norm, overlap)
+        self.param_groups = [{'lr': lr, 'alpha': alpha, 'eps': eps, 'momentum': momentum, 'weight_decay': weight_decay, 'centered': bool(centered)}]
+        self.square_avg = torch.zeros_like(net.flat_params)
+        # flat like square_avg, allocated when their option is on (_ensure_state)
+        self.momentum_buffer = self.grad_avg = None
+        self._ensure_state(self.param_groups[0])
+        # fp16 build: {this gradient is non-finite, steps skipped so far} of THIS optimizer (the pose net's and the agent's step on
+        # different streams in the joint stage; a process-wide flag would let one see the other's overflow)
+        self._skip_state = torch.zeros(2, dtype=torch.int32, device=net.flat_params.device)
+        self.steps = 0
+
     def _ensure_state(self, g):
         """momentum_buffer / grad_avg of the options that are on in the param group g (zeros, as torch creates them at the first step)"""
         if g.get('momentum', 0) > 0 and self.momentum_buffer is None:
@@ -116,8 +158,7 @@ class RMSprop(object):
 
     def step(self):
         g = self.param_groups[0]
-        world_scale = self._finish_exchange() if self._works else self.allreduce_grads()
-        gscale = world_scale / _lib.grad_scale()                    # 1/world, and the fp16 build's gradient scale divided out
+        gscale = self._exchanged_gscale()
         n = self.net.flat_params.numel()
         mom, wd, centered = float(g.get('momentum', 0)), float(g.get('weight_decay', 0)), bool(g.get('centered', False))
         if mom == 0 and wd == 0 and not centered and self.max_grad_norm is None:          # the reference's recipe: one launch, as ever
@@ -127,30 +168,16 @@ class RMSprop(object):
         else:
             self._step_opts(g, mom, wd, centered, n, gscale)
         self.steps += 1
-        self.net.weights_changed()
-        self.net._net(self.net._last_B or self.net.default_batch)      # refresh the bf16 weight copies now
+        self._weights_stepped()
 
     def _step_opts(self, g, mom, wd, centered, n, gscale):
         """norm and clip coefficient of the exchanged gradient (max_grad_norm), then the step that reads the coefficient on the device"""
         self._ensure_state(g)
-        grads, coef = self.net.flat_grads, None
-        if self.max_grad_norm is not None:
-            if self._norm_out is None:
-                self._norm_ws = torch.empty(int(lib().pa_grad_norm_workspace_bytes(n)) // 8, dtype=torch.float64, device=grads.device)
-                self._norm_out = torch.zeros(2, dtype=torch.float32, device=grads.device)
-            check(lib().pa_grad_norm(ptr(grads), n, float(gscale), float(self.max_grad_norm), ptr(self._norm_ws), ptr(self._norm_out), stream()),
-                  'pa_grad_norm')
-            coef = ptr(self._norm_out[1:])
-            self._clipped = True
+        grads, coef = self.net.flat_grads, self._clip_coef(n, gscale)
         o = _lib.RmspropOpts(float(g['lr']), float(g['alpha']), float(g['eps']), mom, wd, int(centered))
         check(lib().pa_rmsprop_step_opts(C.byref(o), ptr(self.net.flat_params), ptr(grads), ptr(self.square_avg),
                                          ptr(self.momentum_buffer) if mom > 0 else None, ptr(self.grad_avg) if centered else None,
                                          n, float(gscale), coef, ptr(self._skip_state), stream()), 'pa_rmsprop_step_opts')
-
-    def last_grad_norm(self):
-        """The norm of the (averaged, unscaled) gradient of the last step taken with max_grad_norm, before clipping: a 0-dim tensor on
-        the device, so reading it is the caller's synchronisation (at print time); None before the first such step."""
-        return self._norm_out[0] if self._clipped else None
 
     def skipped_steps(self):
         """fp16 build: optimizer steps the engine skipped because the (scaled) gradient held inf / NaN; 0 in the bf16 build"""
@@ -181,7 +208,7 @@ class RMSprop(object):
         grad_avg are read when the file's param group (else this optimizer's) has the option on; a file without them (written with
         the option off) leaves them zero, with a warning."""
         import warnings
-        params = [t for t in self.net._table if t[4] == 0]
+        params = self._params()
         group = dict(self.param_groups[0])
         group.update((k, v) for k, v in sd['param_groups'][0].items() if k != 'params')
         extra = self._option_state(group)
@@ -219,3 +246,164 @@ class RMSprop(object):
         for k, v in sd['param_groups'][0].items():
             if k != 'params':
                 self.param_groups[0][k] = v
+
+
+_ADAM_KEYS = ('lr', 'betas', 'eps', 'weight_decay', 'amsgrad', 'decoupled_weight_decay')
+
+
+class Adam(_FlatOptimizer):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, decoupled_weight_decay=False,
+                 max_grad_norm=None, overlap=False):
+        """torch.optim.Adam (torch 2.10 _single_tensor_adam) as one fused step on the flat arrays (pa_adam_step): weight_decay coupled
+        (added to the gradient) or, with decoupled_weight_decay, AdamW's p *= 1 - lr weight_decay; amsgrad keeps the running maximum
+        of exp_avg_sq (max_exp_avg_sq, allocated when amsgrad is first on).  All of them live in param_groups[0] and are read at every
+        step, like lr.  max_grad_norm and overlap: as for RMSprop.
+        The step count of the bias correction lives on the device (self._state, a pa_adam_state): the fp16 build decides there whether
+        a step is taken, and a skipped step must not advance it.  steps_taken() and state_dict() read it, which synchronises."""
+        b1, b2 = betas
+        if not (0 <= b1 < 1 and 0 <= b2 < 1):
+            raise ValueError('betas must be in [0, 1)')
+        if not eps > 0 or weight_decay < 0:
+            raise ValueError('eps must be > 0 and weight_decay >= 0')
+        self._attach(net, max_grad_norm, overlap)
+        self.param_groups = [{'lr': lr, 'betas': (b1, b2), 'eps': eps, 'weight_decay': weight_decay, 'amsgrad': bool(amsgrad),
+                              'decoupled_weight_decay': bool(decoupled_weight_decay)}]
+        self.exp_avg = torch.zeros_like(net.flat_params)
+        self.exp_avg_sq = torch.zeros_like(net.flat_params)
+        self.max_exp_avg_sq = None
+        self._ensure_state(self.param_groups[0])
+        # pa_adam_state: {flag, skipped, step, reserved} int32 and {bc1, bc2, step_size, bc2s} float32 of THIS optimizer
+        self._state = torch.zeros(8, dtype=torch.int32, device=net.flat_params.device)
+
+    def _ensure_state(self, g):
+        if g.get('amsgrad', False) and self.max_exp_avg_sq is None:
+            self.max_exp_avg_sq = torch.zeros_like(self.net.flat_params)
+
+    def step(self):
+        g = self.param_groups[0]
+        gscale = self._exchanged_gscale()
+        n = self.net.flat_params.numel()
+        amsgrad = bool(g.get('amsgrad', False))
+        self._ensure_state(g)
+        coef = self._clip_coef(n, gscale)
+        b1, b2 = g['betas']
+        o = _lib.AdamOpts(float(g['lr']), float(b1), float(b2), float(g['eps']), float(g.get('weight_decay', 0)), int(amsgrad),
+                          int(bool(g.get('decoupled_weight_decay', False))))
+        check(lib().pa_adam_step(C.byref(o), ptr(self.net.flat_params), ptr(self.net.flat_grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                                 ptr(self.max_exp_avg_sq) if amsgrad else None, n, float(gscale), coef, ptr(self._state), stream()),
+              'pa_adam_step')
+        self._weights_stepped()
+
+    def _counts(self):
+        steps, skipped = C.c_longlong(0), C.c_longlong(0)
+        check(lib().pa_adam_steps(ptr(self._state), C.byref(steps), C.byref(skipped), stream()), 'pa_adam_steps')
+        return int(steps.value), int(skipped.value)
+
+    def steps_taken(self):
+        """optimizer steps applied so far (skipped ones not counted), read from the device: synchronises the stream"""
+        return self._counts()[0]
+
+    def skipped_steps(self):
+        """fp16 build: optimizer steps the engine skipped because the (scaled) gradient held inf / NaN; 0 in the bf16 build"""
+        return self._counts()[1]
+
+    def _moments(self, g):
+        self._ensure_state(g)
+        return [('exp_avg', self.exp_avg), ('exp_avg_sq', self.exp_avg_sq)] + ([('max_exp_avg_sq', self.max_exp_avg_sq)] if g.get('amsgrad', False) else [])
+
+    # torch.optim.Adam's format: per-parameter state keyed by index, in parameters() order; `step` a 0-dim float32 CPU tensor
+    def state_dict(self):
+        steps = self.steps_taken()
+        state = {}
+        for i, (name, shape, off, numel, kind) in enumerate(self._params()):
+            state[i] = {'step': torch.tensor(float(steps), dtype=torch.float32)}
+            for key, flat in self._moments(self.param_groups[0]):
+                state[i][key] = flat[off:off + numel].view(shape).clone()
+        pg = dict(self.param_groups[0])
+        pg['betas'] = tuple(pg['betas'])
+        pg['params'] = list(range(len(state)))
+        return {'state': state, 'param_groups': [pg]}
+
+    def load_state_dict(self, sd):
+        """Accepts this class's own files and torch.optim.Adam's / AdamW's: `state` is keyed by the entries of param_groups[0]['params']
+        (positions or arbitrary ids), in parameters() order.  The moments are replaced: an entry that is missing or has another size is
+        reported and left at zero.  `step` goes back to the device (pa_adam_set_steps).  The file of another optimizer (RMSprop's:
+        square_avg and no exp_avg) loads with ONE warning that says so and leaves this optimizer's options, zero moments and step 0."""
+        import warnings
+        params = self._params()
+        state = sd.get('state', {})
+        file_group = sd['param_groups'][0]
+        entries = [st for st in state.values() if isinstance(st, dict)]
+        if entries and not any('exp_avg' in st for st in entries):
+            other = sorted(set(k for st in entries for k in st) - set(['step']))
+            warnings.warn('optimizer state holds %s and no exp_avg: not an Adam file (another optimizer wrote it); the moments start at '
+                          'zero, step 0, and this optimizer keeps its own options' % (', '.join(other) or 'no moments'))
+            for _, flat in self._moments(self.param_groups[0]):
+                flat.zero_()
+            self._set_steps(0)
+            return
+        group = dict(self.param_groups[0])
+        group.update((k, v) for k, v in file_group.items() if k in _ADAM_KEYS)
+        group['betas'] = tuple(group['betas'])
+        moments = self._moments(group)
+        for _, flat in moments:
+            flat.zero_()
+        loaded = dict((key, 0) for key, _ in moments)
+        keys = list(file_group.get('params', range(len(params))))
+        if len(keys) != len(params):
+            warnings.warn('optimizer state has %d parameters, the network %d: the moments are not loaded' % (len(keys), len(params)))
+            keys = []
+        steps = set()
+        for key, (name, shape, off, numel, kind) in zip(keys, params):
+            st = state.get(key)
+            if st is None:
+                continue
+            for mkey, flat in moments:
+                e = st.get(mkey)
+                if e is None:
+                    continue
+                e = torch.as_tensor(e)
+                if e.numel() != numel:
+                    warnings.warn('optimizer state of %s: %s has %d elements, expected %d: skipped' % (name, mkey, e.numel(), numel))
+                    continue
+                flat[off:off + numel] = e.reshape(-1).to(flat.device, torch.float32)
+                loaded[mkey] += 1
+            if 'step' in st:
+                steps.add(int(float(st['step'])))
+        if state and keys:
+            for mkey, _ in moments:
+                if loaded[mkey] < len(params):
+                    warnings.warn('optimizer state: %d of %d parameters had no %s entry (left at zero)' % (len(params) - loaded[mkey], len(params), mkey))
+        if len(steps) > 1:
+            warnings.warn('optimizer state: the parameters have different step counts %s; the largest is used' % sorted(steps))
+        self._set_steps(max(steps) if steps else 0)
+        self.param_groups[0].update(group)
+
+    def _set_steps(self, steps):
+        check(lib().pa_adam_set_steps(ptr(self._state), int(steps), stream()), 'pa_adam_set_steps')
+
+
+class AdamW(Adam):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, max_grad_norm=None, overlap=False):
+        """torch.optim.AdamW: Adam with decoupled weight decay and torch's default weight_decay"""
+        Adam.__init__(self, net, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, decoupled_weight_decay=True,
+                      max_grad_norm=max_grad_norm, overlap=overlap)
+
+
+def make_optimizer(opt, net, lr, overlap=False):
+    """The optimizer the command line asks for (options/train_options.py: --optimizer rmsprop | adam | adamw).  rmsprop, the default:
+    the reference's recipe (alpha 0.99, eps 1e-8) with optim_options(opt).  adam / adamw: --beta1 --beta2 --adam_eps --amsgrad;
+    --weight_decay (coupled for adam, decoupled for adamw; passed as given, so 0 means none for adamw too) and --clip_grad_norm are
+    shared between the kinds."""
+    kind = getattr(opt, 'optimizer', 'rmsprop')
+    if kind == 'rmsprop':
+        return RMSprop(net, lr=lr, alpha=0.99, eps=1e-8, overlap=overlap, **optim_options(opt))
+    if kind not in ('adam', 'adamw'):
+        raise ValueError('unknown optimizer %r' % (kind,))
+    if float(getattr(opt, 'momentum', 0) or 0) != 0 or getattr(opt, 'centered', 0):
+        raise ValueError('--momentum and --centered are RMSprop options: not with --optimizer %s' % kind)
+    clip = float(getattr(opt, 'clip_grad_norm', 0) or 0)
+    kw = dict(lr=lr, betas=(float(getattr(opt, 'beta1', 0.9)), float(getattr(opt, 'beta2', 0.999))), eps=float(getattr(opt, 'adam_eps', 1e-8)),
+              weight_decay=float(getattr(opt, 'weight_decay', 0) or 0), amsgrad=bool(getattr(opt, 'amsgrad', 0)),
+              max_grad_norm=clip if clip > 0 else None, overlap=overlap)
+    return (AdamW if kind == 'adamw' else Adam)(net, **kw)
