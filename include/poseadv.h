@@ -294,6 +294,13 @@ size_t pa_conv2d_workspace_bytes(int B, int Cin, int Cout, int H, int W, int k);
 int pa_conv2d(int mode, const float* a_in, const float* b_in, const float* w, const float* bias, float* out, float* out2,
               int B, int Cin, int Cout, int H, int W, int k, void* ws, void* stream);
 
+/* The data gradient of the 7x7 stride-2 pad-3 stem convolution, operator level like pa_conv2d: dy [B][64][H/2][W/2], w [64][3][7][7] fp32
+ * (both rounded once to the storage type), dx fp32 and 16-byte aligned, fully overwritten: layout 0 [B][3][H][W], 1 [B][H][W][4] (4th
+ * float 0).  The plain transposed convolution: no gradient scale in either build.  H, W even and >= 2; ws: pa_stem_dgrad_workspace_bytes()
+ * bytes (0: bad shape), 16-byte aligned.  Enqueued on `stream`, no synchronisation. */
+size_t pa_stem_dgrad_workspace_bytes(int B, int H, int W);
+int pa_stem_dgrad(const float* dy, const float* w, float* dx, int B, int H, int W, int layout, void* ws, void* stream);
+
 /* Several INDEPENDENT weight gradients the way the training step submits them (the conv1 / conv2 / conv3 / adapter gradients of one
  * _Residual, models/asn_stacked_hg.py:17-24, wait for one event and leave as ONE grouped launch): jobs[j] describes layer j
  * (device pointers, NCHW fp32 operands, PyTorch-layout fp32 outputs).
@@ -409,6 +416,17 @@ int pa_hg_set_loss_total(pa_net* net, float* total_dev);
  * Errors (nothing changes): an agent, a layout other than 0 / 1, every entry NULL, a pointer that is not 16-byte aligned; and
  * pa_hg_train_step(use_graph != 0) is refused while gradients are set. */
 int pa_hg_set_heat_grads(pa_net* net, const float* const* grads_host, int layout);
+
+/* d loss / d image of the next backward passes.  dimg: caller-owned device fp32, 16-byte aligned; layout 0: [B][3][res][res]
+ * (the shape of `img`), 1: [B][res][res][4] (img4's pixel order, 4th float 0); NULL = off (default).  Sticky like
+ * pa_hg_set_heat_grads.  While set, pa_hg_backward / the LAST pa_hg_backward_phase also write the gradient with respect to
+ * the image the last forward pass read (img, or img4 as stored), UNSCALED (the half-precision build divides pa_grad_scale() out; a
+ * gradient that overflowed there stays inf / NaN), fully overwritten, ordered on the net's stream when the call returns.  Works with
+ * the built-in MSE gradient and with pa_hg_set_heat_grads, with dropout masks, in train and eval mode.  One more launch behind the
+ * stem's weight gradient (the data gradient of the 7x7 stride-2 convolution); with dimg == NULL the step is launch for launch what it
+ * is without this call.  Errors (nothing changes): an agent, layout not 0 / 1, a misaligned pointer; pa_hg_train_step(use_graph != 0)
+ * is refused while set. */
+int pa_hg_set_image_grad(pa_net* net, float* dimg, int layout);
 
 /* Half-hourglass forward (models/asn_stacked_hg.py:300-304 with is_half_hg): stem + the down path of
  * hg[0] up to the neck -- everything the agent reads.  train != 0 updates the BatchNorm running

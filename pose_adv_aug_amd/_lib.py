@@ -149,6 +149,9 @@ _PROTOS = {
     'pa_hg_train_step': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     'pa_hg_set_loss_total': (_i, [_vp, _vp]),
     'pa_hg_set_heat_grads': (_i, [_vp, C.POINTER(_vp), _i]),
+    'pa_hg_set_image_grad': (_i, [_vp, _vp, _i]),
+    'pa_stem_dgrad_workspace_bytes': (_sz, [_i, _i, _i]),
+    'pa_stem_dgrad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'pa_hg_accuracy': (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     'pa_hg_forward_half': (_i, [_vp, _vp, _vp, _i]),
     'pa_asn_forward': (_i, [_vp, _vp, _i, _vp, _vp]),

@@ -617,6 +617,45 @@ int pa_hg_set_heat_grads(pa_net* net, const float* const* grads_host, int layout
     return 0;
 }
 
+int pa_hg_set_image_grad(pa_net* net, float* dimg, int layout) {
+    g_err[0] = 0;
+    Net& n = net->n;
+    if (n.is_agent) { pa_set_error_msg("pa_hg_set_image_grad: not a pose net"); return 1; }
+    if (!dimg) { n.image_grad = nullptr; n.image_grad_layout = 0; return 0; }
+    if (layout != 0 && layout != 1) { pa_set_error_msg("pa_hg_set_image_grad: layout must be 0 ([B][3][res][res]) or 1 ([B][res][res][4])"); return 1; }
+    if (reinterpret_cast<uintptr_t>(dimg) & 15) { pa_set_error_msg("pa_hg_set_image_grad: the gradient must be 16-byte aligned"); return 1; }
+    n.image_grad = dimg; n.image_grad_layout = layout;
+    return 0;
+}
+
+// The stem's data gradient as an operator (tests/test_gpu_image_grad.py): dy and w are rounded once to the storage type, the result is the plain
+// transposed convolution (no gradient scale).  Workspace: dy as NHWC 16-bit + the packed weight copy.
+static size_t stem_dgrad_ws(int B, int H, int W, size_t* wf_off) {
+    const size_t g = ((size_t)B * (H / 2) * (W / 2) * 64 * sizeof(bf16) + 255) & ~(size_t)255;
+    if (wf_off) *wf_off = g;
+    return g + 64 * 256 * sizeof(bf16);
+}
+size_t pa_stem_dgrad_workspace_bytes(int B, int H, int W) {
+    if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return 0;
+    return stem_dgrad_ws(B, H, W, nullptr);
+}
+int pa_stem_dgrad(const float* dy, const float* w, float* dx, int B, int H, int W, int layout, void* ws, void* s) {
+    g_err[0] = 0;
+    if (!dy || !w || !dx || !ws) { pa_set_error_msg("pa_stem_dgrad: dy, w, dx and ws must not be NULL"); return 1; }
+    if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) { pa_set_error_msg("pa_stem_dgrad: B >= 1, H and W even and >= 2"); return 1; }
+    if (layout != 0 && layout != 1) { pa_set_error_msg("pa_stem_dgrad: layout must be 0 ([B][3][H][W]) or 1 ([B][H][W][4])"); return 1; }
+    if ((reinterpret_cast<uintptr_t>(dx) & 15) || (reinterpret_cast<uintptr_t>(ws) & 15)) { pa_set_error_msg("pa_stem_dgrad: dx and ws must be 16-byte aligned"); return 1; }
+    size_t wf_off = 0; stem_dgrad_ws(B, H, W, &wf_off);
+    bf16* g16 = reinterpret_cast<bf16*>(ws);
+    bf16* wf = reinterpret_cast<bf16*>(reinterpret_cast<char*>(ws) + wf_off);
+    TRY(pa_launch_nchw_f32_to_nhwc_bf16(dy, g16, B, 64, H / 2, W / 2, ST(s)));
+    TRY(pa_launch_stem_pack(w, wf, ST(s)));
+    PaStemDgradArgs d; memset(&d, 0, sizeof d);
+    d.g = pa_plain(g16); d.wf = wf; d.out = dx; d.B = B; d.Hm = H / 2; d.Wm = W / 2; d.layout = layout; d.scale = 1.f;
+    TRY(pa_launch_stem_dgrad(d, ST(s)));
+    return 0;
+}
+
 int pa_weighted_l2_grad(const float* pred, const float* gt, const float* weight, size_t n, const float* gout_dev, float* dpred, void* s) {
     g_err[0] = 0;
     if (!pred || !gt || !gout_dev || !dpred) { pa_set_error_msg("pa_weighted_l2_grad: pred, gt, gout_dev and dpred must not be NULL"); return 1; }
@@ -745,6 +784,7 @@ int pa_hg_train_step(pa_net* net, const void* img4, const double* pts, int train
     Net& n = net->n;
     if (!img4 || !pts) { pa_set_error_msg("pa_hg_train_step: img4 and pts are required"); return 1; }
     // (a captured graph holds the pointers of its capture: the same rule as for dropout masks, refused before anything is enqueued)
+    if (use_graph && n.image_grad) { pa_set_error_msg("pa_hg_train_step: no captured graph while an image gradient is set (pa_hg_set_image_grad)"); return 1; }
     if (use_graph && n.heat_grads_on) { pa_set_error_msg("pa_hg_train_step: no captured graph while heat-map gradients are set (pa_hg_set_heat_grads)"); return 1; }
     if (!use_graph) {
         TRY(n.forward_pose(nullptr, reinterpret_cast<const bf16*>(img4), pts, train != 0, loss_per_stack));

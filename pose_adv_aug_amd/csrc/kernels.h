@@ -127,6 +127,17 @@ int pa_launch_stem_wgrad(const PaWgradArgs& a, hipStream_t st);
 // reduce the stem's partial slabs [splits][64][256] into PyTorch layout dst[64][3][7][7]
 int pa_launch_stem_wgrad_reduce(const float* part, int splits, float* dst, hipStream_t st, float* zero64 = nullptr);      // zero64: 64 floats the launch also clears (the stem's bias gradient)
 
+// data gradient of the stem (stem_dgrad.hip): d loss / d image from the gradient at the RAW stem output
+struct PaStemDgradArgs {
+    PaOperand g;         // [B][Hm][Wm][64] (PLAIN or LIN2: the BatchNorm backward on load, rounded once to the storage type)
+    const bf16* wf;      // the stem's packed forward copy [64][256]: wf[n][ky*32 + kx*4 + c]
+    float* out;          // fp32, 16-byte aligned, fully overwritten; layout 0: [B][3][2Hm][2Wm], 1: [B][2Hm][2Wm][4] (4th float 0)
+    int B, Hm, Wm, layout;
+    float scale;         // the fp32 result is multiplied by this (1 / PA_GRAD_SCALE in the net: a power of two, exact)
+};
+int pa_launch_stem_dgrad(const PaStemDgradArgs& a, hipStream_t st);
+int pa_launch_stem_pack(const float* w, bf16* wf, hipStream_t st);      // fp32 [64][3][7][7] -> wf as above
+
 // ---- optimizer / weight preparation
 int pa_launch_rmsprop(float* p, const float* g, float* v, size_t n, float lr, float alpha, float eps, float gscale, int* state, hipStream_t st);   // state: the optimizer's own {flag, skipped} device pair or NULL (process-wide pair)
 // the step with torch.optim.RMSprop's other options (momentum buffer iff mom > 0, grad_avg iff centered) and an optional clip coefficient

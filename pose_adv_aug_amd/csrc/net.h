@@ -259,6 +259,10 @@ struct Net {
     std::vector<const float*> heat_grads;
     int heat_grads_layout = 0;                  // 0: [B][16][H][W], 1: [B][H*W][16]
     bool heat_grads_on = false;
+    // d loss / d image wanted by the caller (pa_hg_set_image_grad): while set, backward_stem() also runs the stem's data gradient
+    // (stem_dgrad.hip) into this caller-owned fp32 buffer, unscaled; nullptr = off, and the step is launch for launch what it is without
+    float* image_grad = nullptr;
+    int image_grad_layout = 0;                  // 0: [B][3][res][res], 1: [B][res][res][4]
 
     // ---- declaration helpers
     size_t add_param(const std::string& name, std::initializer_list<int> shape);

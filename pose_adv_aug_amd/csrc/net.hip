@@ -1079,6 +1079,14 @@ int Net::backward_stem() {
     res1.g3_pool_on = false;
     TRY(finish_grad(a0));
     TRY(conv_wgrad(stem_conv, gradop(a0), pa_plain(cur_image), B, res / 2, res / 2));
+    if (image_grad) {       // d loss / d image (pa_hg_set_image_grad): the same operand through the transposed 7x7/2 taps, untimed, on the main stream
+        PaStemDgradArgs d; memset(&d, 0, sizeof d);
+        d.g = gradop(a0); d.wf = stem_conv.wf; d.out = image_grad; d.B = B; d.Hm = res / 2; d.Wm = res / 2; d.layout = image_grad_layout;
+        d.scale = 1.f / PA_GRAD_SCALE;
+        const double e = (double)B * d.Hm * d.Wm * 64;
+        cnt(opb(d.g, e) + 2.0 * 64 * 256, 4.0 * B * res * res * (image_grad_layout ? 4 : 3));
+        TRY(pa_launch_stem_dgrad(d, st));
+    }
     TRY(reduce_grads());
     return join_meters();               // the step's meters ran beside this pass: later readers on the main stream come behind them
 }

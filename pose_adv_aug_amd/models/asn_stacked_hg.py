@@ -198,6 +198,8 @@ class _HeatMapsFunction(torch.autograd.Function):
     def forward(ctx, anchor, net, x, img4, pts, dropout_masks):
         outs = net._forward(x, img4, pts, dropout_masks)
         ctx.net, ctx.serial, ctx.done = net, net._fwd_serial, False
+        # which input carries the image: its gradient (HourglassNet.backward(input_grad=...)) is returned when autograd asks for it
+        ctx.img4_dtype = img4.dtype if img4 is not None else None      # (the engine reads img4 when it is given)
         ctx.set_materialize_grads(False)                # a stack the loss does not use arrives as None = zero, not as a tensor of zeros
         return tuple(outs)
 
@@ -210,6 +212,11 @@ class _HeatMapsFunction(torch.autograd.Function):
             raise RuntimeError('forward_autograd: another forward pass of this net has run since these heat maps were made; '
                                'its stored activations are gone')
         ctx.done = True
+        want_x, want_img4 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if want_x and ctx.img4_dtype is None:
+            return (None, None, net.backward(grads, input_grad='nchw'), None, None, None)
+        if want_img4 and ctx.img4_dtype is not None:
+            return (None, None, None, net.backward(grads, input_grad='nhwc4').to(ctx.img4_dtype), None, None)
         net.backward(grads)
         return (None,) * 6
 
@@ -304,7 +311,30 @@ class HourglassNet(_HipModule):
     use_graph = False        # loss_and_backward(img4=...) replays a captured HIP graph of forward + backward (pa_hg_train_step)
     on_stack_done = None     # callback(stack index) after the backward pass of a stack is enqueued (utils.optim.RMSprop(overlap=True))
 
-    def loss_and_backward(self, x=None, pts=None, img4=None, want_outputs=False, dropout_masks=None, after_forward=None):
+    last_input_grad = None   # loss_and_backward(input_grad=...): d loss / d image of that step (a new tensor per step), else None
+
+    @staticmethod
+    def _input_grad_layout(input_grad):
+        """input_grad of backward() / loss_and_backward() -> None (off), 0 ('nchw' or True: [B][3][res][res]) or 1 ('nhwc4': [B][res][res][4])"""
+        if input_grad is False or input_grad is None:
+            return None
+        if input_grad is True or input_grad == 'nchw':
+            return 0
+        if input_grad == 'nhwc4':
+            return 1
+        raise ValueError("input_grad must be False, True, 'nchw' or 'nhwc4', got %r" % (input_grad,))
+
+    def _open_image_grad(self, h, B, lay):
+        """pa_hg_set_image_grad with a new fp32 tensor in layout `lay` (None: nothing happens); returns the tensor"""
+        if lay is None:
+            return None
+        shape = (B, 3, self.res, self.res) if lay == 0 else (B, self.res, self.res, 4)
+        g = torch.empty(shape, dtype=torch.float32, device=self.flat_params.device)       # (the engine overwrites every element)
+        check(lib().pa_hg_set_image_grad(h, ptr(g), lay), 'pa_hg_set_image_grad')
+        return g
+
+    def loss_and_backward(self, x=None, pts=None, img4=None, want_outputs=False, dropout_masks=None, after_forward=None,
+                          input_grad=False):
         """One pass of stack-hg.py:153-164 without the optimizer: forward in the current mode, loss
         sum_stacks mean((out - gaussian(pts))^2) with the target generated on the fly from `pts`
         ([B][16][2] heat-map coordinates), backward into flat_grads.  Returns (loss 0-d GPU tensor, outputs).
@@ -315,7 +345,10 @@ class HourglassNet(_HipModule):
         after_forward: a callable run between the two passes; its accuracy() / pckh_origin_res() calls (stack-hg.py:176-178 read
         nothing but the forward pass's heat maps) go to the engine's meter stream and run BESIDE the backward pass instead of between
         two steps (pa_net_meters_async); their results are ordered behind this call like everything else.  The value it returns is
-        kept in self.after_forward_result.  (Not with use_graph: there the two passes are one launch.)"""
+        kept in self.after_forward_result.  (Not with use_graph: there the two passes are one launch.)
+        input_grad (False / True or 'nchw' / 'nhwc4', as in backward()): the step also leaves d loss / d image in self.last_input_grad
+        (unscaled fp32; None without it); with use_graph such a call takes the eager path, as one with dropout_masks does."""
+        lay = self._input_grad_layout(input_grad)                  # (ValueError before anything is launched)
         B = x.shape[0] if x is not None else img4.shape[0]
         h = self._net(B)
         self._last_B = B
@@ -324,7 +357,8 @@ class HourglassNet(_HipModule):
         p = pts.to(torch.float64).contiguous()
         losses = torch.empty(self.num_stacks, dtype=torch.float32, device=self.flat_params.device)      # the engine copies every entry
         self._last_losses = losses                                  # per-stack values of this step (the returned loss is their sum)
-        if self.use_graph and x is None and dropout_masks is None:
+        self.last_input_grad = None
+        if self.use_graph and x is None and dropout_masks is None and lay is None:
             check(lib().pa_hg_train_step(h, ptr(img4), ptr(p), 1 if self.training else 0, 1, ptr(losses)), 'pa_hg_train_step')
             if self.training:
                 self._nbt += 1
@@ -348,11 +382,14 @@ class HourglassNet(_HipModule):
                     self.after_forward_result = after_forward()
                 finally:
                     check(lib().pa_net_meters_async(h, 0), 'pa_net_meters_async')
+            self.last_input_grad = self._open_image_grad(h, B, lay)
             self._run_backward(h)
             self._meter_keep = None                            # (the backward pass has enqueued the join: later users of these blocks are ordered behind the meters)
             outs = self.heatmaps(B) if want_outputs else None
         finally:
             lib().pa_hg_set_loss_total(h, None)
+            if lay is not None:
+                lib().pa_hg_set_image_grad(h, None, 0)
             if keep is not None:
                 self._set_masks(h, None)
             if getattr(self, '_meter_keep', None) is not None:
@@ -371,13 +408,18 @@ class HourglassNet(_HipModule):
         else:
             check(lib().pa_hg_backward(h), 'pa_hg_backward')
 
-    def backward(self, grad_outputs, layout='nchw'):
+    def backward(self, grad_outputs, layout='nchw', input_grad=False):
         """The hand-written backward pass of the LAST forward pass from the caller's d loss / d heat maps (pa_hg_set_heat_grads) instead
         of the built-in MSE gradient: any loss of the heat maps trains the net.  grad_outputs: a sequence of num_stacks fp32 GPU tensors
         [B][16][res/4][res/4] ('nchw', the shape forward() returns) or [B][res/4][res/4][16] ('nhwc'); None = zero for that stack.
         UNSCALED gradients (the engine applies _lib.grad_scale()); the parameter gradients land in flat_grads like loss_and_backward's,
         in phases with on_stack_done when an overlapping optimizer is attached.  A wrong count, shape, dtype or device raises ValueError
-        before anything is launched."""
+        before anything is launched.
+        input_grad: True or 'nchw' also returns d loss / d image as a new fp32 tensor [B][3][res][res] (the shape of `x`), 'nhwc4' as
+        [B][res][res][4] (img4's pixel order, 4th float 0): the gradient with respect to the image the forward pass read (x, or img4 as
+        stored), unscaled -- one more launch, the data gradient of the 7x7 stride-2 stem.  False (default): None, no launch added.  Any
+        other value raises ValueError."""
+        lay = self._input_grad_layout(input_grad)
         require_gpu()
         if layout not in ('nchw', 'nhwc'):
             raise ValueError("layout must be 'nchw' or 'nhwc', got %r" % (layout,))
@@ -404,20 +446,27 @@ class HourglassNet(_HipModule):
                 raise ValueError('backward: gradients must be 16-byte aligned')
         ptrs = (C.c_void_p * self.num_stacks)(*[None if g is None else g.data_ptr() for g in keep])
         check(lib().pa_hg_set_heat_grads(h, ptrs, 0 if layout == 'nchw' else 1), 'pa_hg_set_heat_grads')
+        dimg = None
         try:
             masks = self._set_masks(h, self._last_masks)        # the occlusion masks of that forward pass: the backward pass goes through them
+            dimg = self._open_image_grad(h, B, lay)
             self._run_backward(h)
         finally:
             lib().pa_hg_set_heat_grads(h, None, 0)
+            if lay is not None:
+                lib().pa_hg_set_image_grad(h, None, 0)
             if self._last_masks is not None:
                 self._set_masks(h, None)
         del keep, masks
+        return dimg
 
     def forward_autograd(self, x=None, img4=None, pts=None, dropout_masks=None):
         """forward() whose per-stack heat maps carry a grad_fn: `loss = my_loss(outs); loss.backward(); optimizer.step()`.
         Returns a tuple of num_stacks tensors [B][16][res/4][res/4].  loss.backward() calls self.backward() once with the gradients autograd
-        delivers; the parameter gradients land in flat_grads (the project's convention: the parameter views carry no .grad), nothing flows
-        to the input image.  The engine keeps ONE forward pass's activations: backward a second time through the same outputs, or after
+        delivers; the parameter gradients land in flat_grads (the project's convention: the parameter views carry no .grad).  An input
+        that requires grad gets its gradient like any autograd input: x.grad [B][3][res][res], or img4.grad (the NHWC4 gradient cast to
+        img4's dtype, 4th channel 0) -- FGSM / PGD, a learnable occluder or a generator in front of the net; without requires_grad no
+        launch is added.  The engine keeps ONE forward pass's activations: backward a second time through the same outputs, or after
         another forward pass of this net, raises RuntimeError.  pts is optional (accuracy() and _last_losses, as in forward());
         dropout_masks as in forward(): the backward pass differentiates through the same masks."""
         self._ensure_table()

@@ -59,7 +59,8 @@ def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, crit
     data: the batch's augmented input if it was prepared ahead (data.AugmentAhead), else it is made here.
     criterion: a callable (outs, data) -> 0-d loss tensor over the per-stack heat maps of net.forward_autograd (your own loss, e.g.
     pylib.Criterion.weighted_L2 with per-joint weights): forward, criterion, loss.backward(), optimizer.step().  None (the default,
-    what every shipped loop passes): the built-in fused MSE step."""
+    what every shipped loop passes): the built-in fused MSE step.  A data['img4'] that requires grad gets its .grad from that backward
+    pass (forward_autograd: d loss / d image, NHWC4)."""
     if data is None:
         data = augmenter.regular(batch)
     def meters():
