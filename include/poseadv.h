@@ -102,6 +102,35 @@ int pa_affine_warp_bilinear_sized(const uint8_t* src, int Hs, int Ws, const int3
 int pa_transform_pts_sized(const float* pts, const double* params, const double* t, int B, int J, const int32_t* sizes,
                            double* out, float* pts_img, void* stream);
 
+/* The backward pass of the bilinear sampler above: from dimg = d loss / d (its fp32 output) to the six coefficients of tinv, the colour
+ * gains and the augmentation parameters.  With sx = ti0 u + ti1 v + ti2, sy = ti3 u + ti4 v + ti5, (ax, ay) their fractions,
+ * S_c = sum of the 2 x 2 taps w_k p_k,c / 255 (as the forward read them: 0 outside the sample's frame, mirrored when flip), per pixel:
+ *   m_c = 1 iff 0 <= gain_c S_c <= 1 (torch.clamp's rule on the double pre-clamp value; bounds included, so a pixel outside the frame
+ *   passes and contributes exact zeros);  dS_c/dsx = (1 - ay)(p01 - p00) + ay (p11 - p10),  dS_c/dsy = (1 - ax)(p10 - p00) + ax (p11 - p01)
+ *   (floor has derivative 0: at an integer sx this is the derivative of the cell the forward sampled, the right-hand one);
+ *   gx = sum_c dimg_c m_c gain_c dS_c/dsx, gy likewise;  dtinv = sum over pixels {gx u, gx v, gx, gy u, gy v, gy};  dgain_c = sum dimg_c m_c S_c.
+ * The float cast of the output and the rounding of out4 to the storage type are not differentiated.  dparams [B][8] = d loss /
+ * d {cx, cy, scale, rot (per degree), flip (always 0), gain r, g, b} by the chain rule through pa_affine_params: it assumes that tinv
+ * came from pa_affine_params(params, res_in = res); a caller with a tinv of its own takes dtinv.  cx is the centre after the mirror, as
+ * everywhere in params.
+ * dimg: fp32 on the device, 16-byte aligned, the two layouts pa_hg_set_image_grad writes: 0 [B][3][res][res], 1 [B][res][res][4] (the 4th
+ * float is ignored); unscaled in both builds.  sizes: as for pa_affine_warp_bilinear_sized, or NULL (every frame fills [Hs][Ws]).
+ * workspace: pa_affine_warp_bwd_workspace_bytes(B, res) bytes on the device (0: bad shape; host only, no device call), 8-byte aligned.
+ * dtinv [B][6], dgain [B][3], dparams [B][8]: float64 on the device, each may be NULL but not all three; fully overwritten.
+ * Everything in double, two launches (partial sums per strip of output rows stored, then added in a fixed order), no atomics: the same
+ * input gives the same bits.  Enqueued on `stream`, no synchronisation.  The same code in both builds.
+ * Errors (non-zero, pa_last_error set, nothing launched): a NULL src / tinv / params / dimg / workspace, all three outputs NULL, a layout
+ * other than 0 or 1, a dimg that is not 16-byte aligned, a workspace that is not 8-byte aligned, B < 1, res < 1, Hs < 1, Ws < 1,
+ * B * ceil(res / 8) above 2^31 - 1. */
+size_t pa_affine_warp_bwd_workspace_bytes(int B, int res);
+int pa_affine_warp_bilinear_bwd(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const double* tinv, const double* params,
+                                int B, int res, const float* dimg, int layout, void* workspace, double* dtinv, double* dgain,
+                                double* dparams, void* stream);
+/* The chain rule alone, on the host (no device call): params_host [B][8], dtinv_host [B][6], dgain_host [B][3] or NULL (zeros) ->
+ * dparams_host [B][8], with tinv = pa_affine_params(params, res_in).  The code the device's second launch runs. */
+int pa_affine_params_bwd_host(const double* params_host, const double* dtinv_host, const double* dgain_host, int B, int res_in,
+                              double* dparams_host);
+
 /* HumanAug.crop (pylib/HumanAug.py:117-176) behind the dataset's pre-processing (data/mpii_for_mpii.py:114-135,
  * utils/imutils.py:31-40), stage for stage with the arithmetic of the libraries the reference delegates its pixels to
  * (scipy.misc.pilutil over Pillow): source bytes = fp32 frame / 255, mirrored, times gain, clamped; for

@@ -89,6 +89,9 @@ _PROTOS = {
     'pa_transform_pts': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     'pa_affine_warp_bilinear': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'pa_affine_warp_bilinear_sized': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'pa_affine_warp_bwd_workspace_bytes': (_sz, [_i, _i]),
+    'pa_affine_warp_bilinear_bwd': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'pa_affine_params_bwd_host': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     'pa_transform_pts_sized': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'pa_crop_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'pa_crop_design_bytes': (_i, [_i, _i, _i, _i, C.POINTER(C.c_double)]),

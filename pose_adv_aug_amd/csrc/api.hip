@@ -1,6 +1,7 @@
 // extern "C" boundary of libposeadv_hip.so (declared in include/poseadv.h).
 #include "../../include/poseadv.h"
 #include "net.h"
+#include "warp_bwd.h"
 #include <stdio.h>
 #include <string.h>
 #include <new>
@@ -72,6 +73,29 @@ int pa_affine_warp_bilinear_sized(const uint8_t* src, int Hs, int Ws, const int3
                                   int B, int res, void* out4, float* outf, void* s) {
     if (!sizes) { pa_set_error_msg("pa_affine_warp_bilinear_sized: sizes is NULL"); return 1; }
     TRY(pa_launch_warp(src, Hs, Ws, sizes, tinv, params, B, res, reinterpret_cast<bf16*>(out4), outf, ST(s))); return 0;
+}
+// backward of the bilinear sampler (warp_bwd.hip): d loss / d tinv, d gain and, through the chain rule of warp_bwd.h, d params
+size_t pa_affine_warp_bwd_workspace_bytes(int B, int res) { return pa_warp_bwd_workspace_size(B, res); }
+int pa_affine_warp_bilinear_bwd(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const double* tinv, const double* params, int B,
+                                int res, const float* dimg, int layout, void* workspace, double* dtinv, double* dgain, double* dparams, void* s) {
+    g_err[0] = 0;
+    if (!src || !tinv || !params || !dimg || !workspace) { pa_set_error_msg("pa_affine_warp_bilinear_bwd: src, tinv, params, dimg and workspace must not be NULL"); return 1; }
+    if (B < 1 || res < 1 || Hs < 1 || Ws < 1) { pa_set_error_msg("pa_affine_warp_bilinear_bwd: B >= 1, res >= 1 and a frame of at least one pixel"); return 1; }
+    if (pa_warp_bwd_strips(B, res) == 0) { pa_set_error_msg("pa_affine_warp_bilinear_bwd: too many strips (B * ceil(res / 8) must stay below 2^31)"); return 1; }
+    if (layout != 0 && layout != 1) { pa_set_error_msg("pa_affine_warp_bilinear_bwd: layout must be 0 ([B][3][res][res]) or 1 ([B][res][res][4])"); return 1; }
+    if (reinterpret_cast<uintptr_t>(dimg) & 15) { pa_set_error_msg("pa_affine_warp_bilinear_bwd: dimg must be 16-byte aligned"); return 1; }
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) { pa_set_error_msg("pa_affine_warp_bilinear_bwd: workspace must be 8-byte aligned (double partial sums)"); return 1; }
+    if (!dtinv && !dgain && !dparams) { pa_set_error_msg("pa_affine_warp_bilinear_bwd: dtinv, dgain and dparams are all NULL"); return 1; }
+    TRY(pa_launch_warp_bwd(src, Hs, Ws, sizes, tinv, params, B, res, dimg, layout, workspace, dtinv, dgain, dparams, ST(s))); return 0;
+}
+int pa_affine_params_bwd_host(const double* params_host, const double* dtinv_host, const double* dgain_host, int B, int res_in, double* dparams_host) {
+    g_err[0] = 0;
+    if (!params_host || !dtinv_host || !dparams_host) { pa_set_error_msg("pa_affine_params_bwd_host: params, dtinv and dparams must not be NULL"); return 1; }
+    if (B < 1 || res_in < 1) { pa_set_error_msg("pa_affine_params_bwd_host: B >= 1 and res_in >= 1"); return 1; }
+    for (int b = 0; b < B; ++b)
+        pa_affine_params_chain(params_host + (size_t)b * 8, dtinv_host + (size_t)b * 6, dgain_host ? dgain_host + (size_t)b * 3 : nullptr,
+                               (double)res_in, dparams_host + (size_t)b * 8);
+    return 0;
 }
 size_t pa_crop_workspace_bytes(int B, int Hs, int Ws, int res) { return pa_crop_workspace_size(B, Hs, Ws, res); }
 int pa_crop_design_bytes(int B, int Hs, int Ws, int res, double* out) { if (!out) return 1; pa_crop_bytes_bound(B, Hs, Ws, res, out, out + 1); return 0; }

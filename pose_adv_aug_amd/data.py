@@ -150,6 +150,25 @@ class Augmenter(object):
         p[:, 5:8] = 1.0
         return self._finish(batch, want_nchw)
 
+    def bilinear(self, batch, params):
+        """The data dict of _finish for GIVEN parameters (float64 [B][8] on the device, batch.params' layout) with the pixels of the pure
+        bilinear sampler (HumanAug.warp_autograd) instead of the reference's crop: data['img'] (fp32 NCHW) carries a grad_fn when
+        `params` requires grad, so a loss of the net's heat maps reaches params.grad = d loss / d {cx, cy, scale, rot per degree, gain}.
+        data['img4'] is the same launch's storage-type copy (no gradient).  The joint targets are held fixed: 'pts', 'grnd_pts', 'c', 's'
+        and 'r' come from params.detach() -- the Gaussian stamp rounds the joints to pixels and has no useful derivative.  No law is
+        drawn and self.step does not move.  The crop of the other laws (pa_crop) stays non-differentiable."""
+        B = batch.B
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float64 or tuple(params.shape) != (B, 8):
+            raise ValueError('params must be a float64 [%d][8] tensor' % B)
+        pd = params.detach().contiguous()
+        t_out, _ = HumanAug.affine_params(pd, self.inp_res, self.out_res)
+        imgf, img4 = HumanAug.warp_autograd(batch.frames, params, res=self.inp_res, sizes=batch.sizes, want_nhwc4=True)
+        pts_heat, pts_img = HumanAug.transform_pts_batch(batch.joints, pd, t_out, batch.Ws, sizes=batch.sizes)
+        csr = torch.empty(4 * B, dtype=torch.float32, device=pd.device)
+        check(lib().pa_params_csr(ptr(pd), B, ptr(csr), stream()), 'pa_params_csr')
+        return {'img4': img4, 'img': imgf, 'pts': pts_heat, 'grnd_pts': pts_img,
+                'c': csr[:2 * B].view(B, 2), 's': csr[2 * B:3 * B], 'r': csr[3 * B:], 'normalizer': batch.normalizer}
+
 
 class AugmentAhead(object):
     """The reference's DataLoader workers prepare batch i + 1 while batch i trains (stack-hg.py:73-77, num_workers); here the

@@ -123,6 +123,113 @@ def warp_batch(frames, tinv, params, res=256, want_nchw=False, want_nhwc4=True, 
     return out4, outf
 
 
+_WARP_LAYOUTS = {'nchw': 0, 'nhwc4': 1}
+
+
+def _want(t, what, dtype, shape):
+    """ValueError unless t is a contiguous GPU tensor of `dtype` and `shape` (None = any extent)"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError('%s must be a torch tensor' % what)
+    if t.dtype != dtype:
+        raise ValueError('%s must be %s, not %s' % (what, dtype, t.dtype))
+    if t.dim() != len(shape) or any(w is not None and int(s) != int(w) for s, w in zip(t.shape, shape)):
+        raise ValueError('%s must have shape %s, not %s' % (what, list(shape), list(t.shape)))
+    if not t.is_cuda:
+        raise ValueError('%s must be on the GPU' % what)
+    if not t.is_contiguous():
+        raise ValueError('%s must be contiguous' % what)
+
+
+def warp_batch_backward(frames, tinv, params, dimg, layout='nchw', sizes=None):
+    """device: the backward pass of warp_batch (pa_affine_warp_bilinear_bwd).  dimg = d loss / d (its fp32 output): fp32
+    [B][3][res][res] (layout 'nchw') or [B][res][res][4] ('nhwc4', 4th float ignored), the two forms HourglassNet.backward(input_grad=...)
+    delivers.  Returns (dtinv [B][6], dgain [B][3], dparams [B][8]) in float64; dparams = d loss / d {cx, cy, scale, rot per degree,
+    0, gain r g b} assumes tinv = affine_params(params, res_in=res)[1].  A wrong shape, dtype or device raises ValueError before any launch."""
+    if layout not in _WARP_LAYOUTS:
+        raise ValueError("layout must be 'nchw' or 'nhwc4', not %r" % (layout,))
+    _want(frames, 'frames', torch.uint8, (None, None, None, 3))
+    B, Hs, Ws, _ = frames.shape
+    if B < 1 or Hs < 1 or Ws < 1:
+        raise ValueError('frames must hold at least one pixel')
+    _want(tinv, 'tinv', torch.float64, (B, 6))
+    _want(params, 'params', torch.float64, (B, 8))
+    if not isinstance(dimg, torch.Tensor) or dimg.dim() != 4:
+        raise ValueError('dimg must be a 4-d torch tensor')
+    res = int(dimg.shape[2])
+    _want(dimg, 'dimg', torch.float32, (B, 3, res, res) if layout == 'nchw' else (B, res, res, 4))
+    if res < 1:
+        raise ValueError('dimg must hold at least one pixel')
+    if dimg.data_ptr() % 16:
+        raise ValueError('dimg must be 16-byte aligned')
+    if sizes is not None:
+        _want(sizes, 'sizes', torch.int32, (B, 2))
+    if len({t.device for t in (frames, tinv, params, dimg) + ((sizes,) if sizes is not None else ())}) != 1:
+        raise ValueError('frames, tinv, params, dimg and sizes must be on one device')
+    d = frames.device
+    ws = torch.empty(int(lib().pa_affine_warp_bwd_workspace_bytes(B, res)), dtype=torch.uint8, device=d)
+    dtinv = torch.empty((B, 6), dtype=torch.float64, device=d)
+    dgain = torch.empty((B, 3), dtype=torch.float64, device=d)
+    dparams = torch.empty((B, 8), dtype=torch.float64, device=d)
+    check(lib().pa_affine_warp_bilinear_bwd(ptr(frames), Hs, Ws, ptr(sizes), ptr(tinv), ptr(params), B, res, ptr(dimg),
+                                            _WARP_LAYOUTS[layout], ptr(ws), ptr(dtinv), ptr(dgain), ptr(dparams), stream()),
+          'pa_affine_warp_bilinear_bwd')
+    return dtinv, dgain, dparams
+
+
+class _WarpFn(torch.autograd.Function):
+    """pa_affine_params + the bilinear sampler -> (fp32 NCHW, storage-type NHWC4 or None); backward: pa_affine_warp_bilinear_bwd"""
+
+    @staticmethod
+    def forward(ctx, params, frames, res, sizes, want_nhwc4):
+        p = params.detach().contiguous()
+        _, tinv = affine_params(p, res_in=res, res_out=res)
+        out4, outf = warp_batch(frames, tinv, p, res=res, want_nchw=True, want_nhwc4=want_nhwc4, sizes=sizes)
+        ctx.frames, ctx.sizes = frames, sizes
+        ctx.save_for_backward(params, tinv)          # (saved, not just kept: an in-place change of params before backward() is then an error)
+        if out4 is None:
+            return outf, None
+        ctx.mark_non_differentiable(out4)
+        return outf, out4
+
+    @staticmethod
+    def backward(ctx, dimg, _d4=None):
+        if dimg is None:
+            return None, None, None, None, None
+        params, tinv = ctx.saved_tensors
+        g = dimg.to(torch.float32).contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        _, _, dparams = warp_batch_backward(ctx.frames, tinv, params.detach().contiguous(), g, 'nchw', ctx.sizes)
+        return dparams, None, None, None, None
+
+
+def _warp_inputs(frames, params):
+    f = frames if (isinstance(frames, torch.Tensor) and frames.device == dev()) else to_dev(frames, torch.uint8)
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float64 or params.dim() != 2 or params.shape[1] != 8 or \
+            params.shape[0] != f.shape[0] or not params.is_cuda:
+        raise ValueError('params must be a float64 [B][8] tensor on the GPU')
+    return f.contiguous()
+
+
+def warp_autograd(frames, params, res=256, sizes=None, want_nhwc4=False):
+    """device: affine_params + warp_batch as ONE differentiable operator of the augmentation parameters: uint8 frames [B][Hs][Ws][3],
+    params float64 [B][8] -> fp32 NCHW [B][3][res][res] (the sampler's `outf`: the gradient that comes back is fp32, not rounded to the
+    storage type).  With params.requires_grad the result carries a grad_fn and backward() leaves d loss / d {cx, cy, scale, rot per
+    degree, gain} in params.grad (float64 [B][8], flip column 0); changing params in place between the two is an error.  Within a source
+    cell the sampler is smooth; the clamp passes the gradient where 0 <= gain * S <= 1 and floor is taken as locally constant
+    (include/poseadv.h).  The frames get no gradient.  Without params.requires_grad this is warp_batch and nothing else is launched.
+    want_nhwc4: return (fp32 NCHW, the same launch's storage-type NHWC4 copy, which carries no gradient) instead of the one tensor.
+    (crop_batch, the reference's PIL-exact crop, stays non-differentiable.)"""
+    f = _warp_inputs(frames, params)
+    if not (params.requires_grad and torch.is_grad_enabled()):
+        p = params.detach().contiguous()
+        _, tinv = affine_params(p, res_in=res, res_out=res)
+        out4, outf = warp_batch(f, tinv, p, res=res, want_nchw=True, want_nhwc4=bool(want_nhwc4), sizes=sizes)
+    else:
+        outf, out4 = _WarpFn.apply(params, f, int(res), sizes, bool(want_nhwc4))
+    return (outf, out4) if want_nhwc4 else outf
+
+
 def crop(img, center, scale, rot, res, size, stretch=False):
     """Reference signature (pylib/HumanAug.py:117): H x W x 3 image (float [0,1] or uint8) -> res x res x 3 uint8, with the
     reference's pixels (its PIL arithmetic restated on the device).  stretch=False: without scipy's per-image min/max byte
