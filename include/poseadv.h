@@ -224,8 +224,11 @@ int pa_sample_aug(const float* meta, const int32_t* scale_idx, const int32_t* ro
 int pa_sample_aug_given(const float* meta, const int32_t* scale_idx, const int32_t* rot_idx, int mode,
                         const double* draws, int B, double* params, void* stream);
 
-/* softmax + np.random.choice(K, p) of joint-train-pose-s-r-agent.py:252-271.  logits [B][K];
- * probs [B][K] and idx int32 [B] may be NULL. */
+/* softmax + np.random.choice(K, p) of joint-train-pose-s-r-agent.py:252-271.  logits [B][K], B >= 1, 1 <= K <= 64;
+ * probs [B][K] and idx int32 [B] may be NULL.  Row b draws the uniform u of the engine's stream at (seed, step, b, slot),
+ * slot <= 255 (the key holds the slot in 8 bits: a larger one would be a draw of another sample).  The pick is the inverse CDF
+ * as np.random.choice normalises it: the first k whose float64 running sum of the fp32 probs exceeds u * (their float64 sum),
+ * else the last k of positive probability -- never a class of probability 0. */
 int pa_sample_categorical(const float* logits, int B, int K, uint64_t seed, uint64_t step, unsigned slot,
                           float* probs, int32_t* idx, void* stream);
 

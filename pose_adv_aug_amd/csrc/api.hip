@@ -139,18 +139,23 @@ int pa_flip_tta_merge(const float* out, const float* out_flipped, float* merged,
 }
 int pa_sample_aug(const float* meta, const int32_t* scale_idx, const int32_t* rot_idx, int mode, uint64_t seed, uint64_t step,
                   int B, double* params, void* s) {
+    if (B < 1) { pa_set_error_msg("pa_sample_aug: B >= 1"); return 1; }
     if (mode != 0 && ((mode != 3 && !scale_idx) || (mode != 2 && !rot_idx))) { pa_set_error_msg("pa_sample_aug: the agent laws need bin indices"); return 1; }
     TRY(pa_launch_sample_aug(meta, scale_idx, rot_idx, mode, seed, step, nullptr, B, params, ST(s))); return 0;
 }
 int pa_sample_aug_given(const float* meta, const int32_t* scale_idx, const int32_t* rot_idx, int mode, const double* draws,
                         int B, double* params, void* s) {
     if (!draws) { pa_set_error_msg("pa_sample_aug_given: draws is NULL"); return 1; }
+    if (B < 1) { pa_set_error_msg("pa_sample_aug_given: B >= 1"); return 1; }
     if (mode != 0 && ((mode != 3 && !scale_idx) || (mode != 2 && !rot_idx))) { pa_set_error_msg("pa_sample_aug_given: the agent laws need bin indices"); return 1; }
     TRY(pa_launch_sample_aug(meta, scale_idx, rot_idx, mode, 0, 0, draws, B, params, ST(s))); return 0;
 }
 int pa_sample_categorical(const float* logits, int B, int K, uint64_t seed, uint64_t step, unsigned slot, float* probs,
                           int32_t* idx, void* s) {
-    if (K > 64) { pa_set_error_msg("pa_sample_categorical: K <= 64"); return 1; }
+    if (K < 1 || K > 64) { pa_set_error_msg("pa_sample_categorical: 1 <= K <= 64"); return 1; }
+    if (B < 1) { pa_set_error_msg("pa_sample_categorical: B >= 1"); return 1; }
+    // the stream key holds the slot in 8 bits: slot 256 + s of sample b would be slot s of sample b + 1
+    if (slot > 255) { pa_set_error_msg("pa_sample_categorical: slot <= 255"); return 1; }
     TRY(pa_launch_sample_categorical(logits, B, K, seed, step, slot, probs, idx, ST(s))); return 0;
 }
 int pa_sample_dropout_masks(const float* logits, int B, int cells, int dropout_num, uint64_t seed, uint64_t step, const double* uniforms,
@@ -158,6 +163,7 @@ int pa_sample_dropout_masks(const float* logits, int B, int cells, int dropout_n
     if (cells < 1 || cells > 64 || dropout_num < 0 || dropout_num >= cells || !masks) {
         pa_set_error_msg("pa_sample_dropout_masks: need 1 <= cells <= 64, 0 <= dropout_num < cells, masks != NULL"); return 1;
     }
+    if (B < 1) { pa_set_error_msg("pa_sample_dropout_masks: B >= 1"); return 1; }
     TRY(pa_launch_sample_dropout_masks(logits, B, cells, dropout_num, seed, step, uniforms, probs, masks, indexes, ST(s))); return 0;
 }
 int pa_cell_mask(const void* x, const float* masks, void* out, int B, int H, int W, int C, void* s) {

@@ -693,7 +693,10 @@ int pa_launch_warp(const unsigned char* src, int Hs, int Ws, const int* sizes, c
 
 // ------------------------------------------------------------------------------------------------
 // Samplers.  Counter-based (stateless) generator: splitmix64 of (seed, step, sample, slot) -> uniform
-// in (0,1); normals by Box-Muller.  The LAWS are the reference's (data/mpii_for_mpii.py:12-13,119-135;
+// in (0,1]: ((k >> 11) + 0.5) 2^-53 in float64, where the + 0.5 is exact below 2^52 and ties to even above, so the one
+// value k >> 11 == 2^53 - 1 gives exactly 1.0 (probability 2^-53); normals by Box-Muller.  The key is step * 0x100000001B3 +
+// (sample << 8) + slot: slots are 0..255 (slot 256 + s of a sample IS slot s of the next), see DESIGN.md for the slot map.
+// tests/stream_exact.py restates the stream bit for bit.  The LAWS are the reference's (data/mpii_for_mpii.py:12-13,119-135;
 // data/joint_train_s_r_agent.py:15-16,33-36,134-139); the stream is this engine's own (the reference
 // never seeds its RNG).
 __host__ __device__ inline unsigned long long pa_mix64(unsigned long long z) {
@@ -776,16 +779,25 @@ __global__ void sample_categorical_kernel(const float* logits, int B, int K, uns
     for (int k = 1; k < K; ++k) mx = fmaxf(mx, l[k]);
     float sum = 0.f;
     for (int k = 0; k < K; ++k) sum += expf(l[k] - mx);
-    const double u = pa_uniform(seed, step, b, slot);
-    double cdf = 0.0;
-    int pick = K - 1;
-    bool done = false;
+    // np.random.choice normalises the cdf by its last entry: the fp32 probabilities sum to 1 +- ~1e-7, so u is scaled by their
+    // float64 sum, and a u * total that no cdf entry exceeds falls to the last cell of positive probability (the rule of
+    // sample_dropout_masks_kernel below and of oracle/model.py::sample_cells_inverse_cdf)
+    double total = 0.0;
     for (int k = 0; k < K; ++k) {
         const float p = expf(l[k] - mx) / sum;
         if (probs) probs[(size_t)b * K + k] = p;
-        cdf += (double)p;
-        if (!done && u < cdf) { pick = k; done = true; }
+        total += (double)p;
     }
+    const double u = pa_uniform(seed, step, b, slot) * total;
+    double cdf = 0.0;
+    int pick = -1, last = 0;
+    for (int k = 0; k < K; ++k) {
+        const float p = expf(l[k] - mx) / sum;
+        cdf += (double)p;
+        if (p > 0.f) last = k;
+        if (pick < 0 && u < cdf) pick = k;
+    }
+    if (pick < 0) pick = last;
     if (idx) idx[b] = pick;
 }
 
