@@ -34,11 +34,14 @@ float pa_grad_scale(void);
 /* ---------------------------------------------------------------- pose library (pylib/) ---- */
 
 /* HumanPts.pts2heatmap (pylib/HumanPts.py:36-46) + draw_gaussian (:82-116), batched.
- * pts: [B][J][2] float64 (x, y) in heat-map pixels; out: [B][J][H][W] fp32. */
+ * pts: [B][J][2] float64 (x, y) in heat-map pixels; out: [B][J][H][W] fp32, any H, W, J >= 1 (a joint is valid for 0 < x <= W, 0 < y <= H).
+ * Errors (non-zero, pa_last_error set, nothing launched): pts or out NULL; B, J, H or W < 1. */
 int pa_gaussian_heatmap(const double* pts, float* out, int B, int J, int H, int W, void* stream);
 
 /* Criterion.weighted_L2 (pylib/Criterion.py:12-18); weight may be NULL (== 1), which is the inline
- * loss term of stack-hg.py:156-159.  *loss (fp32, device) is ACCUMULATED into: zero it first. */
+ * loss term of stack-hg.py:156-159.  *loss (fp32, device) is ACCUMULATED into: zero it first.  The partial sums of the workgroups are
+ * added with atomics: two runs may differ in the last bits.
+ * Errors (non-zero, pa_last_error set, nothing launched): pred, gt or loss NULL; n == 0. */
 int pa_weighted_l2(const float* pred, const float* gt, const float* weight, size_t n, float* loss, void* stream);
 /* d/dpred of pa_weighted_l2: dpred[e] = 2 * (weight ? weight[e] : 1) * (pred[e] - gt[e]) * (*gout_dev) / n ;
  * gout_dev: ONE device float (the gradient arriving at the loss; no host synchronisation).  dpred is overwritten; it may be pred
@@ -75,7 +78,8 @@ int pa_pck(const float* pred, const float* gt, const float* norm, float boundary
 
 /* HumanAug.GetTransform (pylib/HumanAug.py:10-35) for a batch: params [B][8] float64 =
  * {cx, cy, scale, rot_deg, flip, gain_r, gain_g, gain_b}; t_out [B][6] float64 = forward transform
- * at res_out (first two rows), tinv_in [B][6] = INVERSE transform at res_in (what the warp samples with). */
+ * at res_out (first two rows), tinv_in [B][6] = INVERSE transform at res_in (what the warp samples with).  Both outputs are required.
+ * Errors (non-zero, pa_last_error set, nothing launched): params, t_out or tinv_in NULL; B, res_in or res_out < 1. */
 int pa_affine_params(const double* params, int B, int res_in, int res_out, double* t_out, double* tinv_in, void* stream);
 /* fp32 copies of c, s, r as the metric calls take them (`c = meta['center']`, `s = meta['scale']`, `r = meta['rot']` of the reference's
  * batches, stack-hg.py:140-143): csr [4 B] floats = c [B][2] | s [B] | r [B] from params [B][8]. */
@@ -83,14 +87,21 @@ int pa_params_csr(const double* params, int B, float* csr, void* stream);
 
 /* HumanAug.TransformPts (pylib/HumanAug.py:45-54) + shufflelr (:236-257) + the invalid-joint rule of
  * data/mpii_for_mpii.py:142-146.  pts [B][J][2] fp32 image pixels -> out [B][J][2] float64 heat-map
- * coords (0 for invalid joints); pts_img (optional) = mirrored/swapped image-space joints. */
+ * coords (0 for invalid joints); pts_img (optional) = mirrored/swapped image-space joints.
+ * A sample with flip != 0 has every joint mirrored (x <- width - x, in fp32).  The left / right partners are MPII's: with J == 16 a flipped
+ * sample's joint j is read from its partner (0,5) (1,4) (2,3) (10,15) (11,14) (12,13); with any other J the joints are mirrored but NOT swapped
+ * (there is no partner table for them).  A joint whose mirrored x or whose y is <= 0 gives exactly (0, 0).
+ * Errors (non-zero, pa_last_error set, nothing launched): pts, params, t or out NULL (and sizes, for pa_transform_pts_sized); B or J < 1. */
 int pa_transform_pts(const float* pts, const double* params, const double* t, int B, int J, float width,
                      double* out, float* pts_img, void* stream);
 
 /* The PURE inverse-affine bilinear sampler (2 x 2 taps, no pre-filter): the geometry of HumanAug.crop
  * (pylib/HumanAug.py:117-176) + flip / colour gain of data/mpii_for_mpii.py:126-135 as one gather.  NOT the reference's
  * pixels (those are pa_crop below, which the training / validation paths use); kept as an operator.  src: uint8 [B][Hs][Ws][3]; out4: bf16 [B][res][res][4]
- * (network input layout, 4th channel 0) and/or outf: fp32 [B][3][res][res]; either may be NULL. */
+ * (network input layout, 4th channel +0; channels 0..2 are outf rounded to nearest even) and/or outf: fp32 [B][3][res][res]; either may
+ * be NULL, not both.
+ * Errors (non-zero, pa_last_error set, nothing launched): src, tinv or params NULL (and sizes, for pa_affine_warp_bilinear_sized); out4 and outf
+ * both NULL; Hs, Ws, B or res < 1. */
 int pa_affine_warp_bilinear(const uint8_t* src, int Hs, int Ws, const double* tinv, const double* params,
                             int B, int res, void* out4, float* outf, void* stream);
 /* The same two calls for a batch of frames of DIFFERENT sizes stored top-left aligned in a padded [B][Hs][Ws][3] buffer
@@ -209,7 +220,8 @@ int pa_jpeg_decode(const int16_t* coef, const pa_jpeg_desc* descs, const int64_t
 /* Validation with flip test-time augmentation (stack-hg.py:222-230).
  * pa_flip_lr_nhwc4: mirror the bf16 NHWC4 network input along W (img.numpy()[:, :, :, ::-1], :223).
  * pa_flip_tta_merge: merged = (out + shuffle_channels_for_horizontal_flipping(flip_channels(out_flipped))) / 2
- * (pylib/HumanAug.py:198-210, :179-196, stack-hg.py:228-230) over NCHW fp32 heat maps [B][16][H][W]. */
+ * (pylib/HumanAug.py:198-210, :179-196, stack-hg.py:228-230) over NCHW fp32 heat maps [B][16][H][W].
+ * Errors (non-zero, pa_last_error set, nothing launched): a NULL pointer; B, H or W < 1; for pa_flip_tta_merge J != 16. */
 int pa_flip_lr_nhwc4(const void* src, void* dst, int B, int H, int W, void* stream);
 int pa_flip_tta_merge(const float* out, const float* out_flipped, float* merged, int B, int J, int H, int W, void* stream);
 
@@ -353,7 +365,8 @@ typedef struct pa_wgrad_job {
 size_t pa_wgrad_group_workspace_bytes(const pa_wgrad_job* jobs, int njobs);
 int pa_wgrad_group(const pa_wgrad_job* jobs, int njobs, int mode, void* ws, void* stream);
 
-/* NCHW fp32 <-> NHWC bf16 */
+/* NCHW fp32 <-> NHWC bf16 (fp32 -> storage type: round to nearest even).
+ * Errors (non-zero, pa_last_error set, nothing launched): src or dst NULL; B, C, H or W < 1. */
 int pa_nchw_to_nhwc(const float* src, void* dst_bf16, int B, int C, int H, int W, void* stream);
 int pa_nhwc_to_nchw(const void* src_bf16, float* dst, int B, int C, int H, int W, void* stream);
 

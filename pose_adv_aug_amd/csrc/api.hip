@@ -16,6 +16,9 @@ void pa_set_error_msg(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg
 struct pa_net { Net n; };
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 #define TRY(x) do { int _r = (x); if (_r) { if (!g_err[0]) pa_set_error("kernel launch", (hipError_t)_r, __FILE__, __LINE__); return _r; } } while (0)
+// argument checks of the pose-library operators: decided on the host before any device call, the message names the argument
+#define NEED_PTR(fn, p) do { if (!(p)) { pa_set_error_msg(fn ": " #p " is NULL"); return 1; } } while (0)
+#define NEED_POS(fn, v) do { if ((v) < 1) { pa_set_error_msg(fn ": " #v " must be >= 1"); return 1; } } while (0)
 
 extern "C" {
 
@@ -25,9 +28,15 @@ int pa_dtype(void) { return PA_DTYPE_ID; }
 int pa_version(void) { return 1; }
 
 int pa_gaussian_heatmap(const double* pts, float* out, int B, int J, int H, int W, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_gaussian_heatmap", pts); NEED_PTR("pa_gaussian_heatmap", out);
+    NEED_POS("pa_gaussian_heatmap", B); NEED_POS("pa_gaussian_heatmap", J); NEED_POS("pa_gaussian_heatmap", H); NEED_POS("pa_gaussian_heatmap", W);
     TRY(pa_launch_gaussian_heatmap(pts, out, B, J, H, W, ST(s))); return 0;
 }
 int pa_weighted_l2(const float* pred, const float* gt, const float* weight, size_t n, float* loss, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_weighted_l2", pred); NEED_PTR("pa_weighted_l2", gt); NEED_PTR("pa_weighted_l2", loss);
+    if (n == 0) { pa_set_error_msg("pa_weighted_l2: n must be >= 1"); return 1; }
     TRY(pa_launch_weighted_l2(pred, gt, weight, n, loss, ST(s))); return 0;
 }
 int pa_get_preds(const float* maps, int B, int J, int H, int W, float* preds, float* maxval, void* s) {
@@ -54,24 +63,42 @@ int pa_pck(const float* pred, const float* gt, const float* norm, float boundary
     TRY(pa_launch_pck(pred, gt, norm, boundary, idxs, nidx, thr, vis, B, J, acc, person, dists, ST(s))); return 0;
 }
 int pa_affine_params(const double* params, int B, int res_in, int res_out, double* t_out, double* tinv_in, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_affine_params", params); NEED_PTR("pa_affine_params", t_out); NEED_PTR("pa_affine_params", tinv_in);
+    NEED_POS("pa_affine_params", B); NEED_POS("pa_affine_params", res_in); NEED_POS("pa_affine_params", res_out);
     TRY(pa_launch_affine_params(params, B, res_in, res_out, t_out, tinv_in, ST(s))); return 0;
 }
 int pa_transform_pts(const float* pts, const double* params, const double* t, int B, int J, float width, double* out,
                      float* pts_img, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_transform_pts", pts); NEED_PTR("pa_transform_pts", params); NEED_PTR("pa_transform_pts", t); NEED_PTR("pa_transform_pts", out);
+    NEED_POS("pa_transform_pts", B); NEED_POS("pa_transform_pts", J);
     TRY(pa_launch_transform_pts(pts, params, t, B, J, width, nullptr, out, pts_img, ST(s))); return 0;
 }
 int pa_transform_pts_sized(const float* pts, const double* params, const double* t, int B, int J, const int32_t* sizes, double* out,
                            float* pts_img, void* s) {
-    if (!sizes) { pa_set_error_msg("pa_transform_pts_sized: sizes is NULL"); return 1; }
+    g_err[0] = 0;
+    NEED_PTR("pa_transform_pts_sized", pts); NEED_PTR("pa_transform_pts_sized", params); NEED_PTR("pa_transform_pts_sized", t);
+    NEED_PTR("pa_transform_pts_sized", sizes); NEED_PTR("pa_transform_pts_sized", out);
+    NEED_POS("pa_transform_pts_sized", B); NEED_POS("pa_transform_pts_sized", J);
     TRY(pa_launch_transform_pts(pts, params, t, B, J, 0.f, sizes, out, pts_img, ST(s))); return 0;
 }
 int pa_affine_warp_bilinear(const uint8_t* src, int Hs, int Ws, const double* tinv, const double* params, int B, int res,
                             void* out4, float* outf, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_affine_warp_bilinear", src); NEED_PTR("pa_affine_warp_bilinear", tinv); NEED_PTR("pa_affine_warp_bilinear", params);
+    NEED_POS("pa_affine_warp_bilinear", Hs); NEED_POS("pa_affine_warp_bilinear", Ws); NEED_POS("pa_affine_warp_bilinear", B); NEED_POS("pa_affine_warp_bilinear", res);
+    if (!out4 && !outf) { pa_set_error_msg("pa_affine_warp_bilinear: out4 and outf are both NULL"); return 1; }
     TRY(pa_launch_warp(src, Hs, Ws, nullptr, tinv, params, B, res, reinterpret_cast<bf16*>(out4), outf, ST(s))); return 0;
 }
 int pa_affine_warp_bilinear_sized(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, const double* tinv, const double* params,
                                   int B, int res, void* out4, float* outf, void* s) {
-    if (!sizes) { pa_set_error_msg("pa_affine_warp_bilinear_sized: sizes is NULL"); return 1; }
+    g_err[0] = 0;
+    NEED_PTR("pa_affine_warp_bilinear_sized", src); NEED_PTR("pa_affine_warp_bilinear_sized", sizes); NEED_PTR("pa_affine_warp_bilinear_sized", tinv);
+    NEED_PTR("pa_affine_warp_bilinear_sized", params);
+    NEED_POS("pa_affine_warp_bilinear_sized", Hs); NEED_POS("pa_affine_warp_bilinear_sized", Ws); NEED_POS("pa_affine_warp_bilinear_sized", B);
+    NEED_POS("pa_affine_warp_bilinear_sized", res);
+    if (!out4 && !outf) { pa_set_error_msg("pa_affine_warp_bilinear_sized: out4 and outf are both NULL"); return 1; }
     TRY(pa_launch_warp(src, Hs, Ws, sizes, tinv, params, B, res, reinterpret_cast<bf16*>(out4), outf, ST(s))); return 0;
 }
 // backward of the bilinear sampler (warp_bwd.hip): d loss / d tinv, d gain and, through the chain rule of warp_bwd.h, d params
@@ -131,10 +158,16 @@ int pa_crop_stretch(const uint8_t* src, int Hs, int Ws, const int32_t* sizes, co
     TRY(pa_launch_crop_stretch(src, Hs, Ws, sizes, params, B, res, workspace, reinterpret_cast<bf16*>(out4), outf, out8, ST(s))); return 0;
 }
 int pa_flip_lr_nhwc4(const void* src, void* dst, int B, int H, int W, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_flip_lr_nhwc4", src); NEED_PTR("pa_flip_lr_nhwc4", dst);
+    NEED_POS("pa_flip_lr_nhwc4", B); NEED_POS("pa_flip_lr_nhwc4", H); NEED_POS("pa_flip_lr_nhwc4", W);
     TRY(pa_launch_flip_lr_nhwc4(reinterpret_cast<const bf16*>(src), reinterpret_cast<bf16*>(dst), B, H, W, ST(s))); return 0;
 }
 int pa_flip_tta_merge(const float* out, const float* out_flipped, float* merged, int B, int J, int H, int W, void* s) {
-    if (J != 16) { pa_set_error_msg("pa_flip_tta_merge: the left/right joint table is MPII's (16 joints)"); return 1; }
+    g_err[0] = 0;
+    NEED_PTR("pa_flip_tta_merge", out); NEED_PTR("pa_flip_tta_merge", out_flipped); NEED_PTR("pa_flip_tta_merge", merged);
+    NEED_POS("pa_flip_tta_merge", B); NEED_POS("pa_flip_tta_merge", H); NEED_POS("pa_flip_tta_merge", W);
+    if (J != 16) { pa_set_error_msg("pa_flip_tta_merge: J must be 16, the left/right joint table is MPII's (16 joints)"); return 1; }
     TRY(pa_launch_flip_tta_merge(out, out_flipped, merged, B, H, W, ST(s))); return 0;
 }
 int pa_sample_aug(const float* meta, const int32_t* scale_idx, const int32_t* rot_idx, int mode, uint64_t seed, uint64_t step,
@@ -238,9 +271,15 @@ int pa_adam_set_steps(pa_adam_state* state, long long steps, void* s) {
     TRY(pa_launch_adam_set_steps(reinterpret_cast<PaAdamState*>(state), (int)steps, ST(s))); return 0;
 }
 int pa_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_nchw_to_nhwc", src); NEED_PTR("pa_nchw_to_nhwc", dst);
+    NEED_POS("pa_nchw_to_nhwc", B); NEED_POS("pa_nchw_to_nhwc", C); NEED_POS("pa_nchw_to_nhwc", H); NEED_POS("pa_nchw_to_nhwc", W);
     TRY(pa_launch_nchw_f32_to_nhwc_bf16(src, reinterpret_cast<bf16*>(dst), B, C, H, W, ST(s))); return 0;
 }
 int pa_nhwc_to_nchw(const void* src, float* dst, int B, int C, int H, int W, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_nhwc_to_nchw", src); NEED_PTR("pa_nhwc_to_nchw", dst);
+    NEED_POS("pa_nhwc_to_nchw", B); NEED_POS("pa_nhwc_to_nchw", C); NEED_POS("pa_nhwc_to_nchw", H); NEED_POS("pa_nhwc_to_nchw", W);
     TRY(pa_launch_nhwc_bf16_to_nchw_f32(pa_plain(reinterpret_cast<const bf16*>(src)), dst, B, C, H, W, ST(s))); return 0;
 }
 
