@@ -67,6 +67,29 @@ int pa_get_preds_nhwc(const float* maps, int B, int J, int H, int W, float* pred
 int pa_final_preds_nhwc(const float* maps, const float* center, const float* scale, const float* rot,
                         int B, int J, int H, int W, float* out, float* scratch_preds, void* stream);
 
+/* Soft-arg-max over heat maps (integral regression): the differentiable prediction beside the hard arg-max of pa_get_preds.  Per map
+ * (b, j), with m its maximum, p the pixel index, x_p = p % W + 1 and y_p = p / W + 1 (1-based like pa_get_preds; the row is p / W):
+ *   e_p = exp(beta (h_p - m)),  Z = sum e_p,  ex = sum x_p e_p / Z,  ey = sum y_p e_p / Z.
+ * maps: fp32 on the device, finite; layout 0 = [B][J][H][W], 1 = [B][H*W][J] (pa_hg_set_heat_grads' numbers; 1 is what
+ * pa_hg_heatmap_nhwc points at).  beta: the inverse temperature.  coords [B][J][2] fp32 = (float)ex, (float)ey; state [B][J][4] float64 =
+ * m, Z, ex, ey unrounded (what the backward pass reads).  All arithmetic in double, no atomics, a fixed order of additions: the same
+ * input gives the same bits.  J == 16 with layout 1 and a 16-byte-aligned maps takes 16-byte loads, one workgroup per sample and group of
+ * four joints; everything else a strided kernel, one workgroup per map.  Enqueued on `stream`, no synchronisation; the same code in both
+ * builds.
+ * Errors (non-zero, pa_last_error set, nothing launched): a NULL pointer; B, J, H or W < 1; H * W >= 2^27 or B * J >= 2^31; a layout
+ * other than 0 or 1; beta not finite or <= 0. */
+int pa_soft_argmax(const float* maps, int layout, int B, int J, int H, int W, float beta, float* coords, double* state, void* stream);
+/* Its backward pass: dmaps_p = (float)(beta e_p / Z ((x_p - ex) gx + (y_p - ey) gy)) with (gx, gy) = dcoords [B][J][2] fp32 (d loss /
+ * d coords), e_p recomputed from maps and state (pa_soft_argmax's, same maps, layout and beta).  One pass: maps is read once and every
+ * element of dmaps (fp32, the layout of maps: layout 1 goes straight into pa_hg_set_heat_grads) is written once.  dmaps must not be
+ * maps.  The fast path additionally needs a 16-byte-aligned dmaps.
+ * Errors: as above, and dmaps == maps. */
+int pa_soft_argmax_bwd(const float* maps, int layout, int B, int J, int H, int W, float beta, const double* state, const float* dcoords,
+                       float* dmaps, void* stream);
+/* Calibration of the soft-arg-max error bound (tools/bench_soft_argmax.py): y[i] = the device's double exp(x[i]), the function the two
+ * kernels above evaluate; x, y: n float64 on the device.  Errors: x or y NULL, n == 0. */
+int pa_exp_probe(const double* x, double* y, size_t n, void* stream);
+
 /* PCK from point sets: Evaluation.calc_dists/dist_acc/accuracy (pylib/Evaluation.py:25-75; boundary
  * 1), accuracy_origin_res (:77-97; boundary 0), per_person_pckh (:99-167; `person` output with the
  * visibility points `vis`), HumanAcc.approx_PCKh (pylib/HumanAcc.py:7-44; boundary 0, norm = res/10

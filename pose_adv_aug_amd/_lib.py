@@ -84,6 +84,9 @@ _PROTOS = {
     'pa_final_preds': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'pa_get_preds_nhwc': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'pa_final_preds_nhwc': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'pa_soft_argmax': (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    'pa_soft_argmax_bwd': (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    'pa_exp_probe': (_i, [_vp, _vp, _sz, _vp]),
     'pa_pck': (_i, [_vp, _vp, _vp, _f, _vp, _i, _f, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'pa_affine_params': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     'pa_transform_pts': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),

@@ -2,6 +2,7 @@
 #include "../../include/poseadv.h"
 #include "net.h"
 #include "warp_bwd.h"
+#include "soft_argmax.h"
 #include <stdio.h>
 #include <string.h>
 #include <new>
@@ -123,6 +124,36 @@ int pa_affine_params_bwd_host(const double* params_host, const double* dtinv_hos
         pa_affine_params_chain(params_host + (size_t)b * 8, dtinv_host + (size_t)b * 6, dgain_host ? dgain_host + (size_t)b * 3 : nullptr,
                                (double)res_in, dparams_host + (size_t)b * 8);
     return 0;
+}
+// soft-arg-max over heat maps and its backward pass (soft_argmax.hip); every refusal is decided here, before any device call
+static int soft_argmax_args(const char* fn, int layout, int B, int J, int H, int W, float beta) {
+    std::string f(fn);
+    if (B < 1 || J < 1 || H < 1 || W < 1) { pa_set_error_msg((f + ": B, J, H and W must be >= 1").c_str()); return 1; }
+    if ((long long)H * W >= (1LL << 27) || (long long)B * J > 0x7fffffffLL) { pa_set_error_msg((f + ": H * W must stay below 2^27 and B * J below 2^31").c_str()); return 1; }
+    if (layout != 0 && layout != 1) { pa_set_error_msg((f + ": layout must be 0 ([B][J][H][W]) or 1 ([B][H*W][J])").c_str()); return 1; }
+    if (!(beta > 0.f) || !(beta <= 3.402823466e38f)) { pa_set_error_msg((f + ": beta must be finite and > 0").c_str()); return 1; }
+    return 0;
+}
+int pa_soft_argmax(const float* maps, int layout, int B, int J, int H, int W, float beta, float* coords, double* state, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_soft_argmax", maps); NEED_PTR("pa_soft_argmax", coords); NEED_PTR("pa_soft_argmax", state);
+    if (soft_argmax_args("pa_soft_argmax", layout, B, J, H, W, beta)) return 1;
+    TRY(pa_launch_soft_argmax(maps, layout, B, J, H, W, beta, coords, state, ST(s))); return 0;
+}
+int pa_soft_argmax_bwd(const float* maps, int layout, int B, int J, int H, int W, float beta, const double* state, const float* dcoords,
+                       float* dmaps, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_soft_argmax_bwd", maps); NEED_PTR("pa_soft_argmax_bwd", state); NEED_PTR("pa_soft_argmax_bwd", dcoords); NEED_PTR("pa_soft_argmax_bwd", dmaps);
+    if (soft_argmax_args("pa_soft_argmax_bwd", layout, B, J, H, W, beta)) return 1;
+    if (dmaps == maps) { pa_set_error_msg("pa_soft_argmax_bwd: dmaps must not alias maps"); return 1; }
+    TRY(pa_launch_soft_argmax_bwd(maps, layout, B, J, H, W, beta, state, dcoords, dmaps, ST(s))); return 0;
+}
+// calibration of the soft-arg-max bound: y[i] = the device's double exp(x[i]), the function those kernels call
+int pa_exp_probe(const double* x, double* y, size_t n, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_exp_probe", x); NEED_PTR("pa_exp_probe", y);
+    if (n == 0) { pa_set_error_msg("pa_exp_probe: n must be >= 1"); return 1; }
+    TRY(pa_launch_exp_probe(x, y, n, ST(s))); return 0;
 }
 size_t pa_crop_workspace_bytes(int B, int Hs, int Ws, int res) { return pa_crop_workspace_size(B, Hs, Ws, res); }
 int pa_crop_design_bytes(int B, int Hs, int Ws, int res, double* out) { if (!out) return 1; pa_crop_bytes_bound(B, Hs, Ws, res, out, out + 1); return 0; }

@@ -195,9 +195,9 @@ class _HeatMapsFunction(torch.autograd.Function):
     to net.flat_grads through HourglassNet.backward()."""
 
     @staticmethod
-    def forward(ctx, anchor, net, x, img4, pts, dropout_masks):
-        outs = net._forward(x, img4, pts, dropout_masks)
-        ctx.net, ctx.serial, ctx.done = net, net._fwd_serial, False
+    def forward(ctx, anchor, net, x, img4, pts, dropout_masks, layout):
+        outs = net._forward(x, img4, pts, dropout_masks, layout)
+        ctx.net, ctx.serial, ctx.done, ctx.layout = net, net._fwd_serial, False, layout
         # which input carries the image: its gradient (HourglassNet.backward(input_grad=...)) is returned when autograd asks for it
         ctx.img4_dtype = img4.dtype if img4 is not None else None      # (the engine reads img4 when it is given)
         ctx.set_materialize_grads(False)                # a stack the loss does not use arrives as None = zero, not as a tensor of zeros
@@ -214,11 +214,11 @@ class _HeatMapsFunction(torch.autograd.Function):
         ctx.done = True
         want_x, want_img4 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         if want_x and ctx.img4_dtype is None:
-            return (None, None, net.backward(grads, input_grad='nchw'), None, None, None)
+            return (None, None, net.backward(grads, ctx.layout, input_grad='nchw'), None, None, None, None)
         if want_img4 and ctx.img4_dtype is not None:
-            return (None, None, None, net.backward(grads, input_grad='nhwc4').to(ctx.img4_dtype), None, None)
-        net.backward(grads)
-        return (None,) * 6
+            return (None, None, None, net.backward(grads, ctx.layout, input_grad='nhwc4').to(ctx.img4_dtype), None, None, None)
+        net.backward(grads, ctx.layout)
+        return (None,) * 7
 
 
 class HourglassNet(_HipModule):
@@ -278,7 +278,9 @@ class HourglassNet(_HipModule):
     _last_masks = None       # the dropout masks of the last forward pass (backward() sets them again around its pass)
     _fwd_serial = 0          # counts the forward passes (whole or half) of this net: forward_autograd's backward needs ITS pass's activations
 
-    def _forward(self, x, img4, pts, dropout_masks=None):
+    def _forward(self, x, img4, pts, dropout_masks=None, layout='nchw'):
+        if layout not in ('nchw', 'nhwc'):
+            raise ValueError("layout must be 'nchw' or 'nhwc', got %r" % (layout,))
         B = x.shape[0] if x is not None else img4.shape[0]
         h = self._net(B)
         self._last_B = B
@@ -296,12 +298,26 @@ class HourglassNet(_HipModule):
         if self.training:
             self._nbt += 1
         self._last_losses = losses
-        return self.heatmaps(B)
+        return self.heatmaps(B, layout)
 
-    def heatmaps(self, B=None):
+    def heatmaps(self, B=None, layout='nchw'):
+        """The per-stack heat maps of the last forward pass at batch size B.  'nchw' (default): new tensors [B][16][res/4][res/4], one
+        conversion launch per stack.  'nhwc': [B][res/4][res/4][16] VIEWS of the engine's own buffers (pa_hg_heatmap_nhwc), no launch and
+        no copy -- valid until the next forward pass of this net overwrites them (clone what has to outlive it), and not to be written."""
+        if layout not in ('nchw', 'nhwc'):
+            raise ValueError("layout must be 'nchw' or 'nhwc', got %r" % (layout,))
         B = B or self._last_B
         h = self._net(B)
         outs = []
+        if layout == 'nhwc':
+            ws, Hh = self._nets[B][1], self.res // 4
+            nbytes = B * Hh * Hh * 16 * 4
+            for i in range(self.num_stacks):
+                off = lib().pa_hg_heatmap_nhwc(h, i) - ws.data_ptr()          # the pointer lies in the workspace tensor this module owns
+                if off < 0 or off % 16 or off + nbytes > ws.numel():
+                    raise PoseAdvError('heatmaps: the heat maps of stack %d are not inside the bound workspace' % i)
+                outs.append(ws[off:off + nbytes].view(torch.float32).view(B, Hh, Hh, 16).detach())
+            return outs
         for i in range(self.num_stacks):
             o = torch.empty((B, 16, self.res // 4, self.res // 4), dtype=torch.float32, device=self.flat_params.device)
             check(lib().pa_hg_heatmap_nchw(h, i, ptr(o)), 'pa_hg_heatmap_nchw')
@@ -460,7 +476,7 @@ class HourglassNet(_HipModule):
         del keep, masks
         return dimg
 
-    def forward_autograd(self, x=None, img4=None, pts=None, dropout_masks=None):
+    def forward_autograd(self, x=None, img4=None, pts=None, dropout_masks=None, layout='nchw'):
         """forward() whose per-stack heat maps carry a grad_fn: `loss = my_loss(outs); loss.backward(); optimizer.step()`.
         Returns a tuple of num_stacks tensors [B][16][res/4][res/4].  loss.backward() calls self.backward() once with the gradients autograd
         delivers; the parameter gradients land in flat_grads (the project's convention: the parameter views carry no .grad).  An input
@@ -468,11 +484,16 @@ class HourglassNet(_HipModule):
         img4's dtype, 4th channel 0) -- FGSM / PGD, a learnable occluder or a generator in front of the net; without requires_grad no
         launch is added.  The engine keeps ONE forward pass's activations: backward a second time through the same outputs, or after
         another forward pass of this net, raises RuntimeError.  pts is optional (accuracy() and _last_losses, as in forward());
-        dropout_masks as in forward(): the backward pass differentiates through the same masks."""
+        dropout_masks as in forward(): the backward pass differentiates through the same masks.
+        layout='nhwc': the outputs are [B][res/4][res/4][16] views of the engine's own maps (heatmaps(layout='nhwc'): no conversion launch,
+        valid until the next forward pass of this net), and the gradients autograd delivers go to backward(layout='nhwc') as they are --
+        the layout pylib.Evaluation.soft_argmax(layout='nhwc') reads and writes in place."""
+        if layout not in ('nchw', 'nhwc'):
+            raise ValueError("layout must be 'nchw' or 'nhwc', got %r" % (layout,))
         self._ensure_table()
         if getattr(self, '_autograd_anchor', None) is None:
             self._autograd_anchor = torch.zeros(1, dtype=torch.float32, device=self.flat_params.device, requires_grad=True)
-        return _HeatMapsFunction.apply(self._autograd_anchor, self, x, img4, pts, dropout_masks)
+        return _HeatMapsFunction.apply(self._autograd_anchor, self, x, img4, pts, dropout_masks, layout)
 
     def accuracy(self, idxs, stack=-1):
         """Evaluation.accuracy (pylib/Evaluation.py:54-75) of the last forward's heat maps against the

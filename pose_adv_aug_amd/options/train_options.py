@@ -22,6 +22,10 @@ class TrainOptions(BaseOptions):
         p.add_argument('--beta2', type=float, default=0.999, help='Adam / AdamW: decay of the second moment')
         p.add_argument('--adam_eps', type=float, default=1e-8, help='Adam / AdamW: eps added to the denominator')
         p.add_argument('--amsgrad', type=int, default=0, help='1: Adam / AdamW with AMSGrad (0: off)')
+        # coordinate loss beside the heat-map MSE (stack_hg.coord_criterion): W * mean |soft-arg-max(out, beta) - pts| per stack; 0 = off, the
+        # reference's recipe and the fused step
+        p.add_argument('--coord_loss', type=float, default=0., help='weight of the soft-arg-max coordinate L1 loss (0: off)')
+        p.add_argument('--coord_beta', type=float, default=1., help='inverse temperature of the soft-arg-max of --coord_loss')
         p.add_argument('--bs', type=int, default=12, help='mini-batch size')
         p.add_argument('--load_checkpoint', type=_bool, default=False, help='resume from checkpoint model')
         p.add_argument('--load_checkpoint_pose', type=_bool, default=False, help='use checkpoint model')
@@ -48,4 +52,6 @@ class TrainOptions(BaseOptions):
         o = self.parser.parse_args(args)
         if o.optimizer != 'rmsprop' and (o.momentum != 0 or o.centered):
             self.parser.error('--momentum and --centered are RMSprop options: not with --optimizer %s' % o.optimizer)
+        if o.coord_loss < 0 or not o.coord_beta > 0:
+            self.parser.error('--coord_loss must be >= 0 and --coord_beta > 0')
         return BaseOptions.parse(self, args)

@@ -47,3 +47,27 @@ def weighted_L2(pred, gt, weight):
             raise ValueError('weighted_L2: a pred that requires grad must be a float32 tensor on the HIP device')
         return _WeightedL2.apply(pred, p, g, w, scale)
     return _loss(p, g, w, scale)
+
+
+def coord_L1(pred_xy, pts, valid=None, size=None):
+    """Mean absolute coordinate error over the valid joints: sum(|pred_xy - pts| over x, y of the valid joints) / (2 * their number),
+    0 when no joint is valid.  pred_xy: [B][J][2] predictions in heat-map coordinates (Evaluation.soft_argmax of the maps), pts: [B][J][2]
+    targets (1-based, any float dtype).  valid: [B][J] bool; None: the reference's rule on pts, 0 < x <= W and 0 < y <= H with
+    size = (W, H) of the heat maps (pylib/HumanPts.py:36-46: a joint outside gets an all-zero target map) -- without `size` only the
+    lower half, x > 0 and y > 0, can be applied.  Plain torch on B * J * 2 numbers: differentiable in pred_xy, no host synchronisation.
+    Returns a 0-d tensor."""
+    if not isinstance(pred_xy, torch.Tensor) or pred_xy.dim() != 3 or pred_xy.shape[-1] != 2:
+        raise ValueError('coord_L1: pred_xy must be a [B][J][2] tensor')
+    t = torch.as_tensor(pts).to(device=pred_xy.device, dtype=pred_xy.dtype)
+    if t.shape != pred_xy.shape:
+        raise ValueError('coord_L1: pts %s does not match pred_xy %s' % (tuple(t.shape), tuple(pred_xy.shape)))
+    if valid is None:
+        v = (t[..., 0] > 0) & (t[..., 1] > 0)
+        if size is not None:
+            v = v & (t[..., 0] <= size[0]) & (t[..., 1] <= size[1])
+    else:
+        v = torch.as_tensor(valid).to(device=pred_xy.device, dtype=torch.bool)
+        if v.shape != pred_xy.shape[:2]:
+            raise ValueError('coord_L1: valid %s must be [B][J] = %s' % (tuple(v.shape), tuple(pred_xy.shape[:2])))
+    w = v.to(pred_xy.dtype).unsqueeze(-1)
+    return ((pred_xy - t).abs() * w).sum() / (2.0 * w.sum()).clamp(min=1.0)

@@ -15,6 +15,68 @@ def get_preds(scores):
     return out
 
 
+def _soft_argmax_shape(heat, layout):
+    """(B, J, H, W) and the layout number of a heat-map tensor; ValueError for anything pa_soft_argmax cannot read in place"""
+    if layout not in ('nchw', 'nhwc'):
+        raise ValueError("soft_argmax: layout must be 'nchw' or 'nhwc', got %r" % (layout,))
+    if not isinstance(heat, torch.Tensor) or heat.dtype != torch.float32 or heat.dim() != 4:
+        raise ValueError('soft_argmax: heat must be a 4-dim float32 tensor')
+    if heat.device != dev():
+        raise ValueError('soft_argmax: heat must be on the HIP device %s, got %s' % (dev(), heat.device))
+    if min(heat.shape) < 1:
+        raise ValueError('soft_argmax: empty heat maps %s' % (tuple(heat.shape),))
+    if layout == 'nchw':
+        B, J, H, W = heat.shape
+    else:
+        B, H, W, J = heat.shape
+    return B, J, H, W, (0 if layout == 'nchw' else 1)
+
+
+def _soft_argmax_fwd(h, dims, beta):
+    B, J, H, W, lay = dims
+    coords = torch.empty((B, J, 2), dtype=torch.float32, device=h.device)
+    state = torch.empty((B, J, 4), dtype=torch.float64, device=h.device)
+    check(lib().pa_soft_argmax(ptr(h), lay, B, J, H, W, beta, ptr(coords), ptr(state), stream()), 'pa_soft_argmax')
+    return coords, state
+
+
+class _SoftArgmax(torch.autograd.Function):
+    """soft_argmax for a `heat` that requires grad: forward pa_soft_argmax, backward pa_soft_argmax_bwd from the maps and the state
+    (m, Z, ex, ey in float64) the forward left on ctx.  No host synchronisation on either side."""
+
+    @staticmethod
+    def forward(ctx, heat, h, dims, beta):
+        coords, state = _soft_argmax_fwd(h, dims, beta)
+        ctx.h, ctx.dims, ctx.beta, ctx.state = h, dims, beta, state          # (h: heat's detached contiguous storage, what the kernels read)
+        return coords
+
+    @staticmethod
+    def backward(ctx, gout):
+        B, J, H, W, lay = ctx.dims
+        g = gout.detach().to(torch.float32).contiguous()
+        dmaps = torch.empty_like(ctx.h)
+        check(lib().pa_soft_argmax_bwd(ptr(ctx.h), lay, B, J, H, W, ctx.beta, ptr(ctx.state), ptr(g), ptr(dmaps), stream()),
+              'pa_soft_argmax_bwd')
+        return dmaps, None, None, None
+
+
+def soft_argmax(heat, beta=1.0, layout='nchw'):
+    """The soft-arg-max (integral regression) of heat maps: b x n x h x w ('nchw') or b x h x w x n ('nhwc', the engine's own layout:
+    HourglassNet.forward_autograd(layout='nhwc')) -> b x n x 2 fp32 on the device, the expectation of the 1-based (x, y) under
+    softmax(beta * map).  Comparable with get_preds and with the heat-map coordinates `pts`; beta is the inverse temperature (large: the
+    hard arg-max).  Evaluated in double in a fixed order (pa_soft_argmax): two calls give the same bits.  Differentiable in `heat` (a
+    tensor that requires grad gets a grad_fn whose backward is pa_soft_argmax_bwd; the gradient has heat's layout).  No host
+    synchronisation.  heat must be a float32 tensor on the HIP device with finite values; anything else raises ValueError."""
+    dims = _soft_argmax_shape(heat, layout)
+    beta = float(beta)
+    if not (0.0 < beta < float('inf')):
+        raise ValueError('soft_argmax: beta must be finite and > 0, got %r' % (beta,))
+    h = heat.detach().contiguous()
+    if heat.requires_grad and torch.is_grad_enabled():
+        return _SoftArgmax.apply(heat, h, dims, beta)
+    return _soft_argmax_fwd(h, dims, beta)[0]
+
+
 def _pck(pred, gt, norm, boundary, idxs, thr=0.5, vis=None, want_person=False, want_dists=False):
     p = to_dev(pred, torch.float32); g = to_dev(gt, torch.float32); nm = to_dev(norm, torch.float32).reshape(-1)
     B, J = p.shape[0], p.shape[1]

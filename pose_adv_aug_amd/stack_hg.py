@@ -54,13 +54,28 @@ def broadcast_parameters(net):
         net.weights_changed()
 
 
-def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, criterion=None):
+def coord_criterion(weight, beta=1.0):
+    """The criterion of --coord_loss for train_step(criterion=..., heat_layout='nhwc'): per stack the reference's heat-map MSE
+    (weighted_L2 against the Gaussian target of data['pts'], weight 1) + weight * coord_L1(soft_argmax(out, beta), data['pts']), summed
+    over the stacks, on the engine's own joint-minor maps [B][H][W][16]."""
+    from .pylib import Criterion, Evaluation, HumanPts
+
+    def criterion(outs, data):
+        H, W = outs[0].shape[1], outs[0].shape[2]
+        target = HumanPts.pts2heatmap_batch(data['pts'], H, W).permute(0, 2, 3, 1).contiguous()
+        return sum(Criterion.weighted_L2(o, target, 1) + weight * Criterion.coord_L1(Evaluation.soft_argmax(o, beta, 'nhwc'), data['pts'], size=(W, H))
+                   for o in outs)
+    return criterion
+
+
+def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, criterion=None, heat_layout='nchw'):
     """stack-hg.py:134-180 for one batch.  Returns device scalars (loss, pckh, pckh_origin_res).
     data: the batch's augmented input if it was prepared ahead (data.AugmentAhead), else it is made here.
     criterion: a callable (outs, data) -> 0-d loss tensor over the per-stack heat maps of net.forward_autograd (your own loss, e.g.
     pylib.Criterion.weighted_L2 with per-joint weights): forward, criterion, loss.backward(), optimizer.step().  None (the default,
     what every shipped loop passes): the built-in fused MSE step.  A data['img4'] that requires grad gets its .grad from that backward
-    pass (forward_autograd: d loss / d image, NHWC4)."""
+    pass (forward_autograd: d loss / d image, NHWC4).  heat_layout: the layout of the maps the criterion receives ('nhwc': views of the
+    engine's own buffers, forward_autograd(layout='nhwc'))."""
     if data is None:
         data = augmenter.regular(batch)
     def meters():
@@ -68,7 +83,7 @@ def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, crit
         pckh_o, _ = net.pckh_origin_res(data['c'], data['s'], data['r'], data['grnd_pts'], data['normalizer'])   # :178
         return pckh, pckh_o
     if criterion is not None:
-        outs = net.forward_autograd(img4=data['img4'], pts=data['pts'])
+        outs = net.forward_autograd(img4=data['img4'], pts=data['pts'], layout=heat_layout)
         loss = criterion(outs, data)
         loss.backward()
         optimizer.step()
@@ -112,9 +127,10 @@ def warn_skipped_steps(optimizer, log=print, name=''):
     return n - seen
 
 
-def train(batches, net, optimizer, augmenter, epoch, opt, log=print):
+def train(batches, net, optimizer, augmenter, epoch, opt, log=print, criterion=None):
     """stack-hg.py:124-189 over a sized feed of DeviceBatches (a list, data.BatchFeed, MPII.batches()).  The meters see
-    EVERY iteration (:171-180) through device-side sums; the host synchronises only every print_freq steps."""
+    EVERY iteration (:171-180) through device-side sums; the host synchronises only every print_freq steps.
+    criterion (None: the fused MSE step): a loss of the joint-minor maps, train_step(criterion=..., heat_layout='nhwc')."""
     net.train()
     n = len(batches)
     meters = None
@@ -124,7 +140,10 @@ def train(batches, net, optimizer, augmenter, epoch, opt, log=print):
             ahead.start(batch)
         data = ahead.take()
         ahead.start(nxt)                                   # the next batch's crop runs beside this step's forward pass
-        loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data)
+        if criterion is None:
+            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data)
+        else:
+            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, criterion=criterion, heat_layout='nhwc')
         if meters is None:
             meters = DeviceMeters(('loss', 'pckh', 'pckh_origin_res'), loss.device)
         meters.update({'loss': loss, 'pckh': pckh, 'pckh_origin_res': pckh_o})
@@ -224,9 +243,13 @@ def main(argv=None):
             ckpt.save_preds(predictions)
         return
     start = history.epoch[-1]['epoch'] + 1 if history.epoch else 0
+    criterion = coord_criterion(opt.coord_loss, opt.coord_beta) if opt.coord_loss > 0 else None      # (0: the fused step, unchanged)
     for epoch in range(start, opt.nEpochs):
         adjust_lr(opt, optimizer, epoch)
-        tl, tp = train(batches, net, optimizer, augmenter, epoch, opt, log=log)
+        if criterion is None:
+            tl, tp = train(batches, net, optimizer, augmenter, epoch, opt, log=log)
+        else:
+            tl, tp = train(batches, net, optimizer, augmenter, epoch, opt, log=log, criterion=criterion)
         vl, vp, predictions = validate(val_batches, net, augmenter, epoch, opt, log=log)      # stack-hg.py:98-99
         history.update(OrderedDict([('epoch', epoch)]), OrderedDict([('lr', optimizer.param_groups[0]['lr'])]),
                        OrderedDict([('train_loss', tl), ('val_loss', vl)]), OrderedDict([('train_pckh', tp), ('val_pckh', vp)]))
