@@ -52,7 +52,8 @@ from tests.bn_exact import E, U
 # tests/test_asn_exact_cpu.py::test_oracle_conditioning recomputes the small entries): {(chan, B, res, seed, occlusion agent): value}
 LARGEST_MEAN_OVER_SIGMA = {(256, 24, 256, 51, False): 2.38, (256, 3, 384, 52, False): 2.70, (128, 4, 256, 53, False): 2.70,
                            (256, 24, 256, 54, True): 2.50, (128, 2, 256, 55, True): 2.37, (256, 3, 384, 56, False): 2.60,
-                           (512, 2, 256, 60, False): 3.07, (512, 2, 256, 61, True): 2.83, (512, 2, 256, 62, False): 3.25}
+                           (512, 2, 256, 60, False): 3.07, (512, 2, 256, 61, True): 2.83, (512, 2, 256, 62, False): 3.25,
+                           (256, 3, 320, 91, False): 2.55, (128, 2, 448, 92, False): 2.76, (128, 2, 448, 93, False): 2.70}
 
 IN_PREFIX = ['residual_skip1.', 'residual_skip2.', 'residual_skip3.', 'residual_skip4.', 'residual_neck.']
 POSE_FEATS = ['hg0.skip1', 'hg0.skip2', 'hg0.skip3', 'hg0.skip4', 'hg0.neck']
@@ -205,8 +206,16 @@ def check_pooladd_bwd(dpa, val_hi, val_lo, dhi, dlo, dtype):
     return r + BX._mismatch(dlo, dpa.float() * (val_lo > 0).float()), ties
 
 
+def outside_window(dtop):
+    """elements of the top map's gradient [B][C][H][W] outside the top-left 4 x 4 window that are not exactly zero (NaN counts): the head
+    averages that window only (AvgPool2d(4) on a 5 x 5, 6 x 6 or 7 x 7 map has one window) and nothing else reads the top map"""
+    out = dtop.clone()
+    out[:, :, :4, :4] = 0
+    return int((out != 0).sum())
+
+
 KINDS = ('pool+add forward', 'pool+add backward', 'head logits', 'head loss', 'head fc gradients', 'head data gradient',
-         'mode 2 running stats', 'mode 2 logits')
+         'head gradient outside the window', 'mode 2 running stats', 'mode 2 logits')
 
 
 def oracle_pair(chan, res, seed, dropout=False):
@@ -441,7 +450,11 @@ def run_leg(chan, B, res, seed, log=print, expect=(), history='fresh', stored_ex
             L.params |= {nm + '.weight', nm + '.bias'}
         dz = E(torch.cat([hs['dz'].v, hr['dz'].v], 1), torch.cat([hs['dz'].e, hr['dz'].e], 1))
         da, win = dact_term(dz, Wall, tuple(top.shape))
-        L.note_t('head data gradient', 'deep2 ' + tag, CX.check16(Pa.get('deep2', 1), da, dtype, (top > 0).double() * win))
+        dtop = Pa.get('deep2', 1)
+        L.note_t('head data gradient', 'deep2 ' + tag, CX.check16(dtop, da, dtype, (top > 0).double() * win))
+        # (check16's bound is 0 outside the window, which already admits nothing there; said once more on its own, per element)
+        assert top.shape[2] == top.shape[3] == res // 64 and int(win[0, 0].sum()) == 16
+        L.note('head gradient outside the window', 'deep2 ' + tag, outside_window(dtop), bit=True)
     L.trunk(grads, before, expect, stored_expected)
     L.coverage(grads)
     # update_running=False: the same batch statistics, the running estimates left alone

@@ -39,6 +39,15 @@ dz * (x - mean) * invstd, bn_eval_kernel), with u = 2^-24 and these rules (class
     pa_max_stat_rows = max(512, ceil(n / 64)) does not depend on C; and the consumer-prologue finalize, which the plan's takes_fin does not
     admit above 256 input channels, is replaced by the launch form, whose order for R <= 128 rows is the prologue's own (8 + 4 deep,
     reduce_partial_rows) and for more rows ceil(R / 64) + 20 as above.
+    At the input resolutions 320 / 448 / 192 / 64 (maps 80 ... 5, 112 ... 7, 48 ... 3, 16 ... 1; re-derived from launch_plan.h,
+    elementwise.hip, conv_plan.h and conv3x3_tile.hip, nothing changes in D): the streaming launches whose row items
+    (W / 2) * (C / 8) fit none of the tried workgroup sizes 512 / 256 / 384 / 192 / 128 (W 20 / 28 / 10 / 14 at chan 256, also W 40 / 56
+    at chan 128) run the generic grid-stride kernels with the first-computed 256 or 512 threads (>= 128) in <= 512 workgroups, the same
+    one-group-per-thread chain, shuffle levels and <= 16 waves, so the streaming term stands as written (these launches stay below 512
+    workgroups: one item, four pixels, per thread); where a size fits it is one of the tried ones, all >= 128.  The generic conv kernel
+    takes the 3 x 3 layers of the 10 x 10 / 14 x 14 maps in 64-pixel rows, and the ONE masked 8 x 8 tile of the 5 x 5 / 7 x 7 / 3 x 3 /
+    1 x 1 maps writes one row per workgroup of two images, at most 2 * 49 of its 128 pixels alive: both inside the <= 127 of a row.
+    The row counts (<= 200 for the 80 x 80 maps at B 2, 1 ... 4 at the necks) stay below the capacity 512 the finalize term assumes.
   * the backward sum of dz * xhat is written in two forms: per term dz * (x - mean) * invstd (epilogue8, Bwd8, pa_conv_epilogue),
     or per partial row invstd * (sum dz x - mean sum dz) (pa_conv_epilogue_lds_bwd, pa_conv_epilogue_lds_up), which cancels when
     |mean| >> sigma.  The bound covers both: the rounding terms are taken over |dz| (|x - mean| + 2 |mean|), which bounds

@@ -31,6 +31,12 @@ conv_wgrad_tile.hip:157/171, pose_ops.hip:137): no split of the reduction across
     D = 32 + ceil((M / S + 256) / 32) + S.
   * bias gradient (convs without a BatchNorm behind them): any tree over the <= M / S + 256 values of a split (per-thread column sums
     and their LDS sum, conv_wgrad_tile.hip:466, conv_wgrad.hip:222), then the chain over S: D = M / S + 256 + S.
+  At the input resolutions 320 / 448 / 192 / 64 (re-derived for the shapes that leave the halo tiles; nothing changes): the 3 x 3 layers of
+  the 10 x 10 / 14 x 14 maps run the generic kernel, whose chain of 9 * Cin / 32 MFMAs into one accumulator is the forward formula's (an
+  M tile that wraps image rows changes which pixels a tile holds, not the reduction of any of them); the masked 8 x 8 tile of the 7 x 7 /
+  5 x 5 / 3 x 3 / 1 x 1 maps chains all nine taps whether a tap meets a pixel or the zero halo (conv3x3_tile.hip:342-382), the same depth
+  with zero terms.  The weight-gradient plans there are tile plans with a ragged last tile (1 * 56 * 56 pixels = 24.5 tiles of 128) and
+  generic plans with S = 1 for M = 3 ... 49 pixels, less than one 32-pixel MFMA step: both inside the M / S + 2 P pixels of a split.
   S is the split count Net::layout_conv gives the layer: pa_wgrad_layer_splits over the layer's pa_wgrad_plan (csrc/wgrad_plan.h) -- the
   count of the layer launched alone (the tile kernels' where they take the shape, else the generic kernel's), replaced by the grouped
   count where the grouped kernel takes the layer, and 512 for the stem.  The plan is not exported: wgrad_plan() mirrors it for the

@@ -92,13 +92,51 @@ def test_documented_examples(L):
     assert describe(L, 24, 16, 16, 128, 256, 1, BNRELU, ep=OUT_STATS, flags=BIAS, fin=129)['path'] == REFUSED      # <= 128 rows
 
 
+def test_documented_examples_of_the_other_resolutions(L):
+    """The rules of csrc/conv_plan.h in words, on the maps of the 320 / 448 / 192 / 64 inputs (res / 4 ... res / 64): a 3 x 3 launch with 64 or 128
+    input channels takes 8 x 8 halo tiles where both sides are multiples of 8 that the 16 x 8 tiles do not take (W % 16 != 0), 4 x 4 tiles where they
+    are multiples of 4, ONE masked 8 x 8 tile for any other map up to 8 x 8, and no halo tile at all for any other map -- a side above 8 that is no
+    multiple of 4 -- which leaves the generic kernel (its 64 x 64 tier below 128 * 256 pixels).  A workgroup holds 128 / side^2 sub-tiles: two
+    images of a masked tile.  The row-tile instance with a second output needs W % 32 == 0; the launch without it is a plain row-tile launch from
+    192 row tiles of 64 pixels on."""
+    up = lambda a, b: -(-a // b)
+    for cin in (128, 64):
+        for B in (1, 2, 3, 5):
+            for in_, ep, flags in ((BNRELU, OUT_STATS, BIAS), (LIN2, OUT_BWD, DZ)):          # the net's forward and data-gradient launches
+                f = lambda H: describe(L, B, H, H, cin, cin, 9, in_, ep=ep, flags=flags)
+                for H in (10, 14):
+                    d = f(H)
+                    assert (d['path'], d['tiling'], d['gx'], d['gy'], d['threads']) == (GENERIC, 'G64x64_9', up(B * H * H, 64), cin // 64, 256), (cin, B, H, d)
+                    assert d['takes_fin'] and not d['stores_dz'], (cin, B, H, d)           # the 64 x 64 tier carries the finalize prologue; only tile kernels store dz
+                for H in (1, 3, 5, 7):
+                    d = f(H)
+                    assert (d['path'], d['tiling'].split('_')[0], d['gx'], d['gy'], d['rows']) == (TILE3, 'TS8', up(B, 2), cin // 64, up(B, 2)), (cin, B, H, d)
+                d = f(40)
+                assert (d['path'], d['tiling'].split('_')[0], d['gx']) == (TILE3, 'TS8', up(B * 25, 2)), (cin, B, d)
+                d = f(20)
+                assert (d['path'], d['tiling'].split('_')[0], d['gx']) == (TILE3, 'TS4', up(B * 25, 8)), (cin, B, d)
+                # (the 512-thread instances are the small tiles with 128 input channels)
+                assert {f(H)['threads'] for H in (1, 3, 5, 7, 20, 40)} == {512 if cin == 128 else 256}, (cin, B)
+    # the low-resolution half of the upsample-add backward in the 1 x 1 data gradient's second output: the 384 leg's launch (B 3, 96 x 96), and the
+    # same launch on 80 x 80 (3 * 80 * 80 / 64 = 300 row tiles, W % 32 = 16)
+    fused = lambda H, flags: describe(L, 3, H, H, 128, 256, 1, LIN2, PLAIN, ep=OUT_PLAIN, ep2=OUT_BWD if flags & OUT2 else OUT_PLAIN, flags=flags)
+    assert fused(96, OUT2)['path'] == ROW_UP
+    assert fused(80, OUT2)['path'] == REFUSED
+    d = fused(80, 0)
+    assert (d['path'], d['tiling'], d['gx'], d['rows2']) == (ROW, 'R128_64_128', 300, 0), d
+
+
+# map sides of the 320 / 448 / 192 / 64 inputs that no power-of-two or 384 input has (the legs 'on the ... geometry' of tests/test_gpu_conv_exact.py)
+OTHER_RES_MAPS = ((1, 1), (3, 3), (5, 5), (7, 7), (10, 10), (14, 14), (20, 20), (40, 40), (80, 80))
+
+
 def max_stat_rows(M):
     return max(512, (M + 63) // 64)
 
 
 def _grid():
     for B in (3, 24):
-        for H, W in ((4, 4), (16, 16), (64, 64), (6, 6), (16, 32)):
+        for H, W in ((4, 4), (16, 16), (64, 64), (6, 6), (16, 32)) + OTHER_RES_MAPS:
             for Cin in (64, 128, 256, 512):
                 for Cout in (64, 128, 256, 512):
                     for taps in (1, 9):
@@ -152,7 +190,7 @@ def test_invariants_over_shapes_and_every_mode_combination(L):
                             assert flags & DZ and in_ in (LIN2, POOL) and d['path'] in (ROW, TILE3), case
                         if d['pool_route'] or d['pool_in']:
                             assert taps == 1 and Cin == 128 and d['path'] in (ROW, ONESHOT), case
-    assert 40000 <= n <= 100000 and admitted > n // 10, (n, admitted)
+    assert 250000 <= n <= 300000 and admitted > n // 10, (n, admitted)
     # ... on every combination a launch can have (a pool-routed first addend is always refused)
     assert lds_modes >= {(b, a1, a2) for b in (False, True) for a1 in (NONE, PLAIN, BNRELU, LIN2) for a2 in (NONE, PLAIN, BNRELU, LIN2)}
 
@@ -168,7 +206,7 @@ def _reachable(L):
                 (PLAIN, POOL, ADD2_MAP, 0), (PLAIN, NONE, OUT2, 0), (NONE, NONE, DZ, 0), (NONE, NONE, DZ | IN_MAP | IN_Q | EP2_AFFINE, 0), (NONE, NONE, 0, 64))
     reach = set()
     for B in (1, 4, 8, 16, 24):
-        for H, W in ((4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (6, 6), (16, 32)):
+        for H, W in ((4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (6, 6), (16, 32)) + OTHER_RES_MAPS:
             for Cin in (64, 128, 256, 512):
                 for Cout in (64, 128, 256, 512):
                     for taps in (1, 9):
@@ -191,12 +229,15 @@ NOT_COVERED = {
     'a BatchNorm-backward epilogue that needs the direct form: no network launch, no operator-level entry':
         {'R256_64_128.0', 'R256_64_128.1', 'R256_64_128.2', 'R64_128_128.0', 'R64_128_128.1', 'R64_128_128.2', 'R128_128_128.2', 'R128_128_64.2'},
     # A tiling the networks of the suite reach with other load modes only (its shape class has no layer with this mode: 64-channel outputs
-    # above 32768 pixels, 3 x 3 layers on the generic kernel's small tier with a pending BatchNorm, ...), or whose BatchNorm-on-load launches
-    # always bring their finalize (the 512-thread halo tiles: variants 4 / 5 run instead) or never do (the 256-thread 16 x 4 tiles, the
-    # generic small tier with 64 / 512 input channels: variants 1 / 2 run instead).  The plain variant of each
-    # runs in tests/test_gpu_conv.py::SHAPES and the load transform in the covered instances of the same kernel template.
+    # above 32768 pixels or on 256-channel row tiles, the 16 x 8 halo tiles with unequal channel counts, ...), or whose BatchNorm-on-load launches
+    # always bring their finalize (the 512-thread halo tiles and the 64-channel small tiles' data gradients: variants 4 / 5 run instead) or never
+    # do (the 256-thread 16 x 4 tiles, the generic small tier with 64 / 512 input channels: variants 1 / 2 run instead).  The plain variant of each
+    # runs in tests/test_gpu_conv.py::SHAPES and the load transform in the covered instances of the same kernel template.  (The generic small
+    # tier's 3 x 3 instances with a BatchNorm on load and no finalize, G64x64_9.1 / .2, and the 128 -> 64 row tile with BatchNorm + ReLU on load,
+    # R128_64_64.1, left this list with the 320 / 448 legs: 80 x 80 maps at chan 512 have 200 statistics rows, too many for the prologue, and
+    # chan 128 has a 128 -> 64 layer on >= 192 row tiles there.)
     'a load mode no layer of the networks of the suite has on this tiling (the plain variant and the finalize variants run)':
-        {'G128x64_1.1', 'G128x64_1.2', 'G128x64_9.1', 'G128x64_9.2', 'G64x64_1.5', 'G64x64_9.1', 'G64x64_9.2', 'R128_64_64.1', 'R256_64_64.1',
+        {'G128x64_1.1', 'G128x64_1.2', 'G128x64_9.1', 'G128x64_9.2', 'G64x64_1.5', 'R256_64_64.1',
          'R256_64_64.2', 'T16x4_128_64.4', 'T16x4_128_64.5', 'T16x4_128_64_T512.1', 'T16x4_128_64_T512.2', 'T16x8_128_64.1', 'T16x8_128_64.2',
          'T16x8_64_128.1', 'T16x8_64_128.2', 'TS4_128_64_T512.1', 'TS4_128_64_T512.2', 'TS4_64_64.2', 'TS8_128_64_T512.1', 'TS8_128_64_T512.2',
          'TS8_64_64.2'},

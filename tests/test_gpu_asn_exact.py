@@ -6,8 +6,10 @@ here every element of every conv, BatchNorm, pool+add and head tensor is held to
 
 Legs: the joint loop's size (chan 256, B 24, 256 x 256: shapes the grouped weight-gradient kernel takes); the 384 x 384 geometry at B 3
 (maps 96 / 48 / 24 / 12 / 6: ragged streaming thread counts, and a 6 x 6 top map of which the head may only average the top-left 4 x 4
-window); chan 128 at B 4; the occlusion agent at chan 256 B 24 and chan 128 B 2; the IEEE-half build on the 384 geometry in a child
-process (one storage type per process; all gradient checks in units of pa_grad_scale())."""
+window); the 320 x 320 and 448 x 448 geometries (5 x 5 and 7 x 7 top maps, the largest the agent accepts; widths 20 / 28 / 10 / 14 that fit
+no streaming row walk); chan 128 at B 4; the occlusion agent at chan 256 B 24 and chan 128 B 2; the IEEE-half build on the 384 and 448
+geometries in child processes (one storage type per process; all gradient checks in units of pa_grad_scale()).  On every top map larger
+than the window the head's input gradient outside it is exactly zero, element by element."""
 import os
 import subprocess
 import sys
@@ -31,7 +33,34 @@ def test_agent_is_exact_at_the_joint_loop_size():
 
 def test_agent_is_exact_on_the_384_geometry():
     """6 x 6 top map: the head averages its top-left 4 x 4 window and sends no gradient outside it."""
-    _ok(A.run_leg(256, 3, 384, 52))
+    _ok_with_a_window(A.run_leg(256, 3, 384, 52))
+
+
+def _ok_with_a_window(worst_fails):
+    """a leg whose top map is larger than the head's 4 x 4 window: every element of the head's input gradient outside the window is exactly
+    zero (asn_exact.outside_window counts them; run_leg also reports any as a failure)"""
+    _ok(worst_fails)
+    assert worst_fails[0]['head gradient outside the window'] == 0, worst_fails[0]
+
+
+def test_agent_is_exact_on_the_320_geometry():
+    """chan 256, B 3, 320 x 320 (maps 80 / 40 / 20 / 10 / 5): a 5 x 5 top map, the 3 x 3 layers of the two deepest levels on the generic
+    kernel (10 x 10) and one masked 8 x 8 tile (5 x 5), pool+add and the streaming backward on widths that fit no row walk (20 / 10)."""
+    _ok_with_a_window(A.run_leg(256, 3, 320, 91, expect=('group',)))
+
+
+def test_agent_is_exact_on_the_448_geometry():
+    """chan 128, B 2, 448 x 448 (maps 112 / 56 / 28 / 14 / 7): a 7 x 7 top map, the largest res the agent accepts."""
+    _ok_with_a_window(A.run_leg(128, 2, 448, 92, expect=('group',)))
+
+
+def test_agent_is_exact_on_the_448_geometry_in_the_fp16_build():
+    env = dict(os.environ, POSEADV_DTYPE='fp16')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'asn_exact.py'), '128', '2', '448', '93'], env=env,
+                       capture_output=True, text=True, timeout=900)
+    if os.environ.get('POSEADV_TEST_VERBOSE'):
+        print(r.stdout)
+    assert r.returncode == 0 and 'FP16 ASN EXACT PASSED' in r.stdout, (r.stdout + r.stderr)[-3000:]
 
 
 def test_agent_is_exact_at_chan_128():

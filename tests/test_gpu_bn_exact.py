@@ -10,7 +10,8 @@ configs[4] geometry (384 x 384: the 24 x 24 / 12 x 12 tiled 3 x 3 variants, the 
 Then the tiny-maps size at 1, 3 and 8 stacks (no inner head; a middle stack -- a plain xin<i> with a nonzero gradient arriving from the
 next stack; the configs[4] depth), 3 stacks behind a phased / warm history and in the IEEE-half build, and the step with occlusion masks
 (loss_and_backward(dropout_masks=...), the occlusion agent's training path) at 256 x 256, the smallest size with a 4 x 4 neck.  Last,
-chan 512 (64 channel groups, separate finalize launches) at the sizes of tests/test_gpu_conv_exact.py's chan-512 legs."""
+chan 512 (64 channel groups, separate finalize launches) at the sizes of tests/test_gpu_conv_exact.py's chan-512 legs, and the input
+resolutions 320, 448, 192 and 64 with that file's arguments (map widths that fit no streaming row walk, necks of 1 ... 49 pixels)."""
 import os
 import subprocess
 import sys
@@ -135,6 +136,59 @@ def test_every_bn_pool_merge_and_cell_mask_is_exact_at_chan_512_in_a_masked_step
     """2 stacks, chan 512, B 2, 256 x 256 with occlusion masks: the cell mask's forward and backward launches (with their statistics
     epilogue) and the masked merges at 64 channel groups."""
     _leg(2, 512, 2, 256, 74, masks=740)
+
+
+# ---- input resolutions other than 128 / 256 / 384: the legs of tests/test_gpu_conv_exact.py, argument for argument.  The statistics rows
+# come from the kernels named there (64-pixel rows of the generic kernel on the 10 x 10 / 14 x 14 maps, one row per masked 8 x 8 workgroup
+# of two images on the 5 x 5 / 7 x 7 / 3 x 3 / 1 x 1 necks).  The backward streaming launches (csrc/launch_plan.h: blockDim and the
+# (W / 2) * (C / 8) items of a row must divide one another, over the tried sizes 512 / 256 / 384 / 192 / 128) fit the row walk at chan 256
+# with 256 threads on the 80- and 112-wide maps (1280 / 1792 items) and with 128 on 40 / 56 (640 / 896), at chan 128 with 128 threads on
+# 80 / 112 (640 / 896); 20 / 28 / 10 / 14 at chan 256 (320 / 448 / 160 / 224 items) and 40 / 56 / 20 / 28 / 10 / 14 at chan 128 fit no
+# tried size and go to the generic max-pool and upsample-add kernels.  tests/bn_exact.py re-derives the depth D for these shapes:
+# nothing changes.
+def test_every_bn_pool_and_merge_is_exact_on_the_320_geometry():
+    """2 stacks, chan 256, B 2, 320 x 320 (maps 80 / 40 / 20 / 10 / 5): the upsample-add backward of the 80 x 80 merges runs as a launch of
+    its own behind the row-tile data gradient (the fused form is refused: W % 32 != 0)."""
+    _leg(2, 256, 2, 320, 81)
+
+
+def test_every_bn_pool_and_merge_is_exact_on_the_448_geometry_at_batch_1():
+    """2 stacks, chan 128, B 1, 448 x 448 (maps 112 / 56 / 28 / 14 / 7): 49 values per channel at the neck."""
+    _leg(2, 128, 1, 448, 82)
+
+
+def test_every_bn_pool_and_merge_is_exact_on_the_192_geometry_at_batch_5():
+    """2 stacks, chan 128, B 5, 192 x 192 (maps 48 / 24 / 12 / 6 / 3): 45 values per channel at the 3 x 3 neck, the last pool reads 6 x 6."""
+    _leg(2, 128, 5, 192, 83)
+
+
+def test_every_bn_pool_and_merge_is_exact_on_the_64_geometry():
+    """2 stacks, chan 256, B 4, 64 x 64 (maps 16 / 8 / 4 / 2 / 1): BatchNorms over 4 values per channel at the 1 x 1 neck (biased and
+    unbiased variance differ by a third), the last pool reads one 2 x 2 window per image.  B 3 -- three values per channel -- was
+    DEGENERATE with this seed: the pooled, ReLU'd values of down4's input lie so close together in some channels (|mean| / sigma above
+    about 45) that the invstd interval of hg.0.down4.0.bn1, hg.0.down4.0.bn3 and hg.1.down4.0.bn1 was 1.64 - 1.77 % wide, a property of the
+    operands and not of the kernels; B 4 is the smallest batch that is not (widest interval 0.26 %; B 5: 0.28 %, B 6: 0.10 %).
+    residual1's 32 x 32 maps are 64 row tiles, below the 192 the row-tile kernel takes: no dz3 is stored, the 3 x 3 tile launches store dz2."""
+    assert not _stores_dz(4, 32, 128, 64, 1) and _stores_dz(4, 32, 64, 64, 9)
+    _leg(2, 256, 4, 64, 84, stored_expected=('.x2',))
+
+
+def test_every_bn_pool_and_merge_is_exact_at_chan_512_on_the_320_geometry():
+    """1 stack, chan 512, B 2, 320 x 320: 64 channel groups on maps of width 80 ... 5, separate finalize launches; residual1's conv3 data
+    gradient (160 x 160: 800 row tiles) stores dz3 as on the 256 x 256 legs."""
+    assert _stores_dz(2, 160, 128, 64, 1) and _stores_dz(2, 160, 64, 64, 9)
+    _leg(1, 512, 2, 320, 85)
+
+
+@pytest.mark.parametrize('history', ('warm', 'graph'))
+def test_every_bn_pool_and_merge_is_exact_after_a_history_on_the_320_geometry(history):
+    """chan 128, B 2, 320 x 320 behind optimizer steps and in a graph replay."""
+    _leg(2, 128, 2, 320, 86, history=history)
+
+
+def test_every_bn_pool_and_merge_is_exact_on_the_320_geometry_in_the_fp16_build():
+    """The IEEE-half library at chan 128, B 2, 320 x 320, in a child process."""
+    _fp16_child(['2', '128', '2', '320', '87'])
 
 
 def test_every_bn_pool_and_merge_is_exact_at_chan_512_in_the_fp16_build():

@@ -6,7 +6,8 @@ a failure.
 
 Legs (as tests/test_gpu_bn_exact.py): BASELINE configs[1] at full size; the configs[4] geometry (maps 96 / 48 / 24 / 12 / 6) at B 3; tiny
 maps; the IEEE-half build on the configs[4] geometry in a child process; 1, 3 and 8 stacks; the step with occlusion masks; chan 512 at
-the smallest batch that reaches each tile of the generic kernel.  Then every shape of tests/test_gpu_conv.SHAPES through pa_conv2d
+the smallest batch that reaches each tile of the generic kernel; the input resolutions 320, 448, 192 and 64 (odd and 1 x 1 necks, 10 x 10 /
+14 x 14 maps on the generic kernel, B 1 and B 5).  Then every shape of tests/test_gpu_conv.SHAPES through pa_conv2d
 in all three modes, and the split-count mirror against the library's workspace sizes.
 
 What a leg guards is geometric only: it has the map sizes that conv3x3_tile.hip's dispatch sends to the tiled 24 x 24 / 12 x 12 and masked
@@ -137,6 +138,62 @@ def test_every_conv_is_exact_at_chan_512_in_a_masked_step():
     _leg(2, 512, 2, 256, 74, expect=('group',), masks=740)
 
 
+# ---- input resolutions other than 128 / 256 / 384 (every res % 64 == 0 is accepted): map sides 80 / 40 / 20 / 10 / 5 (320), 112 / 56 / 28 /
+# 14 / 7 (448), 48 / 24 / 12 / 6 / 3 (192) and 16 / 8 / 4 / 2 / 1 (64).  What each side reaches, by csrc/conv_plan.h (asserted through the
+# planner's query, not re-derived; tests/test_conv_plan_cpu.py::test_documented_examples_of_the_other_resolutions states the rules): the
+# 3 x 3 layers on 10 x 10 and 14 x 14 maps take the generic K-stepping kernel with the net's BatchNorm loads (a side above 8 that is no
+# multiple of 4: its 64-pixel M tiles wrap image rows of width 10 / 14); 5 x 5, 7 x 7, 3 x 3 and 1 x 1 maps are one masked 8 x 8 tile, two
+# images per workgroup; 40 / 56 take the 8 x 8 halo tiles, 20 / 28 the 4 x 4 ones.  The weight-gradient plans (the mirror, wgrad_plan) have
+# ragged last tiles (1 * 56 * 56 pixels = 24.5 tiles of 128) and generic plans of fewer pixels than one 32-pixel MFMA step (M = 3 ... 49).
+def _path3(B, H, Cin):
+    """(path, tiling without its channel suffix) of a 3 x 3 forward launch of the net on an H x H map with Cin = Cout"""
+    d = Q.plan(B, H, H, Cin, Cin, 9, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)
+    return d['path'], d['tiling'].split('_')[0]
+
+
+def test_every_conv_is_exact_on_the_320_geometry():
+    """2 stacks, chan 256, B 2, 320 x 320 (maps 80 / 40 / 20 / 10 / 5).  The upsample-add data gradient on the 80 x 80 maps (2 * 80 * 80 / 64 =
+    200 row tiles, W % 32 != 0) is refused with its second output and re-planned without it (Net::conv_dgrad)."""
+    assert [_path3(2, H, 128) for H in (40, 20, 10, 5)] == [(Q.TILE3, 'TS8'), (Q.TILE3, 'TS4'), (Q.GENERIC, 'G64x64'), (Q.TILE3, 'TS8')]
+    up = dict(in_=Q.LIN2, a1=Q.PLAIN, ep=Q.OUT_PLAIN)
+    assert Q.plan(2, 80, 80, 128, 256, 1, ep2=Q.OUT_BWD, flags=Q.OUT2, **up)['path'] == Q.REFUSED and Q.plan(2, 80, 80, 128, 256, 1, **up)['path'] == Q.ROW
+    _leg(2, 256, 2, 320, 81, expect=('group',))
+
+
+def test_every_conv_is_exact_on_the_448_geometry_at_batch_1():
+    """2 stacks, chan 128, B 1, 448 x 448 (maps 112 / 56 / 28 / 14 / 7): one image, 64 mid channels, ragged weight-gradient tiles."""
+    assert [_path3(1, H, 64) for H in (56, 28, 14, 7)] == [(Q.TILE3, 'TS8'), (Q.TILE3, 'TS4'), (Q.GENERIC, 'G64x64'), (Q.TILE3, 'TS8')]
+    assert X.wgrad_plan(1, 56, 56, 64, 128, 1)[:4] == ('tile', 128, 64, 25) and 1 * 56 * 56 % 128 != 0
+    _leg(2, 128, 1, 448, 82, expect=('group',))
+
+
+def test_every_conv_is_exact_on_the_192_geometry_at_batch_5():
+    """2 stacks, chan 128, B 5, 192 x 192 (maps 48 / 24 / 12 / 6 / 3): an odd batch above 3, the 3 x 3 neck (45 pixels)."""
+    assert _path3(5, 3, 64) == (Q.TILE3, 'TS8') and Q.plan(5, 3, 3, 64, 64, 9, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)['gx'] == 3
+    assert X.wgrad_plan(5, 3, 3, 64, 64, 9)[:2] == ('generic', 64) and X.wgrad_plan(5, 3, 3, 64, 64, 9).splits == 1
+    _leg(2, 128, 5, 192, 83, expect=('group',))
+
+
+def test_every_conv_is_exact_on_the_64_geometry():
+    """2 stacks, chan 256, B 4, 64 x 64 (maps 16 / 8 / 4 / 2 / 1): the 1 x 1 neck, where only the centre tap of a 3 x 3 layer meets a
+    pixel and a BatchNorm normalises one value per image.  B 4 is the smallest batch whose operands leave the bounds of
+    tests/test_gpu_bn_exact.py's leg of the same arguments meaningful (B 3 was degenerate there); the two files keep the same arguments."""
+    assert _path3(4, 1, 128) == (Q.TILE3, 'TS8') and Q.plan(4, 1, 1, 128, 128, 9, in_=Q.BNRELU, ep=Q.OUT_STATS, flags=Q.BIAS)['gx'] == 2
+    _leg(2, 256, 4, 64, 84)
+
+
+def test_every_conv_is_exact_at_chan_512_on_the_320_geometry():
+    """1 stack, chan 512, B 2, 320 x 320: the generic kernel at K = 512 / 2304 on maps of width 80 ... 5 (M = 12800 ... 50)."""
+    assert {_tier(2, H, 512, 256) for H in (80, 40, 20, 10, 5)} == {'G64x64_1'} and {_tier(2, H, 256, 256, 9) for H in (80, 40, 20, 10, 5)} == {'G64x64_9'}
+    _leg(1, 512, 2, 320, 85, expect=('group',))
+
+
+@pytest.mark.parametrize('history', ('warm', 'graph'))
+def test_every_conv_is_exact_after_a_history_on_the_320_geometry(history):
+    """chan 128, B 2, 320 x 320 behind optimizer steps (repacked weight copies) and in a graph replay."""
+    _leg(2, 128, 2, 320, 86, history=history)
+
+
 def _fp16_child(args):
     env = dict(os.environ, POSEADV_DTYPE='fp16')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'conv_exact.py')] + args, env=env, capture_output=True, text=True, timeout=900)
@@ -157,6 +214,11 @@ def test_every_conv_is_exact_in_a_masked_step_in_the_fp16_build():
 def test_every_conv_is_exact_at_chan_512_in_the_fp16_build():
     """The IEEE-half library on the chan-512 tiny-maps leg (2 stacks, B 2, 128 x 128): the generic <64,64> instance at K = 512 / 2304."""
     _fp16_child(['2', '512', '2', '128', '75'])
+
+
+def test_every_conv_is_exact_on_the_320_geometry_in_the_fp16_build():
+    """The IEEE-half library at chan 128, B 2, 320 x 320 (maps 80 / 40 / 20 / 10 / 5)."""
+    _fp16_child(['2', '128', '2', '320', '87'])
 
 
 def test_every_conv_is_exact_after_warm_steps_in_the_fp16_build():
