@@ -16,6 +16,7 @@ void pa_set_error_msg(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg
 
 struct pa_net { Net n; };
 #define ST(s) reinterpret_cast<hipStream_t>(s)
+#undef TRY       // (net.h's plain form; at the C boundary a failure also leaves a message)
 #define TRY(x) do { int _r = (x); if (_r) { if (!g_err[0]) pa_set_error("kernel launch", (hipError_t)_r, __FILE__, __LINE__); return _r; } } while (0)
 // argument checks of the pose-library operators: decided on the host before any device call, the message names the argument
 #define NEED_PTR(fn, p) do { if (!(p)) { pa_set_error_msg(fn ": " #p " is NULL"); return 1; } } while (0)

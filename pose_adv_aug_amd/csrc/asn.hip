@@ -4,11 +4,6 @@
 // the half-hourglass forward that produces those features (:300-304) and the KL loss of
 // joint-train-pose-s-r-agent.py:399-407.
 #include "net.h"
-#include <string.h>
-
-#define TRY(x) do { int _r = (x); if (_r) return _r; } while (0)
-
-static PaEpilogue ep_plain() { PaEpilogue e; memset(&e, 0, sizeof e); e.mode = PA_OUT_PLAIN; return e; }
 
 // ------------------------------------------------------------------------------------------------
 // out = maxpool2x2(hi) + lo        (reference :404-415: x = maxpool(x); x = x + skip)

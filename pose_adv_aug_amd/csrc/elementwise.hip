@@ -29,14 +29,11 @@ static void fin_launch(void (*kernel)(P...), dim3 grid, int threads, hipStream_t
 // FC channels x (FT / FC) row slices, float2 loads, LDS tree over the slices.  Result in LDS sums[FC][2].
 // FC = 8: 16-32 workgroups per BatchNorm (the kernel is pure latency: launch + row loads in batches + tree; 32 channels per workgroup
 // took 6 us; FC = 4 -- every common row count in ONE batch of loads, twice the workgroups -- measured 0.03 ms per step slower, round 4).
-// workgroup shape of the finalize launches: FT threads = FC channels x FT / FC row slices
-template <class F>
-static void fin_dispatch(F f) {
-    // 512 threads (8 channels x 64 row slices): measured 6.44 - 6.49 ms per step against 6.50 - 6.54 with 1024-thread workgroups (three
-    // interleaved pairs; 256 threads, or 4 channels per workgroup: the same as 512 / 8) -- a 1024-thread workgroup has to find a whole CU's
-    // worth of wave slots next to the other queues' kernels, and the launch is all these kernels are
-    f(std::integral_constant<int, 512>{}, std::integral_constant<int, 8>{});
-}
+// workgroup shape of the finalize launches: FIN_T threads = FIN_C channels x FIN_T / FIN_C row slices.
+// 512 threads (8 channels x 64 row slices): measured 6.44 - 6.49 ms per step against 6.50 - 6.54 with 1024-thread workgroups (three
+// interleaved pairs; 256 threads, or 4 channels per workgroup: the same as 512 / 8) -- a 1024-thread workgroup has to find a whole CU's
+// worth of wave slots next to the other queues' kernels, and the launch is all these kernels are
+constexpr int FIN_T = 512, FIN_C = 8;
 template <int FT, int FC>
 __device__ __forceinline__ void reduce_partial_rows(const float* part, int rows, int C, int c0, float (*sums)[2]) {
     constexpr int SL = FT / FC;
@@ -113,47 +110,29 @@ __device__ __forceinline__ void reduce_partial_rows(const float* part, int rows,
     __syncthreads();
 }
 
-template <int FT, int FC>
-__global__ __launch_bounds__(FT) void bn_finalize_kernel(const float* stats, int rows, const float* gamma, const float* beta,
-                                                           float* rmean, float* rvar, float* scale, float* shift, float* mean,
-                                                           float* invstd, int C, float count, float momentum, float eps,
-                                                           int update_running) {
+// one finalize as PaBnFin describes it (bn_fin.h): forward here, backward below
+__global__ __launch_bounds__(FIN_T) void bn_fin_fwd_kernel(PaBnFin f, int C) {
     PA_SET_ELT_PRIO();
-    __shared__ float sums[FC][2];
-    const int c0 = blockIdx.x * FC;
+    __shared__ float sums[FIN_C][2];
+    const int c0 = blockIdx.x * FIN_C;
     // the channel's parameters are requested BEFORE the reduction (after it they were one more dependent memory round trip of a kernel that
     // is nothing but round trips)
-    const bool mine = threadIdx.x < FC && c0 + (int)threadIdx.x < C;
+    const bool mine = threadIdx.x < FIN_C && c0 + (int)threadIdx.x < C;
     float g = 0.f, bt = 0.f, rm = 0.f, rv = 0.f;
     if (mine) {
-        g = gamma[c0 + threadIdx.x]; bt = beta[c0 + threadIdx.x];
-        if (update_running) { rm = rmean[c0 + threadIdx.x]; rv = rvar[c0 + threadIdx.x]; }
+        g = f.gamma[c0 + threadIdx.x]; bt = f.beta[c0 + threadIdx.x];
+        if (f.update_running) { rm = f.rmean[c0 + threadIdx.x]; rv = f.rvar[c0 + threadIdx.x]; }
     }
-    reduce_partial_rows<FT, FC>(stats, rows, C, c0, sums);
+    reduce_partial_rows<FIN_T, FIN_C>(f.stats, f.rows, C, c0, sums);
     if (!mine) return;
     const int c = c0 + threadIdx.x;
     float s, sh, mu, is, var;
-    pa_bn_fwd_consts(sums[threadIdx.x][0], sums[threadIdx.x][1], count, eps, g, bt, s, sh, mu, is, var);
-    scale[c] = s;
-    shift[c] = sh;
-    mean[c] = mu;
-    invstd[c] = is;
-    if (update_running) {
-        pa_bn_running(mu, var, count, momentum, rm, rv);
-        rmean[c] = rm; rvar[c] = rv;
+    pa_bn_fwd_consts(sums[threadIdx.x][0], sums[threadIdx.x][1], f.count, f.eps, g, bt, s, sh, mu, is, var);
+    f.scale[c] = s; f.shift[c] = sh; f.mean[c] = mu; f.invstd[c] = is;
+    if (f.update_running) {
+        pa_bn_running(mu, var, f.count, f.momentum, rm, rv);
+        f.rmean[c] = rm; f.rvar[c] = rv;
     }
-}
-
-int pa_launch_bn_finalize(const float* stats, int rows, const float* gamma, const float* beta, float* rmean, float* rvar,
-                          float* scale, float* shift, float* mean, float* invstd, int C, float count,
-                          float momentum, float eps, int update_running, hipStream_t st) {
-    if (C & 1) { pa_set_error_msg("BatchNorm finalize: the statistics rows are read as 16-byte channel pairs -- C must be even (the networks pad to 64)"); return 1; }
-    fin_dispatch([&](auto ft, auto fc) {
-        constexpr int FT = decltype(ft)::value, FC = decltype(fc)::value;
-        fin_launch(bn_finalize_kernel<FT, FC>, dim3((C + FC - 1) / FC), FT, st, stats, rows, gamma, beta, rmean, rvar, scale, shift, mean, invstd, C, count,
-                   momentum, eps, update_running);
-    });
-    return (int)hipGetLastError();
 }
 
 __global__ void bn_eval_kernel(const PaBnEvalJob* jobs, float eps) {
@@ -172,73 +151,42 @@ int pa_launch_bn_eval(const PaBnEvalJob* jobs_dev, int njobs, float eps, hipStre
 }
 
 // dx = s*(dz - S1/M - xhat*S2/M) = kA*dz + kB*x + kC    (per channel)
-template <int FT, int FC>
-__global__ __launch_bounds__(FT) void bn_bwd_finalize_kernel(const float* bstats, int rows, const float* scale, const float* mean,
-                                                               const float* invstd, float* kA, float* kB, float* kC,
-                                                               float* dgamma, float* dbeta, int C, float count) {
+// one BatchNorm-backward finalize (gridDim.y == 1) or two in one launch (blockIdx.y picks the layer: the upsample-add backward feeds two at once)
+__global__ __launch_bounds__(FIN_T) void bn_fin_bwd_kernel(PaBnFin f0, int C0, PaBnFin f1, int C1) {
     PA_SET_ELT_PRIO();
-    __shared__ float sums[FC][2];
-    const int c0 = blockIdx.x * FC;
-    const bool mine = threadIdx.x < FC && c0 + (int)threadIdx.x < C;
-    float sc = 0.f, is = 0.f, mu = 0.f;              // (requested before the reduction, see bn_finalize_kernel)
-    if (mine) { sc = scale[c0 + threadIdx.x]; is = invstd[c0 + threadIdx.x]; mu = mean[c0 + threadIdx.x]; }
-    reduce_partial_rows<FT, FC>(bstats, rows, C, c0, sums);
+    const PaBnFin& f = blockIdx.y == 0 ? f0 : f1;
+    const int C = blockIdx.y == 0 ? C0 : C1;
+    __shared__ float sums[FIN_C][2];
+    const int c0 = blockIdx.x * FIN_C;
+    if (c0 >= C) return;
+    const bool mine = threadIdx.x < FIN_C && c0 + (int)threadIdx.x < C;
+    float sc = 0.f, is = 0.f, mu = 0.f;              // (requested before the reduction, see bn_fin_fwd_kernel)
+    if (mine) { sc = f.scale[c0 + threadIdx.x]; is = f.invstd[c0 + threadIdx.x]; mu = f.mean[c0 + threadIdx.x]; }
+    reduce_partial_rows<FIN_T, FIN_C>(f.stats, f.rows, C, c0, sums);
     if (!mine) return;
     const int c = c0 + threadIdx.x;
     float S1 = sums[threadIdx.x][0], S2 = sums[threadIdx.x][1];
     float ka, kb, kc;
-    pa_bn_bwd_consts(S1, S2, count, sc, is, mu, ka, kb, kc);
-    kA[c] = ka; kB[c] = kb; kC[c] = kc;
-    if (dgamma) dgamma[c] = S2;
-    if (dbeta) dbeta[c] = S1;
+    pa_bn_bwd_consts(S1, S2, f.count, sc, is, mu, ka, kb, kc);
+    f.kA[c] = ka; f.kB[c] = kb; f.kC[c] = kc;
+    if (f.dgamma) f.dgamma[c] = S2;
+    if (f.dbeta) f.dbeta[c] = S1;
 }
 
-// two BatchNorm-backward finalizes in one launch (blockIdx.y picks the layer): the upsample-add backward feeds two layers at once
-struct BwdFinArgs { const float* bstats; int rows; const float* scale; const float* mean; const float* invstd; float *kA, *kB, *kC, *dgamma, *dbeta; int C; float count; };
-template <int FT, int FC>
-__global__ __launch_bounds__(FT) void bn_bwd_finalize2_kernel(BwdFinArgs a0, BwdFinArgs a1) {
-    PA_SET_ELT_PRIO();
-    const BwdFinArgs& a = blockIdx.y == 0 ? a0 : a1;
-    __shared__ float sums[FC][2];
-    const int c0 = blockIdx.x * FC;
-    if (c0 >= a.C) return;
-    const bool mine = threadIdx.x < FC && c0 + (int)threadIdx.x < a.C;
-    float sc = 0.f, is = 0.f, mu = 0.f;
-    if (mine) { sc = a.scale[c0 + threadIdx.x]; is = a.invstd[c0 + threadIdx.x]; mu = a.mean[c0 + threadIdx.x]; }
-    reduce_partial_rows<FT, FC>(a.bstats, a.rows, a.C, c0, sums);
-    if (!mine) return;
-    const int c = c0 + threadIdx.x;
-    float S1 = sums[threadIdx.x][0], S2 = sums[threadIdx.x][1];
-    float ka, kb, kc;
-    pa_bn_bwd_consts(S1, S2, a.count, sc, is, mu, ka, kb, kc);
-    a.kA[c] = ka; a.kB[c] = kb; a.kC[c] = kc;
-    if (a.dgamma) a.dgamma[c] = S2;
-    if (a.dbeta) a.dbeta[c] = S1;
-}
+static const char* const fin_odd_c = "BatchNorm finalize: the statistics rows are read as 16-byte channel pairs -- C must be even (the networks pad to 64)";
 
-int pa_launch_bn_bwd_finalize2(const float* bs0, int rows0, const float* sc0, const float* mu0, const float* is0, float* kA0, float* kB0, float* kC0,
-                               float* dg0, float* db0, int C0, float cnt0,
-                               const float* bs1, int rows1, const float* sc1, const float* mu1, const float* is1, float* kA1, float* kB1, float* kC1,
-                               float* dg1, float* db1, int C1, float cnt1, hipStream_t st) {
-    BwdFinArgs a0 = {bs0, rows0, sc0, mu0, is0, kA0, kB0, kC0, dg0, db0, C0, cnt0};
-    BwdFinArgs a1 = {bs1, rows1, sc1, mu1, is1, kA1, kB1, kC1, dg1, db1, C1, cnt1};
-    if ((C0 | C1) & 1) { pa_set_error_msg("BatchNorm finalize: C must be even (16-byte channel pairs)"); return 1; }
-    const int cm = C0 > C1 ? C0 : C1;
-    fin_dispatch([&](auto ft, auto fc) {
-        constexpr int FT = decltype(ft)::value, FC = decltype(fc)::value;
-        fin_launch(bn_bwd_finalize2_kernel<FT, FC>, dim3((cm + FC - 1) / FC, 2), FT, st, a0, a1);
-    });
+int pa_launch_bn_fin(const PaBnFin& f, int C, hipStream_t st) {
+    if (C & 1) { pa_set_error_msg(fin_odd_c); return 1; }
+    const dim3 grid((C + FIN_C - 1) / FIN_C);
+    if (f.bwd) fin_launch(bn_fin_bwd_kernel, grid, FIN_T, st, f, C, f, C);      // (one layer: gridDim.y == 1)
+    else fin_launch(bn_fin_fwd_kernel, grid, FIN_T, st, f, C);
     return (int)hipGetLastError();
 }
 
-int pa_launch_bn_bwd_finalize(const float* bstats, int rows, const float* scale, const float* mean, const float* invstd,
-                              float* kA, float* kB, float* kC, float* dgamma, float* dbeta, int C, float count,
-                              hipStream_t st) {
-    if (C & 1) { pa_set_error_msg("BatchNorm finalize: the statistics rows are read as 16-byte channel pairs -- C must be even (the networks pad to 64)"); return 1; }
-    fin_dispatch([&](auto ft, auto fc) {
-        constexpr int FT = decltype(ft)::value, FC = decltype(fc)::value;
-        fin_launch(bn_bwd_finalize_kernel<FT, FC>, dim3((C + FC - 1) / FC), FT, st, bstats, rows, scale, mean, invstd, kA, kB, kC, dgamma, dbeta, C, count);
-    });
+int pa_launch_bn_fin2(const PaBnFin& a, int Ca, const PaBnFin& b, int Cb, hipStream_t st) {
+    if (!a.bwd || !b.bwd) { pa_set_error_msg("BatchNorm finalize: the pair launch takes two backward finalizes"); return 1; }
+    if ((Ca | Cb) & 1) { pa_set_error_msg(fin_odd_c); return 1; }
+    fin_launch(bn_fin_bwd_kernel, dim3(((Ca > Cb ? Ca : Cb) + FIN_C - 1) / FIN_C, 2), FIN_T, st, a, Ca, b, Cb);
     return (int)hipGetLastError();
 }
 

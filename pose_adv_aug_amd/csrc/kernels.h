@@ -80,22 +80,13 @@ struct PaRedList { int idx[PA_RED_LIST_MAX]; };
 int pa_launch_wgrad_reduce_list(const PaWgradReduceJob* jobs_dev, const int* idx, int n, int max_elems, hipStream_t st);      // any n <= 24 jobs of the table
 
 // ---- BatchNorm bookkeeping
-// forward: partial rows stats[rows][C][2] (sum, sumsq; over `count` values in total) -> scale/shift/mean/invstd,
-// running stats update
-int pa_launch_bn_finalize(const float* stats, int rows, const float* gamma, const float* beta, float* rmean, float* rvar,
-                          float* scale, float* shift, float* mean, float* invstd, int C, float count,
-                          float momentum, float eps, int update_running, hipStream_t st);
+// the finalize as a launch of its own, described by PaBnFin (bn_fin.h) like the consumer-prologue form, over C (even) channels: forward
+// (rows of sum, sumsq -> scale/shift/mean/invstd, running stats update) or backward (rows of sum dz, sum dz*xhat -> LIN2 coefficients, dgamma, dbeta)
+int pa_launch_bn_fin(const PaBnFin& f, int C, hipStream_t st);
+int pa_launch_bn_fin2(const PaBnFin& a, int Ca, const PaBnFin& b, int Cb, hipStream_t st);      // two backward finalizes in one launch
 // eval: scale/shift from running stats, for `n` BatchNorms described by a device table
 struct PaBnEvalJob { const float* gamma; const float* beta; const float* rmean; const float* rvar; float* scale; float* shift; int C; };
 int pa_launch_bn_eval(const PaBnEvalJob* jobs_dev, int njobs, float eps, hipStream_t st);
-// backward: partial rows bstats[rows][C][2] (sum dz, sum dz*xhat) -> LIN2 coefficients (A,B,C), dgamma, dbeta
-int pa_launch_bn_bwd_finalize2(const float* bs0, int rows0, const float* sc0, const float* mu0, const float* is0, float* kA0, float* kB0, float* kC0,
-                               float* dg0, float* db0, int C0, float cnt0,
-                               const float* bs1, int rows1, const float* sc1, const float* mu1, const float* is1, float* kA1, float* kB1, float* kC1,
-                               float* dg1, float* db1, int C1, float cnt1, hipStream_t st);
-int pa_launch_bn_bwd_finalize(const float* bstats, int rows, const float* scale, const float* mean, const float* invstd,
-                              float* kA, float* kB, float* kC, float* dgamma, float* dbeta, int C, float count,
-                              hipStream_t st);
 
 // ---- pooling / upsampling (NHWC bf16).  These launches, pa_launch_ep_apply and pa_launch_cell_mask take their geometry from pa_elt_plan
 // (launch_plan.h), which also refuses what the kernels cannot do: a statistics epilogue needs C / 8 a power of two <= 64

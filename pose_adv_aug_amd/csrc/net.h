@@ -3,11 +3,16 @@
 // needs.  Mirrors the reference module tree (models/asn_stacked_hg.py) name-for-name so that
 // checkpoints interchange.  Internal header; the public C ABI is include/poseadv.h.
 #pragma once
+#include <string.h>
 #include <string>
 #include <vector>
 #include "common.h"
 #include "kernels.h"
 #include "pose_ops.h"
+#include "work_model.h"
+
+#define TRY(x) do { int _r = (x); if (_r) return _r; } while (0)
+inline PaEpilogue ep_plain() { PaEpilogue e; memset(&e, 0, sizeof e); e.mode = PA_OUT_PLAIN; return e; }
 
 struct Arena {
     char* base = nullptr;
@@ -66,13 +71,7 @@ struct Act {                 // NHWC bf16 activation; `bn` != null means BatchNo
 
 struct Net;
 
-// optional per-launch timing of the MFMA kernels with HIP events (bench.py's roofline object)
-// classes 0-5: the maps with >= PA_PROF_LOW_M pixels (32 x 32 and larger at batch 24: bandwidth- / MFMA-shaped launches); 9-11: every
-// convolution launch below that (16 x 16 ... 4 x 4: bound by launch / staging / epilogue LATENCY, DESIGN.md section 4 -- averaging them
-// into the classes above says nothing about either)
-enum { PA_PROF_FWD1 = 0, PA_PROF_FWD3, PA_PROF_DGRAD1, PA_PROF_DGRAD3, PA_PROF_WGRAD1, PA_PROF_WGRAD3, PA_PROF_STEM_FWD,
-       PA_PROF_STEM_WGRAD, PA_PROF_LOWRES_FWD, PA_PROF_LOW_FWD, PA_PROF_LOW_DGRAD, PA_PROF_LOW_WGRAD, PA_PROF_NCLS };
-#define PA_PROF_LOW_M 16384
+// optional per-launch timing of the MFMA kernels with HIP events (bench.py's roofline object); the classes: work_model.h
 struct ProfEntry { hipEvent_t e0, e1; int cls; double bytes, flops; };
 struct Prof {
     bool on = false;
@@ -194,7 +193,7 @@ struct Net {
     hipEvent_t ev_wdone;
     // weight-gradient launches are collected and flushed in groups: ONE event record on the producing stream per group
     // (an event record between two kernels of a queue costs a 15-20 us bubble on it: ~100 records per step were 1.5 ms)
-    struct PendingWgrad { PaWgradArgs a; int cls; double bytes, flops; bool stem; int job_wgs; ConvLayer* c; };      // job_wgs: workgroups as a job of a group launch (0: launched alone)
+    struct PendingWgrad { PaWgradArgs a; PaWork w; bool stem; int job_wgs; ConvLayer* c; };      // job_wgs: workgroups as a job of a group launch (0: launched alone)
     // with a weight-gradient stream, the slabs of a group are summed right behind it on that stream (part of them still in the 256 MB
     // Infinity Cache) instead of by one 280 us reduction on the main stream at the end of the step
     std::vector<PendingWgrad> pending_wgrads;
@@ -210,13 +209,14 @@ struct Net {
     int record_join(int k);                    // mark the end of that branch
     int wait_join(int k);                      // st waits for that mark
     Prof prof;
-    // bytes this design moves (pa_net_design_bytes): operands of every launch since begin_step(), counted once per launch
+    // bytes this design moves (pa_net_design_bytes): operands of every launch since begin_step(), counted once per launch (work_model.h)
     double dbytes_rd = 0, dbytes_wr = 0;
-    static double opb(const PaOperand& o, double elems) {
-        if (o.mode == PA_LD_POOL) return (2.0 + 1.0) * elems / 4 + (o.q ? 2.0 * elems : 0.0);      // pooled gradient + byte map, plain addend
-        return o.mode == PA_LD_NONE ? 0.0 : (o.mode == PA_LD_LIN2 ? 4.0 : 2.0) * elems;
-    }
-    void cnt(double rd, double wr) { dbytes_rd += rd; dbytes_wr += wr; }
+    void cnt(const PaWork& w) { dbytes_rd += w.rd; dbytes_wr += w.wr; }
+    // PA_ABLATE (tuning builds; constant false in the release build): is this launch left out?  kind: PA_L_*, the table of the bits in net.hip
+    bool ablated(int kind, int k = 0, int H = 1 << 30, long M = 0) const;
+    // ONE launch: its design bytes counted, its profile entry (w.cls >= 0) around launch() on `st`.  skip: the instrument leaves the launch
+    // out (the entry stays, 0 is returned) -- its bytes are then counted only where count_skipped says the site always did
+    template <class F> int account(const PaWork& w, F launch, bool skip = false, bool count_skipped = true);
     // forward + loss + backward of the training step captured ONCE into a HIP graph (fork / join events of the side and
     // weight-gradient streams become graph edges) and replayed: pa_hg_train_step with use_graph
     hipGraph_t step_graph = nullptr; hipGraphExec_t step_exec = nullptr; int step_key = -1;
@@ -235,7 +235,6 @@ struct Net {
     std::vector<ConvLayer> outc, forth, inc;
     bf16* img4 = nullptr;
     Act a0, pool0;
-    bf16* pool0grad_unused = nullptr;
     std::vector<Act> lin_out, xin;                 // xin[i] = input of stack i
     std::vector<float*> heat; std::vector<bf16*> heat64, dheat64, dheat_in, forth_tmp, lgrad_tmp;
     double* pts_dev = nullptr;                     // [B][16][2] heat-map coords (caller provided per step)
@@ -307,6 +306,9 @@ struct Net {
     bool fin_consumer_ok(const ConvLayer& c, int B, int H, int W, bool dgrad) const;
     PaBnFin fin_fwd(const BNLayer& b, int M) const;
     PaBnFin fin_bwd(const BNLayer& b, int M) const;
+    bool fin_can_wait(const BNLayer* bn, bool defer, bool bwd) const {      // this BatchNorm's forward / backward finalize can wait for its consumer
+        return bn && defer && (bwd ? bn->bstat_rows : bn->stat_rows) > 0 && (bwd ? bn->bstat_rows : bn->stat_rows) <= fin_rows_max;
+    }
     int finish_grad_or_defer(const Act& a, bool defer);
     int finish_grad2_or_defer(const Act& a, bool defer_a, const Act& b, bool defer_b);
     bool x3_fin_ok(const Residual& r, const Act& in) const;     // can r.x3's backward finalize ride in conv3's data gradient?

@@ -3,21 +3,45 @@
 // hand-written backward and gradient reduction.  See net.h.
 #include "net.h"
 #include <stdio.h>
-#include <string.h>
 
-// PA_ABLATE=<mask> (tuning builds only; results are WRONG, timing bounds only): 1 no slab reductions, 2 no weight-gradient
-// launches, 4 no BatchNorm finalize launches, 8 no 3x3 convolutions, 16 no 1x1 data gradients; 1024 no upsample-add backward, 2048 no
-// pooling backward, 4096 no pooling / upsample-add forward (bounds of what fusing them into their neighbours can return)
-static int ablate() { return pa_tuning().ablate; }
-// bits 128 / 256 / 512: forward convolutions + finalize / data gradients + backward finalize / weight gradients of maps up to
-// PA_ABLATE_H (default 8) pixels high are skipped: what the low-resolution stretch costs the step at most (wrong results)
-static int ablate_h() { return pa_tuning().ablate_h; }
-#define TRY(x) do { int _r = (x); if (_r) return _r; } while (0)
+// PA_ABLATE=<mask> (tuning builds only; results are WRONG, timing bounds only: the most that fusing a launch kind into its neighbours can
+// return).  The bits that leave a launch of each kind out: `always`; `k1` / `k3` by kernel size; `big1` / `big3` by kernel size on maps of
+// >= 16384 pixels; `low` on maps up to PA_ABLATE_H (default 8) pixels high (what the low-resolution stretch costs the step at most)
+enum { PA_L_SLAB_REDUCE, PA_L_CONV_WGRAD, PA_L_BN_FIN_FWD, PA_L_BN_FIN_BWD, PA_L_FWD_SITE, PA_L_CONV_FWD, PA_L_CONV_DGRAD, PA_L_UPADD_BWD,
+       PA_L_POOL_BWD, PA_L_POOL_UPADD_FWD, PA_L_STEM_ROUTE };
+static const struct { int always, k1, k3, big1, big3, low; } ablate_bits[] = {
+    /* PA_L_SLAB_REDUCE     */ {1, 0, 0, 0, 0, 0},              // slab reductions of the weight-gradient stream
+    /* PA_L_CONV_WGRAD      */ {2, 0, 0, 32, 64, 512},
+    /* PA_L_BN_FIN_FWD      */ {4, 0, 0, 0, 0, 0},              // finalize launches
+    /* PA_L_BN_FIN_BWD      */ {4, 0, 0, 0, 0, 256},
+    /* PA_L_FWD_SITE        */ {0, 0, 0, 0, 0, 128},            // a forward convolution WITH its finalize, uncounted
+    /* PA_L_CONV_FWD        */ {0, 0, 8, 0, 0, 0},
+    /* PA_L_CONV_DGRAD      */ {0, 16, 8, 0, 0, 256},
+    /* PA_L_UPADD_BWD       */ {1024, 0, 0, 0, 0, 0},           // (and no fused low-resolution half in the data gradient above it)
+    /* PA_L_POOL_BWD        */ {2048, 0, 0, 0, 0, 0},           // (and no routing of the hourglass pools)
+    /* PA_L_POOL_UPADD_FWD  */ {4096, 0, 0, 0, 0, 0},
+    /* PA_L_STEM_ROUTE      */ {2048 | 16 | 4, 0, 0, 0, 0, 0},  // the stem pool's routed form needs its three launches
+};
+bool Net::ablated(int kind, int k, int H, long M) const {
+    const int mask = pa_tuning().ablate;
+    if (!mask) return false;
+    const auto& b = ablate_bits[kind]; const bool big = M >= 16384;
+    return (mask & (b.always | (k == 1 ? b.k1 | (big ? b.big1 : 0) : 0) | (k == 3 ? b.k3 | (big ? b.big3 : 0) : 0) | (H <= pa_tuning().ablate_h ? b.low : 0))) != 0;
+}
+
+template <class F> int Net::account(const PaWork& w, F launch, bool skip, bool count_skipped) {
+    if (!skip || count_skipped) cnt(w);
+    ProfEntry* pe = w.cls >= 0 ? prof.begin(w.cls, w.bytes, w.flops, st) : nullptr;
+    const int rc = skip ? 0 : launch();
+    prof.end(pe, st);
+    return rc;
+}
 
 PaOperand pa_plain(const bf16* p) { PaOperand o; o.p = p; o.q = nullptr; o.k0 = o.k1 = o.k2 = nullptr; o.map = nullptr; o.mode = PA_LD_PLAIN; return o; }
 PaOperand pa_none() { PaOperand o; o.p = o.q = nullptr; o.k0 = o.k1 = o.k2 = nullptr; o.map = nullptr; o.mode = PA_LD_NONE; return o; }
-static PaEpilogue ep_plain() { PaEpilogue e; memset(&e, 0, sizeof e); e.mode = PA_OUT_PLAIN; return e; }
 static int round64(int v) { return (v + 63) / 64 * 64; }
+static PaWorkOp wop(const PaOperand& o) { return PaWorkOp{o.mode, o.q != nullptr}; }
+static PaWorkConv wconv(const ConvLayer& c, int B, int H, int W) { return PaWorkConv{B, H, W, c.Cin, c.Cout, c.pcin, c.pcout, c.k, c.splits}; }
 
 // ------------------------------------------------------------------------------------------------
 // declaration
@@ -301,13 +325,6 @@ int Prof::report(double* out) {
     return 0;
 }
 
-// algorithmic work of one conv launch: every activation element read once / written once (2-byte
-// elements), weights once; 2*M*N*K flops
-static void conv_work(int M, int cin, int cout, int taps, bool wgrad, double& bytes, double& flops) {
-    bytes = 2.0 * M * ((double)cin + cout) + (wgrad ? 4.0 : 2.0) * (double)cout * taps * cin;
-    flops = 2.0 * M * (double)cout * taps * cin;
-}
-
 // ------------------------------------------------------------------------------------------------
 // runtime helpers
 PaOperand Net::op(const Act& a) const {
@@ -332,26 +349,21 @@ PaEpilogue Net::final_ep(const Act& a) const {
 }
 
 int Net::finish_grad(const Act& a) {
-    if (!a.bn) return 0;
-    if (ablate() & 4) return 0;
-    if ((ablate() & 256) && a.H <= ablate_h()) return 0;
-    BNLayer* b = a.bn;
-    return pa_launch_bn_bwd_finalize(b->bstats, b->bstat_rows, b->scale, b->mean, b->invstd, b->kA, b->kB, b->kC, grads + b->p_gamma,
-                                     grads + b->p_beta, b->C, (float)a.M(), st);
+    if (!a.bn || ablated(PA_L_BN_FIN_BWD, 0, a.H)) return 0;
+    return pa_launch_bn_fin(fin_bwd(*a.bn, a.M()), a.bn->C, st);
 }
 
 // defer: the only next reader of a's BatchNorm-backward constants is a data-gradient launch that takes the pending finalize
 int Net::finish_grad_or_defer(const Act& a, bool defer) {
-    if (a.bn && defer && a.bn->bstat_rows > 0 && a.bn->bstat_rows <= fin_rows_max) { a.bn->bfin_pending = true; return 0; }
+    if (fin_can_wait(a.bn, defer, true)) { a.bn->bfin_pending = true; return 0; }
     return finish_grad(a);
 }
 
 int Net::finish_grad2_or_defer(const Act& a, bool defer_a, const Act& b, bool defer_b) {
-    const bool da = a.bn && defer_a && a.bn->bstat_rows > 0 && a.bn->bstat_rows <= fin_rows_max;
-    const bool db = b.bn && defer_b && b.bn->bstat_rows > 0 && b.bn->bstat_rows <= fin_rows_max;
-    if (da && db) { a.bn->bfin_pending = true; b.bn->bfin_pending = true; return 0; }
-    if (da) { a.bn->bfin_pending = true; return finish_grad(b); }
-    if (db) { b.bn->bfin_pending = true; return finish_grad(a); }
+    const bool da = fin_can_wait(a.bn, defer_a, true), db = fin_can_wait(b.bn, defer_b, true);
+    if (da) a.bn->bfin_pending = true;
+    if (db) b.bn->bfin_pending = true;
+    if (da || db) return da && db ? 0 : finish_grad(da ? b : a);
     return finish_grad2(a, b);
 }
 
@@ -360,14 +372,9 @@ int Net::finish_grad2_or_defer(const Act& a, bool defer_a, const Act& b, bool de
 bool Net::x3_fin_ok(const Residual& r, const Act& in) const { return (fin_mask & 4) && !drop_mask && fin_consumer_ok(r.c3, in.B, in.H, in.W, true); }
 
 int Net::finish_grad2(const Act& a, const Act& b) {
-    if (ablate() & 4) return 0;
-    if ((ablate() & 256) && a.H <= ablate_h()) return 0;
+    if (ablated(PA_L_BN_FIN_BWD, 0, a.H)) return 0;
     if (!a.bn || !b.bn) { TRY(finish_grad(a)); return finish_grad(b); }
-    BNLayer *x = a.bn, *y = b.bn;
-    return pa_launch_bn_bwd_finalize2(x->bstats, x->bstat_rows, x->scale, x->mean, x->invstd, x->kA, x->kB, x->kC, grads + x->p_gamma, grads + x->p_beta,
-                                      x->C, (float)a.M(),
-                                      y->bstats, y->bstat_rows, y->scale, y->mean, y->invstd, y->kA, y->kB, y->kC, grads + y->p_gamma, grads + y->p_beta,
-                                      y->C, (float)b.M(), st);
+    return pa_launch_bn_fin2(fin_bwd(*a.bn, a.M()), a.bn->C, fin_bwd(*b.bn, b.M()), b.bn->C, st);
 }
 
 bool Net::fin_consumer_ok(const ConvLayer& c, int B_, int H, int W, bool dgrad) const {
@@ -405,21 +412,12 @@ int Net::conv_fwd(ConvLayer& c, const PaOperand& in, int B_, int H, int W, const
     a.B = B_; a.H = H; a.W = W; a.Cin = c.pcin; a.Cout = c.pcout; a.taps = c.k == 7 ? 1 : c.taps();
     a.ep = ep_plain();
     if (bn_after && train_bn) { a.ep.mode = PA_OUT_STATS; a.ep.stats = bn_after->stats; a.ep.rows_out = &bn_after->stat_rows; }
-    double wb, wf; conv_work(B_ * H * W, c.k == 7 ? 147 : c.Cin, c.Cout, c.k == 7 ? 1 : c.taps(), false, wb, wf);
-    if (c.k == 7) wb = 2.0 * B_ * (4.0 * H * W * 4 + (double)H * W * 64) + 2.0 * 64 * 147;      // image read once (4-ch padded) + output
-    if ((ablate() & 128) && H <= ablate_h()) return 0;
-    { const double M = (double)B_ * H * W;
-      cnt((c.k == 7 ? 2.0 * B_ * 4.0 * H * W * 4 : opb(in, M * a.Cin)) + opb(add1, M * a.Cout) + opb(add2, M * a.Cout) + 2.0 * a.Cout * a.taps * a.Cin, 2.0 * M * a.Cout); }
-    ProfEntry* pe = prof.begin(c.k == 7 ? PA_PROF_STEM_FWD : ((long)B_ * H * W < PA_PROF_LOW_M ? PA_PROF_LOW_FWD : (c.k == 3 ? PA_PROF_FWD3 : PA_PROF_FWD1)), wb, wf, st);
-    int rc = (c.k == 3 && (ablate() & 8)) ? 0 : ((c.k == 7) ? pa_launch_stem_conv(a, st) : pa_launch_conv(a, st));
-    prof.end(pe, st);
-    TRY(rc);
-    if (bn_after && train_bn && defer_after && bn_after->stat_rows > 0 && bn_after->stat_rows <= fin_rows_max) { bn_after->fin_pending = true; return 0; }
-    if (bn_after && train_bn && !(ablate() & 4))
-        TRY(pa_launch_bn_finalize(bn_after->stats, bn_after->stat_rows, params + bn_after->p_gamma, params + bn_after->p_beta,
-                                  buffers + bn_after->b_rmean, buffers + bn_after->b_rvar, bn_after->scale, bn_after->shift,
-                                  bn_after->mean, bn_after->invstd, bn_after->C, (float)(B_ * H * W), momentum, eps, bn_update, st));
-    return 0;
+    if (ablated(PA_L_FWD_SITE, c.k, H)) return 0;
+    const PaWork w = pa_work_conv_fwd(wconv(c, B_, H, W), wop(in), wop(add1), wop(add2));
+    TRY(account(w, [&] { return c.k == 7 ? pa_launch_stem_conv(a, st) : pa_launch_conv(a, st); }, ablated(PA_L_CONV_FWD, c.k)));
+    if (!bn_after || !train_bn) return 0;
+    if (fin_can_wait(bn_after, defer_after, false)) { bn_after->fin_pending = true; return 0; }
+    return ablated(PA_L_BN_FIN_FWD) ? 0 : pa_launch_bn_fin(fin_fwd(*bn_after, B_ * H * W), bn_after->C, st);
 }
 
 int Net::conv_dgrad(ConvLayer& c, const PaOperand& dy, int B_, int H, int W, const PaOperand& add1, const PaOperand& add2,
@@ -436,37 +434,23 @@ int Net::conv_dgrad(ConvLayer& c, const PaOperand& dy, int B_, int H, int W, con
     }
     if (dy.mode == PA_LD_POOL || dy.mode == PA_LD_LIN2) a.dz_out = dz_out;      // stored where the plan's instance does (PaConvPlan::stores_dz)
     // the low-resolution half of the upsample-add backward in this launch's epilogue (round 6): an instance of the row-tile 1x1 kernel
-    if (low && dy.mode != PA_LD_POOL && pa_tuning().upadd_fuse && low->bn && !drop_mask && !(ablate() & 1024)) { a.out2 = low->grad; a.ep2 = final_ep(*low); }
+    if (low && dy.mode != PA_LD_POOL && pa_tuning().upadd_fuse && low->bn && !drop_mask && !ablated(PA_L_UPADD_BWD)) { a.out2 = low->grad; a.ep2 = final_ep(*low); }
     PaConvPlan p = pa_conv_plan(pa_conv_shape(a));
     if (a.out2 && p.path != PA_CVP_ROW_UP) { a.out2 = nullptr; memset(&a.ep2, 0, sizeof a.ep2); p = pa_conv_plan(pa_conv_shape(a)); }      // not that instance's launch: on its own
     const bool up = p.path == PA_CVP_ROW_UP; if (dz_done) *dz_done = p.stores_dz;
-    double wb, wf; conv_work(B_ * H * W, c.Cin, c.Cout, c.taps(), false, wb, wf);
-    ProfEntry* pe = prof.begin((long)B_ * H * W < PA_PROF_LOW_M ? PA_PROF_LOW_DGRAD : (c.k == 3 ? PA_PROF_DGRAD3 : PA_PROF_DGRAD1), wb, wf, st);
-    if ((c.k == 3 && (ablate() & 8)) || (c.k == 1 && (ablate() & 16)) || ((ablate() & 256) && H <= ablate_h())) { if (a.ep.rows_out) *a.ep.rows_out = 1; prof.end(pe, st); return 0; }
-    { const double M = (double)B_ * H * W;
-      if (dy.mode == PA_LD_POOL) cnt(opb(dy, M * a.Cin) + 2.0 * M * a.Cout + 2.0 * a.Cout * a.taps * a.Cin, 2.0 * M * a.Cout + 2.0 * M * a.Cin);
-      else cnt(opb(dy, M * a.Cin) + opb(add1, M * a.Cout) + opb(add2, M * a.Cout) + (ep.mode == PA_OUT_BWD ? 2.0 * M * a.Cout : 0.0) + 2.0 * a.Cout * a.taps * a.Cin
-                   + (up ? 2.0 * M * a.Cout / 4 : 0.0),
-               2.0 * M * a.Cout + (p.stores_dz ? 2.0 * M * a.Cin : 0.0) + (up ? 2.0 * M * a.Cout / 4 : 0.0)); }
-    int rc = pa_launch_conv(a, p, st);
-    if (up && low_done) *low_done = true;
-    prof.end(pe, st);
-    return rc;
+    const PaWork w = pa_work_conv_dgrad(wconv(c, B_, H, W), wop(dy), wop(add1), wop(add2), ep.mode, p.stores_dz, up);
+    const bool skip = ablated(PA_L_CONV_DGRAD, c.k, H);      // (a skipped launch is not counted, and leaves the row count a producer would have)
+    if (skip && a.ep.rows_out) *a.ep.rows_out = 1;
+    if (!skip && up && low_done) *low_done = true;
+    return account(w, [&] { return pa_launch_conv(a, p, st); }, skip, false);
 }
 
 int Net::conv_wgrad(ConvLayer& c, const PaOperand& dy, const PaOperand& x, int B_, int H, int W) {
     PaWgradArgs a; memset(&a, 0, sizeof a);
     a.dy = dy; a.x = x; a.part = c.part; a.dbpart = c.dbpart;
     a.B = B_; a.H = H; a.W = W; a.Cin = c.pcin; a.Cout = c.pcout; a.taps = c.k == 7 ? 1 : c.taps(); a.splits = c.splits;
-    double wb, wf; conv_work(B_ * H * W, c.k == 7 ? 147 : c.Cin, c.Cout, c.k == 7 ? 1 : c.taps(), true, wb, wf);
-    if (c.k == 7) wb = 2.0 * B_ * (4.0 * H * W * 4 + (double)H * W * 64) + 4.0 * 64 * 147;
-    const int cls = c.k == 7 ? PA_PROF_STEM_WGRAD : ((long)B_ * H * W < PA_PROF_LOW_M ? PA_PROF_LOW_WGRAD : (c.k == 3 ? PA_PROF_WGRAD3 : PA_PROF_WGRAD1));
-    if (ablate() & 2) return 0;
-    if ((ablate() & 32) && c.k == 1 && (long)B_ * H * W >= 16384) return 0;      // timing bound: what fusing the large 1x1 weight gradients into their data gradients could save at most
-    if ((ablate() & 64) && c.k == 3 && (long)B_ * H * W >= 16384) return 0;
-    if ((ablate() & 512) && H <= ablate_h()) return 0;
-    { const double M = (double)B_ * H * W, slab = 4.0 * (double)c.splits * a.Cout * a.taps * a.Cin;      // slabs written, read back by the reducer, gradient written
-      cnt((c.k == 7 ? 2.0 * B_ * 4.0 * H * W * 4 : opb(x, M * a.Cin)) + opb(dy, M * a.Cout) + slab, slab + 4.0 * a.Cout * a.taps * a.Cin); }
+    if (ablated(PA_L_CONV_WGRAD, c.k, H, (long)B_ * H * W)) return 0;
+    const PaWork w = pa_work_conv_wgrad(wconv(c, B_, H, W), wop(dy), wop(x));
     // With a weight-gradient stream every launch is collected and leaves in flush_wgrads() on that stream -- except the stem's, the last
     // launch of the step: on the main stream, idle by then, it runs beside the weight-gradient queue's last reduction instead of behind it.
     // Without one (single-stream mode: bench.py's roofline leg, debugging) the launches the grouped kernel takes are collected too and
@@ -476,14 +460,12 @@ int Net::conv_wgrad(ConvLayer& c, const PaOperand& dy, const PaOperand& x, int B
     const bool stem_now = c.k == 7 && aside && pa_tuning().stem_on_main;
     const int job_wgs = c.k == 7 ? 0 : pa_wgrad_job_workgroups(a);
     if (aside ? !stem_now : job_wgs > 0) {
-        PendingWgrad p; p.a = a; p.cls = cls; p.bytes = wb; p.flops = wf; p.stem = c.k == 7; p.job_wgs = job_wgs; p.c = &c;
+        PendingWgrad p; p.a = a; p.w = w; p.stem = c.k == 7; p.job_wgs = job_wgs; p.c = &c;
         pending_wgrads.push_back(p);
+        cnt(w);      // (counted here; its profile entry opens where it is launched: launch_pending_wgrads)
         return 0;
     }
-    ProfEntry* pe = prof.begin(cls, wb, wf, st);
-    int rc = (c.k == 7) ? pa_launch_stem_wgrad(a, st) : pa_launch_wgrad(a, st);
-    prof.end(pe, st);
-    if (rc) return rc;
+    TRY(account(w, [&] { return c.k == 7 ? pa_launch_stem_wgrad(a, st) : pa_launch_wgrad(a, st); }));
     if (stem_now) TRY(pa_launch_stem_wgrad_reduce(c.part, c.splits, grads + c.p_w, st, grads + c.p_b));
     return 0;
 }
@@ -521,7 +503,7 @@ int Net::launch_pending_wgrads() {
     }
     // slabs are summed on the weight-gradient stream as the step goes: the layers of a flush join the stash, and the stash is summed by a
     // few more workgroups of a LATER group launch of this stream (in_group) or by a launch of its own
-    const bool stash = aside && !(ablate() & 1), in_group = t.wg_red_in_group != 0;
+    const bool stash = aside && !ablated(PA_L_SLAB_REDUCE), in_group = t.wg_red_in_group != 0;
     bool first = true;
     // every launch of the list the grouped kernel takes goes into group launches of up to 8 jobs (also while the per-launch event timing
     // runs: a group launch counts for the class of its largest job); the others -- the stem, shapes of the generic kernel -- are launched
@@ -534,10 +516,10 @@ int Net::launch_pending_wgrads() {
         int big = 0; double bytes = 0.0, flops = 0.0;
         for (int j = 0; j < nj; ++j) {
             const PendingWgrad& q = pending_wgrads[jidx[j]];
-            bytes += q.bytes; flops += q.flops;
-            if (q.flops > pending_wgrads[jidx[big]].flops) big = j;
+            bytes += q.w.bytes; flops += q.w.flops;
+            if (q.w.flops > pending_wgrads[jidx[big]].w.flops) big = j;
         }
-        ProfEntry* pe = prof.begin(pending_wgrads[jidx[big]].cls, bytes, flops, ws);
+        ProfEntry* pe = prof.begin(pending_wgrads[jidx[big]].w.cls, bytes, flops, ws);
         const bool carry = stash && in_group && !red_stash.empty();      // the slabs of EARLIER flushes ride in this launch
         const int rc = (nj == 1 && !carry) ? pa_launch_wgrad(*jobs[0], ws)
                                            : pa_launch_wgrad_group(jobs, nj, ws, false, red_jobs, carry ? red_stash.data() : nullptr, carry ? (int)red_stash.size() : 0);
@@ -572,7 +554,7 @@ int Net::launch_pending_wgrads() {
     for (size_t pi = 0; pi < pending_wgrads.size(); ++pi) {
         PendingWgrad& p = pending_wgrads[pi];
         if (grouped[pi]) continue;
-        ProfEntry* pe = prof.begin(p.cls, p.bytes, p.flops, ws);
+        ProfEntry* pe = prof.begin(p.w.cls, p.w.bytes, p.w.flops, ws);
         pa_wgrad_set_launch_flags((t.wgrad_anyorder && !first && !prof.on && !in_capture) ? 1u : 0u);
         int rc = p.stem ? pa_launch_stem_wgrad(p.a, ws) : pa_launch_wgrad(p.a, ws);
         pa_wgrad_set_launch_flags(0u);
@@ -596,42 +578,25 @@ int Net::launch_pending_wgrads() {
     return 0;
 }
 
-// the streaming launches with their operand bytes counted (Net::cnt, pa_net_design_bytes)
+// the streaming launches with their operand bytes counted (Net::account, work_model.h); a skipped one leaves the row count its consumer waits for
+static double elems(int B, int H, int W, int C) { return (double)B * H * W * C; }
 static int c_maxpool_fwd(Net& n, const PaOperand& in, bf16* out, int B, int H, int W, int C, hipStream_t st, unsigned char* map = nullptr, bf16* xmax = nullptr) {
-    const double e = (double)B * H * W * C; n.cnt(Net::opb(in, e), 2.0 * e / 4 + (map ? e / 4 : 0.0) + (xmax ? 2.0 * e / 4 : 0.0));
-    if (ablate() & 4096) return 0;
-    return pa_launch_maxpool_fwd(in, out, B, H, W, C, st, map, xmax);
+    return n.account(pa_work_maxpool_fwd(wop(in), elems(B, H, W, C), map != nullptr, xmax != nullptr),
+                     [&] { return pa_launch_maxpool_fwd(in, out, B, H, W, C, st, map, xmax); }, n.ablated(PA_L_POOL_UPADD_FWD));
 }
 static int c_maxpool_bwd(Net& n, const bf16* dout, const PaOperand& in, const PaOperand& add, const PaEpilogue& ep, bf16* din, int B, int H, int W, int C,
-                         hipStream_t st, int* rows = nullptr) {
-    const double e = (double)B * H * W * C; n.cnt(2.0 * e / 4 + Net::opb(in, e) + Net::opb(add, e) + (ep.mode == PA_OUT_BWD ? 2.0 * e : 0.0), 2.0 * e);
-    if (ablate() & 2048) { if (ep.rows_out) *ep.rows_out = 1; return 0; }
-    return pa_launch_maxpool_bwd(dout, in, add, ep, din, B, H, W, C, st, rows);
-}
-static int c_upadd_fwd(Net& n, const PaOperand& low, const PaOperand& skip, bf16* out, int B, int H, int W, int C, hipStream_t st) {
-    const double e = (double)B * H * W * C; n.cnt(Net::opb(low, e / 4) + Net::opb(skip, e), 2.0 * e);
-    if (ablate() & 4096) return 0;
-    return pa_launch_upadd_fwd(low, skip, out, B, H, W, C, st);
+                         hipStream_t st) {
+    const bool skip = n.ablated(PA_L_POOL_BWD);
+    if (skip && ep.rows_out) *ep.rows_out = 1;
+    return n.account(pa_work_maxpool_bwd(wop(in), wop(add), ep.mode, elems(B, H, W, C)),
+                     [&] { return pa_launch_maxpool_bwd(dout, in, add, ep, din, B, H, W, C, st); }, skip);
 }
 static int c_upadd_bwd(Net& n, const bf16* dout, const PaEpilogue& ep_low, bf16* dlow, const PaEpilogue& ep_skip, bf16* dskip, int B, int H, int W, int C,
-                       hipStream_t st, int* rows = nullptr, int part = 3) {
-    const double e = (double)B * H * W * C;
-    n.cnt(2.0 * e + ((part & 1) && ep_low.mode == PA_OUT_BWD ? 2.0 * e / 4 : 0.0) + ((part & 2) && ep_skip.mode == PA_OUT_BWD ? 2.0 * e : 0.0),
-          ((part & 1) ? 2.0 * e / 4 : 0.0) + ((part & 2) ? 2.0 * e : 0.0));
-    if (ablate() & 1024) { if (ep_low.rows_out && (part & 1)) *ep_low.rows_out = 1; if (ep_skip.rows_out && (part & 2)) *ep_skip.rows_out = 1; return 0; }
-    return pa_launch_upadd_bwd(dout, ep_low, dlow, ep_skip, dskip, B, H, W, C, st, rows, part);
-}
-template <class... A> static int c_head_fwd(Net& n, const PaOperand& x, A... rest) {
-    const double M = (double)n.B * (n.res / 4) * (n.res / 4); n.cnt(Net::opb(x, M * n.chan) + 2.0 * 16 * n.chan, M * 16 * 4 + M * 64 * 2);
-    return pa_launch_head_fwd(x, rest...);
-}
-template <class... A> static int c_heat_grad(Net& n, const float* heat, const double* pts, const bf16* din, A... rest) {
-    const double M = (double)n.B * (n.res / 4) * (n.res / 4); n.cnt(M * 16 * 4 + (din ? M * 64 * 2 : 0.0), M * 64 * 2);
-    return pa_launch_heat_grad(heat, pts, din, rest...);
-}
-template <class... A> static int c_heat_inject(Net& n, const float* G, int layout, const bf16* din, A... rest) {
-    const double M = (double)n.B * (n.res / 4) * (n.res / 4); n.cnt((G ? M * 16 * 4 : 0.0) + (din ? M * 64 * 2 : 0.0), M * 64 * 2);
-    return pa_launch_heat_inject(G, layout, din, rest...);
+                       hipStream_t st, int part = 3) {
+    const bool skip = n.ablated(PA_L_UPADD_BWD);
+    if (skip) { if (ep_low.rows_out && (part & 1)) *ep_low.rows_out = 1; if (ep_skip.rows_out && (part & 2)) *ep_skip.rows_out = 1; }
+    return n.account(pa_work_upadd_bwd(elems(B, H, W, C), part, ep_low.mode, ep_skip.mode),
+                     [&] { return pa_launch_upadd_bwd(dout, ep_low, dlow, ep_skip, dskip, B, H, W, C, st, nullptr, part); }, skip);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -769,7 +734,9 @@ int Hourglass::decode(Net& n) {
         TRY(up[k].fwd(n, *low));
         const Act& m = merged[k];
         if (n.multi_stream) TRY(n.wait_join(k));
-        TRY(c_upadd_fwd(n, n.op(up[k].out()), n.op(n.drop_mask ? skipm[k] : skip[k].out()), m.raw, m.B, m.H, m.W, m.C, n.st));
+        const PaOperand lo = n.op(up[k].out()), sk = n.op(n.drop_mask ? skipm[k] : skip[k].out());
+        TRY(n.account(pa_work_upadd_fwd(wop(lo), wop(sk), (double)m.numel()), [&] { return pa_launch_upadd_fwd(lo, sk, m.raw, m.B, m.H, m.W, m.C, n.st); },
+                      n.ablated(PA_L_POOL_UPADD_FWD)));
         low = &merged[k];
     }
     return 0;
@@ -784,7 +751,7 @@ bool Hourglass::low_fusable(const Net& n, int k) const {
 // Can the first block of skip[k] take the gradient of pool k through the arg-max map (its conv1 data gradient as Residual::bwd_b launches it:
 // BatchNorm backward on load, dz3 or its LIN2 form as first addend, the epilogue of the block input x)?
 bool Hourglass::route_ok(Net& n, int k, const Act& x, const PaOperand& ex0) {
-    if (!(n.pool_route & 1) || !map_written[k] || (ablate() & 2048)) return false;
+    if (!(n.pool_route & 1) || !map_written[k] || n.ablated(PA_L_POOL_BWD)) return false;
     if (ex0.mode != PA_LD_NONE && ex0.mode != PA_LD_PLAIN) return false;
     Residual& r = skip[k].head();
     if (r.has_adapter || r.low_of_in) return false;
@@ -817,13 +784,13 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
             TRY(n.fork_to(k));
             {
                 StreamScope sc(n, n.side);
-                TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad, m.B, m.H, m.W, m.C, n.st, nullptr, 2));
+                TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad, m.B, m.H, m.W, m.C, n.st, 2));
                 TRY(n.finish_grad_or_defer(sko, n.x3_fin_ok(skip[k], x)));
                 TRY(skip[k].bwd_a(n, x));
             }
             TRY(n.record_join(k));
             // (d up[k].out() may have come out of the data gradient that produced d merged[k]: low_done)
-            if (!low_done[k]) TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad, m.B, m.H, m.W, m.C, n.st, nullptr, 1));
+            if (!low_done[k]) TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad, m.B, m.H, m.W, m.C, n.st, 1));
             TRY(n.finish_grad_or_defer(upo, n.x3_fin_ok(up[k], upin_)));
             up[k].head().low_of_in = low_fusable(n, k + 1) ? &up[k + 1].out() : nullptr;
             TRY(up[k].bwd(n, upin_, pa_none(), true));
@@ -836,7 +803,7 @@ int Hourglass::bwd(Net& n, const Act& in, const PaOperand& extra0) {
         } else {
             // (low_done: only d skip is left -- the launch that can do one half exists wherever the fused data gradient does)
             TRY(c_upadd_bwd(n, m.grad, n.final_ep(upo), upo.grad, n.final_ep(sko), sko.grad,
-                                    m.B, m.H, m.W, m.C, n.st, nullptr, low_done[k] ? 2 : 3));
+                                    m.B, m.H, m.W, m.C, n.st, low_done[k] ? 2 : 3));
         }
         {
             const Act& upin_ = (k == 3) ? (n.drop_mask ? neckm : neck.out()) : merged[k + 1];
@@ -1004,8 +971,8 @@ int Net::forward_pose_body(const float* img_nchw, const bf16* img4_in, const dou
         TRY(hg[i].decode(*this));
         TRY(post[i].fwd(*this, hg[i].out()));
         TRY(conv_fwd(lin[i], op(post[i].out()), B, Hh, Hh, pa_none(), pa_none(), lin_out[i].raw, &lin_bn[i]));
-        TRY(c_head_fwd(*this, op(lin_out[i]), outc[i].wf, params + outc[i].p_b, heat[i], heat64[i], pts ? pts_dev : nullptr,
-                               pts ? loss_dev + i : nullptr, B, Hh, Hh, chan, st));
+        TRY(account(pa_work_head_fwd(wop(op(lin_out[i])), elems(B, Hh, Hh, 1), chan), [&] {
+            return pa_launch_head_fwd(op(lin_out[i]), outc[i].wf, params + outc[i].p_b, heat[i], heat64[i], pts ? pts_dev : nullptr, pts ? loss_dev + i : nullptr, B, Hh, Hh, chan, st); }));
         if (i + 1 < stacks) {
             TRY(conv_fwd(forth[i], op(lin_out[i]), B, Hh, Hh, op(xin[i]), pa_none(), forth_tmp[i], nullptr));
             TRY(conv_fwd(inc[i], pa_plain(heat64[i]), B, Hh, Hh, pa_plain(forth_tmp[i]), pa_none(), xin[i + 1].raw, nullptr));
@@ -1026,10 +993,12 @@ int Net::backward_stack(int i) {
         TRY(conv_dgrad(inc[i], gx, B, Hh, Hh, pa_none(), pa_none(), ep_plain(), dheat_in[i]));
         TRY(conv_wgrad(forth[i], gx, op(lin_out[i]), B, Hh, Hh));
     }
+    const bf16* din = inner ? dheat_in[i] : nullptr;
     if (heat_grads_on) {        // the caller's gradient (pa_hg_set_heat_grads), unscaled: only the half-precision build's PA_GRAD_SCALE is applied
-        TRY(c_heat_inject(*this, heat_grads[i], heat_grads_layout, inner ? dheat_in[i] : nullptr, dheat64[i], PA_GRAD_SCALE, B, Hh, Hh, st));
+        TRY(account(pa_work_heat_inject(elems(B, Hh, Hh, 1), heat_grads[i] != nullptr, inner),
+                    [&] { return pa_launch_heat_inject(heat_grads[i], heat_grads_layout, din, dheat64[i], PA_GRAD_SCALE, B, Hh, Hh, st); }));
     } else {
-        TRY(c_heat_grad(*this, heat[i], pts_dev, inner ? dheat_in[i] : nullptr, dheat64[i], gscale, B, Hh, Hh, st));
+        TRY(account(pa_work_heat_grad(elems(B, Hh, Hh, 1), inner), [&] { return pa_launch_heat_grad(heat[i], pts_dev, din, dheat64[i], gscale, B, Hh, Hh, st); }));
     }
     const PaOperand gh = pa_plain(dheat64[i]);
     TRY(conv_wgrad(outc[i], gh, op(lin_out[i]), B, Hh, Hh));
@@ -1064,9 +1033,8 @@ int Net::backward_stem() {
     stem_routed = stem_route_ok();
     res1.g3_pool_on = stem_routed;
     if (stem_routed) {
-        const double e = (double)B * (res / 4) * (res / 4) * 128;
-        cnt(4.0 * e, 0.0);
-        TRY(pa_launch_maxpool_bwd_stats(pool0.grad, stem_xmax, op(res1.x3), final_ep(res1.x3), B, res / 2, res / 2, 128, st));
+        TRY(account(pa_work_pool_stats(elems(B, res / 4, res / 4, 128)),
+                    [&] { return pa_launch_maxpool_bwd_stats(pool0.grad, stem_xmax, op(res1.x3), final_ep(res1.x3), B, res / 2, res / 2, 128, st); }));
         TRY(finish_grad(res1.x3));
         res1.g3_pool = gradop(res1.x3);
         res1.g3_pool.mode = PA_LD_POOL; res1.g3_pool.p = pool0.grad; res1.g3_pool.map = stem_map;
@@ -1083,9 +1051,7 @@ int Net::backward_stem() {
         PaStemDgradArgs d; memset(&d, 0, sizeof d);
         d.g = gradop(a0); d.wf = stem_conv.wf; d.out = image_grad; d.B = B; d.Hm = res / 2; d.Wm = res / 2; d.layout = image_grad_layout;
         d.scale = 1.f / PA_GRAD_SCALE;
-        const double e = (double)B * d.Hm * d.Wm * 64;
-        cnt(opb(d.g, e) + 2.0 * 64 * 256, 4.0 * B * res * res * (image_grad_layout ? 4 : 3));
-        TRY(pa_launch_stem_dgrad(d, st));
+        TRY(account(pa_work_stem_dgrad(wop(d.g), B, d.Hm, d.Wm, d.layout), [&] { return pa_launch_stem_dgrad(d, st); }));
     }
     TRY(reduce_grads());
     return join_meters();               // the step's meters ran beside this pass: later readers on the main stream come behind them
@@ -1094,7 +1060,7 @@ int Net::backward_stem() {
 // both halves of the stem's routed pool exist for this shape: the statistics launch (the streaming plans of the pool) and the pool-routed load
 // of residual1's conv3 data gradient, which must also be the launch that stores dz3 for the later readers of that gradient
 bool Net::stem_route_ok() {
-    if (!(pool_route & 2) || !stem_map_written || (ablate() & (2048 | 16 | 4))) return false;
+    if (!(pool_route & 2) || !stem_map_written || ablated(PA_L_STEM_ROUTE)) return false;
     const int H = res / 2;
     if (!pa_pool_stats_route_supported(op(res1.x3), final_ep(res1.x3), B, H, H, 128)) return false;
     const PaEpilogue mask = final_ep(res1.x3); PaConvShape s{};
