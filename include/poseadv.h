@@ -342,6 +342,29 @@ int pa_adam_steps(const pa_adam_state* state, long long* steps, long long* skipp
 /* state->step = steps, on `stream` (load_state_dict); the other words stay.  Errors: a NULL or misaligned state, steps < 0 or > INT32_MAX. */
 int pa_adam_set_steps(pa_adam_state* state, long long steps, void* stream);
 
+/* Exponential moving average of the weights, updated on the device (utils.optim.ModelEma): ema += w (src - ema) after an optimizer
+ * step, w = 1 - decay.  No reference counterpart: the reference validates and saves the raw weights.
+ * state: 32 bytes on the device, zeroed once by the caller and owned by ONE average.  updates = averaging steps applied so far; held =
+ * steps on which the average stayed because the optimizer skipped its own step; apply, w, decay_used = what the last pa_ema_advance
+ * decided.  They live on the device for the reason pa_adam_state's step does: the half-precision build decides there whether the
+ * optimizer's step is taken, and the average must not move (nor its warm-up count advance) on a skipped one.
+ * pa_ema_advance: one one-thread launch, no host synchronisation.  skip_flag: NULL, or word 0 of the optimizer's own state (the int32
+ * pair of pa_rmsprop_step_state, or a pa_adam_state), read on the device behind that optimizer's step.  Non-zero: apply = 0, held += 1,
+ * nothing else changes.  Otherwise, in double, d = warmup ? min(decay, (1 + updates) / (10 + updates)) : decay; w = (float)(1.0 - d),
+ * decay_used = (float)d, apply = 1, updates += 1.
+ * pa_ema_lerp: apply == 0: every element untouched.  Otherwise per element, in fp32, ema = copy ? src : fmaf(w, src - ema, ema): one
+ * subtraction, one fused multiply-add (torch.lerp(ema, src, w) for w < 0.5).  ema, src: n floats, 16-byte aligned, distinct arrays.
+ * Zero padding stays zero; no atomics, the same input gives the same bits.  n == 0: returns 0, launches nothing.
+ * Errors (non-zero, pa_last_error set, nothing launched): a NULL state / ema / src, ema == src, a misaligned ema or src, decay outside
+ * [0, 1) or not finite, updates < 0 or > INT32_MAX. */
+typedef struct pa_ema_state { int32_t updates, held, apply, reserved; float w, decay_used, reserved_f[2]; } pa_ema_state;
+int pa_ema_advance(pa_ema_state* state, float decay, int warmup, const int32_t* skip_flag, void* stream);
+int pa_ema_lerp(float* ema, const float* src, size_t n, const pa_ema_state* state, int copy, void* stream);
+/* *updates, *held (either may be NULL); synchronises `stream`. */
+int pa_ema_counts(const pa_ema_state* state, long long* updates, long long* held, void* stream);
+/* state->updates = updates, on `stream` (loading a file); the other words stay. */
+int pa_ema_set_updates(pa_ema_state* state, long long updates, void* stream);
+
 /* ---------------------------------------------------------------- operator level ---------- */
 /* One residual bottleneck block _Residual(C, C) (models/asn_stacked_hg.py:11-49), forward + backward,
  * NCHW fp32 in/out, parameters in the block's own state_dict order (flat fp32).  Used by the parity

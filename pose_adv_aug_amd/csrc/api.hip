@@ -3,6 +3,7 @@
 #include "net.h"
 #include "warp_bwd.h"
 #include "soft_argmax.h"
+#include "ema.h"
 #include <stdio.h>
 #include <string.h>
 #include <new>
@@ -301,6 +302,34 @@ int pa_adam_set_steps(pa_adam_state* state, long long steps, void* s) {
     if (!adam_state_ok("pa_adam_set_steps", state)) return 1;
     if (steps < 0 || steps > 2147483647LL) { pa_set_error_msg("pa_adam_set_steps: steps must be in 0 .. 2^31 - 1"); return 1; }
     TRY(pa_launch_adam_set_steps(reinterpret_cast<PaAdamState*>(state), (int)steps, ST(s))); return 0;
+}
+// Weight EMA (ema.hip; utils.optim.ModelEma): the update count, the hold decision and the weight w live in the caller's device state.  An
+// argument error launches nothing.
+static_assert(sizeof(pa_ema_state) == 32 && sizeof(PaEmaState) == 32, "pa_ema_state is 32 bytes");
+int pa_ema_advance(pa_ema_state* state, float decay, int warmup, const int32_t* skip_flag, void* s) {
+    g_err[0] = 0;
+    if (!state || (reinterpret_cast<uintptr_t>(state) & 3)) { pa_set_error_msg("pa_ema_advance: state is NULL or misaligned (a pa_ema_state on the device)"); return 1; }
+    if (!(decay >= 0.f && decay < 1.f)) { pa_set_error_msg("pa_ema_advance: decay must be finite and in [0, 1)"); return 1; }
+    TRY(pa_launch_ema_advance(reinterpret_cast<PaEmaState*>(state), decay, warmup != 0, skip_flag, ST(s))); return 0;
+}
+int pa_ema_lerp(float* ema, const float* src, size_t n, const pa_ema_state* state, int copy, void* s) {
+    g_err[0] = 0;
+    if (!state || !ema || !src) { pa_set_error_msg("pa_ema_lerp: state, ema or src is NULL"); return 1; }
+    if (ema == src) { pa_set_error_msg("pa_ema_lerp: ema and src are the same array"); return 1; }
+    if ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(src)) & 15) { pa_set_error_msg("pa_ema_lerp: ema and src must be 16-byte aligned"); return 1; }
+    if (n == 0) return 0;
+    TRY(pa_launch_ema_lerp(ema, src, n, reinterpret_cast<const PaEmaState*>(state), copy != 0, ST(s))); return 0;
+}
+int pa_ema_counts(const pa_ema_state* state, long long* updates, long long* held, void* s) {
+    g_err[0] = 0;
+    if (!state) { pa_set_error_msg("pa_ema_counts: state is NULL"); return 1; }
+    TRY(pa_ema_read_counts(reinterpret_cast<const PaEmaState*>(state), updates, held, ST(s))); return 0;
+}
+int pa_ema_set_updates(pa_ema_state* state, long long updates, void* s) {
+    g_err[0] = 0;
+    if (!state) { pa_set_error_msg("pa_ema_set_updates: state is NULL"); return 1; }
+    if (updates < 0 || updates > 2147483647LL) { pa_set_error_msg("pa_ema_set_updates: updates must be in 0 .. 2^31 - 1"); return 1; }
+    TRY(pa_launch_ema_set_updates(reinterpret_cast<PaEmaState*>(state), (int)updates, ST(s))); return 0;
 }
 int pa_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, void* s) {
     g_err[0] = 0;

@@ -50,36 +50,39 @@ def sample_bins(logits, seed, step, slot):
     return probs, idx
 
 
-def pose_step(hg, optimizer_hg, data):
-    """the common tail of both branches of train_hg (:229-245 / :282-299)"""
+def pose_step(hg, optimizer_hg, data, ema=None):
+    """the common tail of both branches of train_hg (:229-245 / :282-299); ema (utils.optim.ModelEma of hg, None: off) follows the step"""
     loss, _ = hg.loss_and_backward(img4=data['img4'], pts=data['pts'])
     optimizer_hg.step()
+    if ema is not None:
+        ema.update(optimizer_hg)
     pckh, _ = hg.pckh_origin_res(data['c'], data['s'], data['r'], data['grnd_pts'], data['normalizer'])
     return loss, pckh[0]
 
 
-def train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=0):
+def train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=0, ema=None):
     """one iteration of train_hg (:213-299).  Returns (kind, loss, pckh) as device scalars."""
     hg.train()
     agent_sr.eval()
     if i % 2 == 0:                                                   # regular augmentation (:224-245)
-        loss, pckh = pose_step(hg, optimizer_hg, augmenter.regular(batch))
+        loss, pckh = pose_step(hg, optimizer_hg, augmenter.regular(batch), ema)
         return 'regular', loss, pckh
     std = augmenter.standard(batch)                                  # img_std (:247)
     ls, lr = hg(asn=agent_sr, img4=std['img4'], is_half_hg=True, is_aug=True)       # (:250)
     _, si = sample_bins(ls, _bin_seed(seed, augmenter), i, BIN_SLOTS_TRAIN_HG[0])
     _, ri = sample_bins(lr, _bin_seed(seed, augmenter), i, BIN_SLOTS_TRAIN_HG[1])
-    loss, pckh = pose_step(hg, optimizer_hg, augmenter.agent(batch, si, ri, mode=1))     # load_batch_data(separate_s_r=False)
+    loss, pckh = pose_step(hg, optimizer_hg, augmenter.agent(batch, si, ri, mode=1), ema)     # load_batch_data(separate_s_r=False)
     return 'agent', loss, pckh
 
 
-def train_hg(batches, hg, optimizer_hg, agent_sr, augmenter, epoch, opt, log=print):
+def train_hg(batches, hg, optimizer_hg, agent_sr, augmenter, epoch, opt, log=print, ema=None):
     """:195-315.  All six meters see every iteration (device-side sums, split by the kind of step); the host synchronises
     every print_freq steps only."""
     meters = None
     n = len(batches)
+    with_ema = {} if ema is None else {'ema': ema}            # (off: the call the loop has always made)
     for i, batch in enumerate(batches):
-        kind, loss, pckh = train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=epoch)
+        kind, loss, pckh = train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=epoch, **with_ema)
         if meters is None:
             meters = DeviceMeters(METER_NAMES, loss.device)
         tag = ('loss_hg_regular', 'pckhs_regular') if kind == 'regular' else ('loss_hg_sr', 'pckhs_sr')
@@ -161,7 +164,7 @@ def main(argv=None):
     from .stack_hg import broadcast_parameters, init_distributed, make_feeds, validate
     from .utils.checkpoint import Checkpoint
     from .utils.logger import Logger
-    from .utils.optim import make_optimizer
+    from .utils.optim import make_ema, make_optimizer
     from .utils.util import ASNTrainHistory, PoseTrainHistory, adjust_lr
     from .utils.visualizer import Visualizer
     opt = TrainOptions().parse(argv)
@@ -215,11 +218,19 @@ def main(argv=None):
     checkpoint_sr.save_prefix = joint_dir + '/agent-'                                         # :110
     broadcast_parameters(hg)
     broadcast_parameters(agent_sr)
+    # the pose net's weight EMA (--ema_decay 0: None): a copy of the loaded, broadcast weights, or the average the file carries.  The
+    # agent keeps its raw weights, and it reads the RAW pose net: the two play against each other step by step.
+    ema = make_ema(opt, hg)
+    if ema is not None:
+        checkpoint_hg.load_ema(ema)
+    eval_net, eval_name = (hg, 'raw') if ema is None else (ema.module, 'EMA (decay %g)' % ema.decay)
+    with_ema = {} if ema is None else {'ema': ema}            # (off: the calls the loop has always made)
 
     augmenter = Augmenter(seed=4242 + rank, stretch=bool(opt.crop_stretch))
     train_feed, val_feed = make_feeds(opt, rank, world, log)                                  # :117-133
     if not opt.is_train:                                                                      # :137-144
-        _, _, predictions = validate(val_feed, hg, augmenter, train_history_pose.epoch[-1]['epoch'], opt, log=log)
+        log('epoch:%d validating the %s weights' % (train_history_pose.epoch[-1]['epoch'], eval_name))
+        _, _, predictions = validate(val_feed, eval_net, augmenter, train_history_pose.epoch[-1]['epoch'], opt, log=log)
         if rank == 0:
             checkpoint_hg.save_preds(predictions)
         return
@@ -231,14 +242,15 @@ def main(argv=None):
     epoch_sr = train_history_sr.epoch[-1]['epoch'] + 1
     for epoch in range(start_epoch_pose, opt.nEpochs):
         adjust_lr(opt, optimizer_hg, epoch)
-        train_loss_pose, train_pckh = train_hg(train_feed, hg, optimizer_hg, agent_sr, augmenter, epoch, opt, log=log)
-        val_loss, val_pckh, predictions = validate(val_feed, hg, augmenter, epoch, opt, log=log)
+        train_loss_pose, train_pckh = train_hg(train_feed, hg, optimizer_hg, agent_sr, augmenter, epoch, opt, log=log, **with_ema)
+        log('epoch:%d validating the %s weights' % (epoch, eval_name))
+        val_loss, val_pckh, predictions = validate(val_feed, eval_net, augmenter, epoch, opt, log=log)
         lr_now = optimizer_hg.param_groups[0]['lr']
         train_history_pose.update(OrderedDict([('epoch', epoch)]), OrderedDict([('lr', lr_now)]),
                                   OrderedDict([('train_loss', train_loss_pose), ('val_loss', val_loss)]),
                                   OrderedDict([('train_pckh', train_pckh), ('val_pckh', val_pckh)]))
         if rank == 0:
-            checkpoint_hg.save_checkpoint(hg, optimizer_hg, train_history_pose, predictions)  # :171-173
+            checkpoint_hg.save_checkpoint(hg, optimizer_hg, train_history_pose, predictions, **with_ema)  # :171-173
             logger.append([epoch, lr_now, train_loss_pose, val_loss, train_pckh, val_pckh])
         # one agent batch per epoch (:180-191, Appendix A.8)
         batch = next(iter(train_feed))

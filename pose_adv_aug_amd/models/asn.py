@@ -15,6 +15,10 @@ class ASN(_HipModule):
         self._last_B = None
         self._last_pose = None
 
+    def _twin(self):
+        """a new agent of the same configuration with its own flat arrays and handles (utils.optim.ModelEma)"""
+        return ASN(self.chan, self.scale_num, self.rotation_num, res=self.res, default_batch=self.default_batch, is_dropout=self.is_dropout)
+
     def _create(self, B):
         if self.is_dropout:
             return lib().pa_asn_create_dropout(self.chan, B, self.res)

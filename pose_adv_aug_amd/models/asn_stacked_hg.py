@@ -233,6 +233,11 @@ class HourglassNet(_HipModule):
         self.default_batch = default_batch
         self._last_B = None
 
+    def _twin(self):
+        """a new net of the same configuration with its own flat arrays and handles (utils.optim.ModelEma)"""
+        return HourglassNet(self.num_modules, self.num_stacks, chan=self.chan, num_classes=self.num_classes, res=self.res,
+                            default_batch=self.default_batch)
+
     def _create(self, B):
         if self.num_modules == 1:
             return lib().pa_hg_create(self.num_stacks, self.num_classes, self.chan, B, self.res)

@@ -26,6 +26,11 @@ class TrainOptions(BaseOptions):
         # reference's recipe and the fused step
         p.add_argument('--coord_loss', type=float, default=0., help='weight of the soft-arg-max coordinate L1 loss (0: off)')
         p.add_argument('--coord_beta', type=float, default=1., help='inverse temperature of the soft-arg-max of --coord_loss')
+        # exponential moving average of the pose net's weights (utils/optim.py ModelEma): validation, the -preds.mat files and is_best
+        # come from the averaged net, the checkpoint carries both; 0 = off, the reference's recipe: no twin net and no launch
+        p.add_argument('--ema_decay', type=float, default=0., help='decay of the weight EMA that is validated and saved (0: off)')
+        p.add_argument('--ema_warmup', type=int, default=0, choices=(0, 1), help='1: decay min(D, (1 + t) / (10 + t)) over the first updates')
+        p.add_argument('--ema_buffers', type=str, default='ema', choices=('ema', 'copy'), help='BatchNorm running statistics of the EMA: averaged, or copied')
         p.add_argument('--bs', type=int, default=12, help='mini-batch size')
         p.add_argument('--load_checkpoint', type=_bool, default=False, help='resume from checkpoint model')
         p.add_argument('--load_checkpoint_pose', type=_bool, default=False, help='use checkpoint model')
@@ -54,4 +59,6 @@ class TrainOptions(BaseOptions):
             self.parser.error('--momentum and --centered are RMSprop options: not with --optimizer %s' % o.optimizer)
         if o.coord_loss < 0 or not o.coord_beta > 0:
             self.parser.error('--coord_loss must be >= 0 and --coord_beta > 0')
+        if not 0 <= o.ema_decay < 1:
+            self.parser.error('--ema_decay must be in [0, 1) (0: off)')
         return BaseOptions.parse(self, args)

@@ -12,7 +12,7 @@ import torch.distributed as dist
 
 from .data import AugmentAhead, Augmenter, BatchFeed, DeviceBatch, num_samples, with_next
 from .models.asn_stacked_hg import create_hg
-from .utils.optim import make_optimizer
+from .utils.optim import make_ema, make_optimizer
 from .utils.util import AverageMeter, DeviceMeters, PoseTrainHistory, adjust_lr
 
 PCK_IDX = [0, 1, 2, 3, 4, 5, 10, 11, 14, 15]            # stack-hg.py:89
@@ -68,14 +68,15 @@ def coord_criterion(weight, beta=1.0):
     return criterion
 
 
-def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, criterion=None, heat_layout='nchw'):
+def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, criterion=None, heat_layout='nchw', ema=None):
     """stack-hg.py:134-180 for one batch.  Returns device scalars (loss, pckh, pckh_origin_res).
     data: the batch's augmented input if it was prepared ahead (data.AugmentAhead), else it is made here.
     criterion: a callable (outs, data) -> 0-d loss tensor over the per-stack heat maps of net.forward_autograd (your own loss, e.g.
     pylib.Criterion.weighted_L2 with per-joint weights): forward, criterion, loss.backward(), optimizer.step().  None (the default,
     what every shipped loop passes): the built-in fused MSE step.  A data['img4'] that requires grad gets its .grad from that backward
     pass (forward_autograd: d loss / d image, NHWC4).  heat_layout: the layout of the maps the criterion receives ('nhwc': views of the
-    engine's own buffers, forward_autograd(layout='nhwc'))."""
+    engine's own buffers, forward_autograd(layout='nhwc')).
+    ema (utils.optim.ModelEma of `net`, None: off): updated behind the optimizer step, on the device (held when the step was skipped)."""
     if data is None:
         data = augmenter.regular(batch)
     def meters():
@@ -87,6 +88,8 @@ def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, crit
         loss = criterion(outs, data)
         loss.backward()
         optimizer.step()
+        if ema is not None:
+            ema.update(optimizer)
         if not want_pckh:
             return loss.detach(), None, None
         pckh, pckh_o = meters()
@@ -96,10 +99,14 @@ def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, crit
         # engine's meter stream (100 us of short launches that otherwise sit between two steps); same values
         loss, _ = net.loss_and_backward(img4=data['img4'], pts=data['pts'], after_forward=meters)
         optimizer.step()
+        if ema is not None:
+            ema.update(optimizer)
         pckh, pckh_o = net.after_forward_result
         return loss, pckh[0], pckh_o[0]
     loss, _ = net.loss_and_backward(img4=data['img4'], pts=data['pts'])
     optimizer.step()
+    if ema is not None:
+        ema.update(optimizer)
     if not want_pckh:
         return loss, None, None
     pckh, pckh_o = meters()
@@ -127,7 +134,7 @@ def warn_skipped_steps(optimizer, log=print, name=''):
     return n - seen
 
 
-def train(batches, net, optimizer, augmenter, epoch, opt, log=print, criterion=None):
+def train(batches, net, optimizer, augmenter, epoch, opt, log=print, criterion=None, ema=None):
     """stack-hg.py:124-189 over a sized feed of DeviceBatches (a list, data.BatchFeed, MPII.batches()).  The meters see
     EVERY iteration (:171-180) through device-side sums; the host synchronises only every print_freq steps.
     criterion (None: the fused MSE step): a loss of the joint-minor maps, train_step(criterion=..., heat_layout='nhwc')."""
@@ -135,15 +142,16 @@ def train(batches, net, optimizer, augmenter, epoch, opt, log=print, criterion=N
     n = len(batches)
     meters = None
     ahead = AugmentAhead(augmenter)
+    with_ema = {} if ema is None else {'ema': ema}            # (off: the call the loop has always made)
     for i, (batch, nxt) in enumerate(with_next(batches)):
         if i == 0:
             ahead.start(batch)
         data = ahead.take()
         ahead.start(nxt)                                   # the next batch's crop runs beside this step's forward pass
         if criterion is None:
-            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data)
+            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, **with_ema)
         else:
-            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, criterion=criterion, heat_layout='nhwc')
+            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, criterion=criterion, heat_layout='nhwc', **with_ema)
         if meters is None:
             meters = DeviceMeters(('loss', 'pckh', 'pckh_origin_res'), loss.device)
         meters.update({'loss': loss, 'pckh': pckh, 'pckh_origin_res': pckh_o})
@@ -232,13 +240,19 @@ def main(argv=None):
     else:
         ckpt.save_prefix = exp_dir + '/'
     broadcast_parameters(net)
+    ema = make_ema(opt, net)                          # (--ema_decay 0: None) a copy of the loaded, broadcast weights ...
+    if ema is not None and opt.load_prefix_pose != '':
+        ckpt.load_ema(ema)                            # ... or the average the file carries
+    eval_net, eval_name = (net, 'raw') if ema is None else (ema.module, 'EMA (decay %g)' % ema.decay)
+    with_ema = {} if ema is None else {'ema': ema}            # (off: the calls the loop has always made)
     augmenter = Augmenter(seed=1234 + rank, stretch=bool(opt.crop_stretch))     # (training and validation: the reference stretches both)
     vis = Visualizer(opt, log_path=os.path.join(exp_dir, 'train-log.txt' if opt.is_train else 'val-log.txt') if rank == 0 else None)
     log = (lambda m: (print(m), vis.write_log(m))) if rank == 0 else (lambda m: None)
     batches, val_batches = make_feeds(opt, rank, world, log)
     if not opt.is_train:                                                                     # stack-hg.py:90-96
         epoch = history.epoch[-1]['epoch'] if history.epoch else 0
-        _, _, predictions = validate(val_batches, net, augmenter, epoch, opt, log=log)
+        log('epoch:%d validating the %s weights' % (epoch, eval_name))
+        _, _, predictions = validate(val_batches, eval_net, augmenter, epoch, opt, log=log)
         if rank == 0:
             ckpt.save_preds(predictions)
         return
@@ -247,14 +261,15 @@ def main(argv=None):
     for epoch in range(start, opt.nEpochs):
         adjust_lr(opt, optimizer, epoch)
         if criterion is None:
-            tl, tp = train(batches, net, optimizer, augmenter, epoch, opt, log=log)
+            tl, tp = train(batches, net, optimizer, augmenter, epoch, opt, log=log, **with_ema)
         else:
-            tl, tp = train(batches, net, optimizer, augmenter, epoch, opt, log=log, criterion=criterion)
-        vl, vp, predictions = validate(val_batches, net, augmenter, epoch, opt, log=log)      # stack-hg.py:98-99
+            tl, tp = train(batches, net, optimizer, augmenter, epoch, opt, log=log, criterion=criterion, **with_ema)
+        log('epoch:%d validating the %s weights' % (epoch, eval_name))
+        vl, vp, predictions = validate(val_batches, eval_net, augmenter, epoch, opt, log=log)      # stack-hg.py:98-99
         history.update(OrderedDict([('epoch', epoch)]), OrderedDict([('lr', optimizer.param_groups[0]['lr'])]),
                        OrderedDict([('train_loss', tl), ('val_loss', vl)]), OrderedDict([('train_pckh', tp), ('val_pckh', vp)]))
         if rank == 0:
-            ckpt.save_checkpoint(net, optimizer, history, predictions)                        # :108 (+ -preds.mat)
+            ckpt.save_checkpoint(net, optimizer, history, predictions, **with_ema)                      # :108 (+ -preds.mat)
 
 
 if __name__ == '__main__':

@@ -7,7 +7,10 @@ torch.nn.utils.clip_grad_norm_ (max_grad_norm), all inside the engine's own laun
 every one of them off, step() is the one pa_rmsprop_step_state call it has always been.
 
 Adam / AdamW (torch.optim.Adam's formula with weight decay coupled or decoupled, AMSGrad, the same clipping): one fused step
-(pa_adam_step) whose step count and bias-correction constants live on the device.  make_optimizer picks one from the command line."""
+(pa_adam_step) whose step count and bias-correction constants live on the device.  make_optimizer picks one from the command line.
+
+ModelEma: an exponential moving average of the weights in a twin net, updated on the device behind the step (pa_ema_advance, pa_ema_lerp);
+its update count and the decision to hold on a skipped step live on the device, next to the optimizer's flag.  make_ema: from the command line."""
 import ctypes as C
 import os
 
@@ -179,6 +182,10 @@ class RMSprop(_FlatOptimizer):
                                          ptr(self.momentum_buffer) if mom > 0 else None, ptr(self.grad_avg) if centered else None,
                                          n, float(gscale), coef, ptr(self._skip_state), stream()), 'pa_rmsprop_step_opts')
 
+    def skip_flag_ptr(self):
+        """device address of the int32 "the last step was skipped" flag (ModelEma.update reads it on the device)"""
+        return ptr(self._skip_state)
+
     def skipped_steps(self):
         """fp16 build: optimizer steps the engine skipped because the (scaled) gradient held inf / NaN; 0 in the bf16 build"""
         n = C.c_longlong(0)
@@ -299,6 +306,10 @@ class Adam(_FlatOptimizer):
         check(lib().pa_adam_steps(ptr(self._state), C.byref(steps), C.byref(skipped), stream()), 'pa_adam_steps')
         return int(steps.value), int(skipped.value)
 
+    def skip_flag_ptr(self):
+        """device address of the int32 "the last step was skipped" flag, word 0 of the pa_adam_state (ModelEma.update reads it on the device)"""
+        return ptr(self._state)
+
     def steps_taken(self):
         """optimizer steps applied so far (skipped ones not counted), read from the device: synchronises the stream"""
         return self._counts()[0]
@@ -388,6 +399,92 @@ class AdamW(Adam):
         """torch.optim.AdamW: Adam with decoupled weight decay and torch's default weight_decay"""
         Adam.__init__(self, net, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, decoupled_weight_decay=True,
                       max_grad_norm=max_grad_norm, overlap=overlap)
+
+
+class ModelEma(object):
+    def __init__(self, net, decay=0.999, warmup=False, buffers='ema'):
+        """Exponential moving average of the weights of `net` (any _HipModule: the pose net or an agent), kept on the device:
+        ema += (1 - decay) (p - ema) after every optimizer step that was TAKEN (pa_ema_advance + pa_ema_lerp, fp32 like torch's
+        swa_utils.get_ema_multi_avg_fn).  self.module is a twin of `net` -- the same class and configuration, its own flat arrays and
+        handles -- that holds the average and is a normal net: eval(), forward, heatmaps, accuracy, pckh_origin_res, state_dict().
+        warmup: decay_t = min(decay, (1 + t) / (10 + t)) with t = updates so far, so that the first steps do not average against the
+        initial weights for 1 / (1 - decay) steps.  buffers: 'ema' averages the BatchNorm running statistics like the parameters,
+        'copy' takes the net's own.
+        The update count, the count of held steps and the weight of the step live on the device (self._state, a pa_ema_state): the fp16
+        build decides there whether the optimizer's step is taken, and update(optimizer) reads that optimizer's flag there, so the
+        average does not move, and the warm-up count does not advance, on a skipped step.  updates() / held() read them (synchronising).
+        Several GPUs: every rank holds the same parameters after the step (the gradient is summed before it), so every rank forms the
+        same average without any exchange; the BatchNorm statistics are per rank, in the average as in the net.
+        Create it after the checkpoint load and broadcast_parameters, or call reset() after them.
+        The average is fp32: at decay 0.9999 an increment (1 - decay) (p - ema) below half an ulp of the average is lost."""
+        if not 0 <= float(decay) < 1:
+            raise ValueError('decay must be in [0, 1)')
+        if buffers not in ('ema', 'copy'):
+            raise ValueError("buffers must be 'ema' or 'copy'")
+        self.net, self.decay, self.warmup, self.buffers = net, float(decay), bool(warmup), buffers
+        net._ensure_table()
+        self.module = net._twin()
+        self.module._ensure_table()
+        self.module.eval()
+        self._state = torch.zeros(8, dtype=torch.int32, device=net.flat_params.device)
+        self.reset()
+
+    def reset(self):
+        """the twin becomes a bit-exact copy of the net again (parameters, buffers, num_batches_tracked) and the counts go to 0"""
+        m = self.module
+        m.flat_params.copy_(self.net.flat_params)
+        m.flat_buffers.copy_(self.net.flat_buffers)
+        m._nbt = self.net._nbt
+        self._state.zero_()
+        m.weights_changed()
+
+    def update(self, optimizer=None):
+        """Call after optimizer.step(), on the same stream: one prologue that reads the optimizer's skip flag (None: every call
+        averages), one launch over the parameters, one over the buffers.  The twin's 16-bit weight copies are re-packed at its next
+        use, not here."""
+        m, net = self.module, self.net
+        flag = optimizer.skip_flag_ptr() if optimizer is not None else None
+        check(lib().pa_ema_advance(ptr(self._state), self.decay, int(self.warmup), flag, stream()), 'pa_ema_advance')
+        check(lib().pa_ema_lerp(ptr(m.flat_params), ptr(net.flat_params), net.flat_params.numel(), ptr(self._state), 0, stream()), 'pa_ema_lerp')
+        check(lib().pa_ema_lerp(ptr(m.flat_buffers), ptr(net.flat_buffers), net.flat_buffers.numel(), ptr(self._state),
+                                1 if self.buffers == 'copy' else 0, stream()), 'pa_ema_lerp')
+        m._nbt = net._nbt
+        m.weights_changed()
+
+    def _counts(self):
+        updates, held = C.c_longlong(0), C.c_longlong(0)
+        check(lib().pa_ema_counts(ptr(self._state), C.byref(updates), C.byref(held), stream()), 'pa_ema_counts')
+        return int(updates.value), int(held.value)
+
+    def updates(self):
+        """averaging steps applied so far, read from the device: synchronises the stream"""
+        return self._counts()[0]
+
+    def held(self):
+        """update() calls that left the average where it was because the optimizer had skipped its step (fp16 build)"""
+        return self._counts()[1]
+
+    def state_dict(self):
+        return {'decay': self.decay, 'warmup': self.warmup, 'buffers': self.buffers, 'updates': self.updates(), 'module': self.module.state_dict()}
+
+    def load_state_dict(self, sd):
+        """the options, the averaged weights and the update count (back on the device: pa_ema_set_updates) of state_dict()"""
+        decay, buffers = float(sd['decay']), sd['buffers']
+        if not 0 <= decay < 1 or buffers not in ('ema', 'copy'):
+            raise ValueError('ModelEma.load_state_dict: decay %r / buffers %r' % (sd['decay'], buffers))
+        self.decay, self.warmup, self.buffers = decay, bool(sd['warmup']), buffers
+        self.module.load_state_dict(sd['module'])
+        self._state.zero_()
+        check(lib().pa_ema_set_updates(ptr(self._state), int(sd['updates']), stream()), 'pa_ema_set_updates')
+
+
+def make_ema(opt, net):
+    """The weight average the command line asks for (options/train_options.py: --ema_decay D --ema_warmup 0|1 --ema_buffers ema|copy);
+    None with --ema_decay 0, the default: no twin, no launch."""
+    decay = float(getattr(opt, 'ema_decay', 0) or 0)
+    if decay == 0:
+        return None
+    return ModelEma(net, decay=decay, warmup=bool(getattr(opt, 'ema_warmup', 0)), buffers=getattr(opt, 'ema_buffers', 'ema'))
 
 
 def make_optimizer(opt, net, lr, overlap=False):
