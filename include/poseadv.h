@@ -365,6 +365,18 @@ int pa_ema_counts(const pa_ema_state* state, long long* updates, long long* held
 /* state->updates = updates, on `stream` (loading a file); the other words stay. */
 int pa_ema_set_updates(pa_ema_state* state, long long updates, void* stream);
 
+/* Gradient accumulation over micro-batches (utils.optim: optimizer.accumulate() after a backward pass, then step()).  No reference
+ * counterpart: the reference steps on every batch.
+ * dst[i] = a[i] + b[i] for i < n: one fp32 addition per element, no scaling, no atomics, so the same input gives the same bits and a
+ * group's sum is ((g1 + g2) + g3) + ... in the order of the calls; the mean is taken by the gscale of the step that follows.  inf, NaN
+ * and denormal operands and results are ordinary values (inf + -inf = NaN).
+ * b == NULL: a copy, dst[i] = a[i] (the first micro-batch of a group); with dst == a as well: returns 0, launches nothing.
+ * dst may be exactly a or exactly b (in place), and a may be b; ranges that overlap in any other way are refused.  The pointers need
+ * 4-byte alignment only: with all three 16-byte aligned (the flat arrays are) the kernel moves 16-byte chunks, otherwise (a view into a
+ * flat array) single floats.
+ * Errors (non-zero, pa_last_error set, nothing launched): a NULL dst or a, n < 1, ranges that overlap in part. */
+int pa_grad_accumulate(float* dst, const float* a, const float* b, size_t n, void* stream);
+
 /* ---------------------------------------------------------------- operator level ---------- */
 /* One residual bottleneck block _Residual(C, C) (models/asn_stacked_hg.py:11-49), forward + backward,
  * NCHW fp32 in/out, parameters in the block's own state_dict order (flat fp32).  Used by the parity

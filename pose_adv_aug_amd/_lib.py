@@ -124,6 +124,7 @@ _PROTOS = {
     'pa_ema_lerp': (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     'pa_ema_counts': (_i, [_vp, _vp, _vp, _vp]),
     'pa_ema_set_updates': (_i, [_vp, C.c_longlong, _vp]),
+    'pa_grad_accumulate': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'pa_residual_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'pa_residual_fwd_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'pa_conv2d_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -4,6 +4,7 @@
 #include "warp_bwd.h"
 #include "soft_argmax.h"
 #include "ema.h"
+#include "grad_accum.h"
 #include <stdio.h>
 #include <string.h>
 #include <new>
@@ -330,6 +331,23 @@ int pa_ema_set_updates(pa_ema_state* state, long long updates, void* s) {
     if (!state) { pa_set_error_msg("pa_ema_set_updates: state is NULL"); return 1; }
     if (updates < 0 || updates > 2147483647LL) { pa_set_error_msg("pa_ema_set_updates: updates must be in 0 .. 2^31 - 1"); return 1; }
     TRY(pa_launch_ema_set_updates(reinterpret_cast<PaEmaState*>(state), (int)updates, ST(s))); return 0;
+}
+// Gradient accumulation (grad_accum.hip; utils.optim accumulate() / step()): dst = a + b, or dst = a with b == NULL.  Every pair of the
+// three ranges is either the same range or disjoint; an argument error launches nothing.
+int pa_grad_accumulate(float* dst, const float* a, const float* b, size_t n, void* s) {
+    g_err[0] = 0;
+    NEED_PTR("pa_grad_accumulate", dst); NEED_PTR("pa_grad_accumulate", a);
+    if (n < 1 || n > ((size_t)-1) / sizeof(float)) { pa_set_error_msg("pa_grad_accumulate: n must be >= 1 (and n floats addressable)"); return 1; }
+    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+    const uintptr_t r[3] = { reinterpret_cast<uintptr_t>(dst), reinterpret_cast<uintptr_t>(a), reinterpret_cast<uintptr_t>(b) };
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j) {
+            if (!r[j] || r[i] == r[j]) continue;          // (b == NULL: the copy form; the same range: in place, or a read twice)
+            const uintptr_t lo = r[i] < r[j] ? r[i] : r[j], hi = r[i] < r[j] ? r[j] : r[i];
+            if (hi - lo < bytes) { pa_set_error_msg("pa_grad_accumulate: dst, a and b overlap in part (each pair must be the same range or disjoint)"); return 1; }
+        }
+    if (!b && dst == a) return 0;
+    TRY(pa_launch_grad_accumulate(dst, a, b, n, ST(s))); return 0;
 }
 int pa_nchw_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, void* s) {
     g_err[0] = 0;

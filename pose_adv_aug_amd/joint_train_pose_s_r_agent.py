@@ -50,39 +50,48 @@ def sample_bins(logits, seed, step, slot):
     return probs, idx
 
 
-def pose_step(hg, optimizer_hg, data, ema=None):
-    """the common tail of both branches of train_hg (:229-245 / :282-299); ema (utils.optim.ModelEma of hg, None: off) follows the step"""
+def pose_step(hg, optimizer_hg, data, ema=None, accumulate=False):
+    """the common tail of both branches of train_hg (:229-245 / :282-299); ema (utils.optim.ModelEma of hg, None: off) follows the step.
+    accumulate: True for a micro-batch that does not end its group (--accum_steps): optimizer_hg.accumulate() in place of the step"""
     loss, _ = hg.loss_and_backward(img4=data['img4'], pts=data['pts'])
-    optimizer_hg.step()
-    if ema is not None:
-        ema.update(optimizer_hg)
+    if accumulate:
+        optimizer_hg.accumulate()
+    else:
+        optimizer_hg.step()
+        if ema is not None:
+            ema.update(optimizer_hg)
     pckh, _ = hg.pckh_origin_res(data['c'], data['s'], data['r'], data['grnd_pts'], data['normalizer'])
     return loss, pckh[0]
 
 
-def train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=0, ema=None):
+def train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=0, ema=None, accumulate=False):
     """one iteration of train_hg (:213-299).  Returns (kind, loss, pckh) as device scalars."""
     hg.train()
     agent_sr.eval()
     if i % 2 == 0:                                                   # regular augmentation (:224-245)
-        loss, pckh = pose_step(hg, optimizer_hg, augmenter.regular(batch), ema)
+        loss, pckh = pose_step(hg, optimizer_hg, augmenter.regular(batch), ema, accumulate)
         return 'regular', loss, pckh
     std = augmenter.standard(batch)                                  # img_std (:247)
     ls, lr = hg(asn=agent_sr, img4=std['img4'], is_half_hg=True, is_aug=True)       # (:250)
     _, si = sample_bins(ls, _bin_seed(seed, augmenter), i, BIN_SLOTS_TRAIN_HG[0])
     _, ri = sample_bins(lr, _bin_seed(seed, augmenter), i, BIN_SLOTS_TRAIN_HG[1])
-    loss, pckh = pose_step(hg, optimizer_hg, augmenter.agent(batch, si, ri, mode=1), ema)     # load_batch_data(separate_s_r=False)
+    loss, pckh = pose_step(hg, optimizer_hg, augmenter.agent(batch, si, ri, mode=1), ema, accumulate)     # load_batch_data(separate_s_r=False)
     return 'agent', loss, pckh
 
 
 def train_hg(batches, hg, optimizer_hg, agent_sr, augmenter, epoch, opt, log=print, ema=None):
     """:195-315.  All six meters see every iteration (device-side sums, split by the kind of step); the host synchronises
-    every print_freq steps only."""
+    every print_freq steps only.
+    opt.accum_steps N > 1: the pose optimizer steps on every N-th iteration and on the last (utils.optim.accum_plan); with N = 2 one
+    step takes the mean gradient of a regular and an agent-augmented micro-batch.  The agent's own steps keep one batch each."""
+    from .stack_hg import accum_plan_for
     meters = None
     n = len(batches)
     with_ema = {} if ema is None else {'ema': ema}            # (off: the call the loop has always made)
+    plan = accum_plan_for(opt, n, optimizer_hg, log)
     for i, batch in enumerate(batches):
-        kind, loss, pckh = train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=epoch, **with_ema)
+        with_accum = {'accumulate': True} if plan is not None and not plan[i][0] else {}
+        kind, loss, pckh = train_hg_step(i, hg, optimizer_hg, agent_sr, augmenter, batch, seed=epoch, **with_ema, **with_accum)
         if meters is None:
             meters = DeviceMeters(METER_NAMES, loss.device)
         tag = ('loss_hg_regular', 'pckhs_regular') if kind == 'regular' else ('loss_hg_sr', 'pckhs_sr')

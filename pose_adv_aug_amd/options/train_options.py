@@ -31,6 +31,9 @@ class TrainOptions(BaseOptions):
         p.add_argument('--ema_decay', type=float, default=0., help='decay of the weight EMA that is validated and saved (0: off)')
         p.add_argument('--ema_warmup', type=int, default=0, choices=(0, 1), help='1: decay min(D, (1 + t) / (10 + t)) over the first updates')
         p.add_argument('--ema_buffers', type=str, default='ema', choices=('ema', 'copy'), help='BatchNorm running statistics of the EMA: averaged, or copied')
+        # gradient accumulation (utils/optim.py accumulate(), accum_plan): the optimizer steps on the mean gradient of N micro-batches of
+        # --bs each; 1 = off, the reference's recipe: a step per batch and no launch added
+        p.add_argument('--accum_steps', type=int, default=1, help='micro-batches of --bs per optimizer step (1: off)')
         p.add_argument('--bs', type=int, default=12, help='mini-batch size')
         p.add_argument('--load_checkpoint', type=_bool, default=False, help='resume from checkpoint model')
         p.add_argument('--load_checkpoint_pose', type=_bool, default=False, help='use checkpoint model')
@@ -61,4 +64,6 @@ class TrainOptions(BaseOptions):
             self.parser.error('--coord_loss must be >= 0 and --coord_beta > 0')
         if not 0 <= o.ema_decay < 1:
             self.parser.error('--ema_decay must be in [0, 1) (0: off)')
+        if o.accum_steps < 1:
+            self.parser.error('--accum_steps must be >= 1 (1: off)')
         return BaseOptions.parse(self, args)

@@ -144,6 +144,10 @@ def main(argv=None):
     from .utils.util import ASNTrainHistory
     from .models.asn_stacked_hg import create_hg, create_asn
     opt = TrainOptions().parse(argv)
+    if opt.accum_steps != 1:
+        # the agent's target is built from the PCKh of ONE batch under its own augmentation: its steps keep one batch each
+        raise SystemExit('pretrain_s_r_agent: --accum_steps %d is not supported here (the agent steps on one batch at a time); it applies '
+                         'to the pose net in stack_hg and in the joint loop' % opt.accum_steps)
     exp = os.path.join(opt.exp_dir, opt.exp_id)
     sr_dir = os.path.join(exp, opt.sr_dir + '-' + opt.load_prefix_pose[0:-1]) if opt.load_prefix_pose != '' else os.path.join(exp, opt.sr_dir)
     os.makedirs(sr_dir, exist_ok=True)

@@ -12,7 +12,7 @@ import torch.distributed as dist
 
 from .data import AugmentAhead, Augmenter, BatchFeed, DeviceBatch, num_samples, with_next
 from .models.asn_stacked_hg import create_hg
-from .utils.optim import make_ema, make_optimizer
+from .utils.optim import accum_plan, make_ema, make_optimizer
 from .utils.util import AverageMeter, DeviceMeters, PoseTrainHistory, adjust_lr
 
 PCK_IDX = [0, 1, 2, 3, 4, 5, 10, 11, 14, 15]            # stack-hg.py:89
@@ -68,7 +68,18 @@ def coord_criterion(weight, beta=1.0):
     return criterion
 
 
-def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, criterion=None, heat_layout='nchw', ema=None):
+def _step_or_accumulate(optimizer, ema, accumulate):
+    """what follows a backward pass: the optimizer step and the weight EMA behind it, or -- a micro-batch that does not end its group
+    (--accum_steps) -- optimizer.accumulate() alone: the weights do not move, so neither does their average"""
+    if accumulate:
+        optimizer.accumulate()
+        return
+    optimizer.step()
+    if ema is not None:
+        ema.update(optimizer)
+
+
+def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, criterion=None, heat_layout='nchw', ema=None, accumulate=False):
     """stack-hg.py:134-180 for one batch.  Returns device scalars (loss, pckh, pckh_origin_res).
     data: the batch's augmented input if it was prepared ahead (data.AugmentAhead), else it is made here.
     criterion: a callable (outs, data) -> 0-d loss tensor over the per-stack heat maps of net.forward_autograd (your own loss, e.g.
@@ -76,7 +87,9 @@ def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, crit
     what every shipped loop passes): the built-in fused MSE step.  A data['img4'] that requires grad gets its .grad from that backward
     pass (forward_autograd: d loss / d image, NHWC4).  heat_layout: the layout of the maps the criterion receives ('nhwc': views of the
     engine's own buffers, forward_autograd(layout='nhwc')).
-    ema (utils.optim.ModelEma of `net`, None: off): updated behind the optimizer step, on the device (held when the step was skipped)."""
+    ema (utils.optim.ModelEma of `net`, None: off): updated behind the optimizer step, on the device (held when the step was skipped).
+    accumulate: True for a micro-batch that does not end its group (--accum_steps): optimizer.accumulate() in place of step(), no EMA
+    update; the meters are this micro-batch's either way."""
     if data is None:
         data = augmenter.regular(batch)
     def meters():
@@ -87,9 +100,7 @@ def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, crit
         outs = net.forward_autograd(img4=data['img4'], pts=data['pts'], layout=heat_layout)
         loss = criterion(outs, data)
         loss.backward()
-        optimizer.step()
-        if ema is not None:
-            ema.update(optimizer)
+        _step_or_accumulate(optimizer, ema, accumulate)
         if not want_pckh:
             return loss.detach(), None, None
         pckh, pckh_o = meters()
@@ -98,15 +109,11 @@ def train_step(net, optimizer, augmenter, batch, want_pckh=True, data=None, crit
         # the meters read the forward pass's heat maps only: launched between the two passes they run beside the backward pass on the
         # engine's meter stream (100 us of short launches that otherwise sit between two steps); same values
         loss, _ = net.loss_and_backward(img4=data['img4'], pts=data['pts'], after_forward=meters)
-        optimizer.step()
-        if ema is not None:
-            ema.update(optimizer)
+        _step_or_accumulate(optimizer, ema, accumulate)
         pckh, pckh_o = net.after_forward_result
         return loss, pckh[0], pckh_o[0]
     loss, _ = net.loss_and_backward(img4=data['img4'], pts=data['pts'])
-    optimizer.step()
-    if ema is not None:
-        ema.update(optimizer)
+    _step_or_accumulate(optimizer, ema, accumulate)
     if not want_pckh:
         return loss, None, None
     pckh, pckh_o = meters()
@@ -134,24 +141,46 @@ def warn_skipped_steps(optimizer, log=print, name=''):
     return n - seen
 
 
+_EFFECTIVE_LOGGED = weakref.WeakKeyDictionary()      # optimizer -> the effective batch has been logged
+
+
+def accum_plan_for(opt, n, optimizer, log=print):
+    """utils.optim.accum_plan for an epoch of n iterations, or None with --accum_steps 1 (the default: the loop as it has always run).
+    Says once per optimizer, i.e. once per run, what the effective batch is."""
+    N = int(getattr(opt, 'accum_steps', 1) or 1)
+    if N == 1:
+        return None
+    if optimizer not in _EFFECTIVE_LOGGED:
+        _EFFECTIVE_LOGGED[optimizer] = True
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        bs = int(getattr(opt, 'bs', 0) or 0)
+        log('gradient accumulation: %d micro-batches per optimizer step; effective batch %d x %d x %d rank(s) = %d '
+            '(BatchNorm statistics stay per micro-batch)' % (N, bs, N, world, bs * N * world))
+    return accum_plan(n, N)
+
+
 def train(batches, net, optimizer, augmenter, epoch, opt, log=print, criterion=None, ema=None):
     """stack-hg.py:124-189 over a sized feed of DeviceBatches (a list, data.BatchFeed, MPII.batches()).  The meters see
     EVERY iteration (:171-180) through device-side sums; the host synchronises only every print_freq steps.
-    criterion (None: the fused MSE step): a loss of the joint-minor maps, train_step(criterion=..., heat_layout='nhwc')."""
+    criterion (None: the fused MSE step): a loss of the joint-minor maps, train_step(criterion=..., heat_layout='nhwc').
+    opt.accum_steps N > 1: the optimizer steps on every N-th iteration and on the last of the epoch, on the mean gradient of the
+    micro-batches since its last step (utils.optim.accum_plan); meters and log lines stay per iteration."""
     net.train()
     n = len(batches)
     meters = None
     ahead = AugmentAhead(augmenter)
     with_ema = {} if ema is None else {'ema': ema}            # (off: the call the loop has always made)
+    plan = accum_plan_for(opt, n, optimizer, log)
     for i, (batch, nxt) in enumerate(with_next(batches)):
         if i == 0:
             ahead.start(batch)
         data = ahead.take()
         ahead.start(nxt)                                   # the next batch's crop runs beside this step's forward pass
+        with_accum = {'accumulate': True} if plan is not None and not plan[i][0] else {}
         if criterion is None:
-            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, **with_ema)
+            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, **with_ema, **with_accum)
         else:
-            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, criterion=criterion, heat_layout='nhwc', **with_ema)
+            loss, pckh, pckh_o = train_step(net, optimizer, augmenter, batch, data=data, criterion=criterion, heat_layout='nhwc', **with_ema, **with_accum)
         if meters is None:
             meters = DeviceMeters(('loss', 'pckh', 'pckh_origin_res'), loss.device)
         meters.update({'loss': loss, 'pckh': pckh, 'pckh_origin_res': pckh_o})

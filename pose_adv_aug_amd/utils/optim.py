@@ -10,7 +10,11 @@ Adam / AdamW (torch.optim.Adam's formula with weight decay coupled or decoupled,
 (pa_adam_step) whose step count and bias-correction constants live on the device.  make_optimizer picks one from the command line.
 
 ModelEma: an exponential moving average of the weights in a twin net, updated on the device behind the step (pa_ema_advance, pa_ema_lerp);
-its update count and the decision to hold on a skipped step live on the device, next to the optimizer's flag.  make_ema: from the command line."""
+its update count and the decision to hold on a skipped step live on the device, next to the optimizer's flag.  make_ema: from the command line.
+
+Gradient accumulation: optimizer.accumulate() after a backward pass instead of step() folds flat_grads into a private sum
+(pa_grad_accumulate); the step() that ends the group adds the sum to its own gradient and takes the mean through gscale.
+accum_plan: which iterations of an epoch step (--accum_steps)."""
 import ctypes as C
 import os
 
@@ -50,9 +54,36 @@ class _FlatOptimizer(object):
         self.max_grad_norm = max_grad_norm
         self._norm_ws = self._norm_out = None           # the norm's scratch and its {norm, coefficient} output
         self._clipped = False
+        # gradient accumulation: the fp32 sum of the micro-batch gradients since the last step (allocated by the first accumulate()), and
+        # how many it holds
+        self._overlap, self._acc, self.pending = bool(overlap), None, 0
 
     def zero_grad(self):
+        """also drops a pending group of accumulate() calls"""
         self.net.zero_grad()
+        self.pending = 0
+
+    def accumulate(self):
+        """Call after a backward pass INSTEAD of step(): this micro-batch's flat_grads joins the sum of its group (every backward pass
+        overwrites flat_grads; two of them before a step() do not add up by themselves, as torch's .grad does).  The first of a group
+        is a copy, the later ones _acc = _acc + flat_grads: one launch of pa_grad_accumulate, fp32, in the order of the calls.  The step()
+        that ends the group adds _acc to its own gradient and divides by the group's size (_exchanged_gscale); the gradient is exchanged
+        between ranks there, once per group.  BatchNorm statistics stay per micro-batch."""
+        if self._overlap:
+            raise ValueError('accumulate() on an optimizer created with overlap=True: its per-stack buckets would exchange the gradient '
+                             'of every micro-batch; create the optimizer with overlap=False')
+        grads = self.net.flat_grads
+        if self._acc is None:
+            self._acc = torch.empty_like(grads)
+        first = self.pending == 0
+        check(lib().pa_grad_accumulate(ptr(self._acc), ptr(grads if first else self._acc), None if first else ptr(grads), grads.numel(), stream()),
+              'pa_grad_accumulate')
+        self.pending += 1
+
+    def _warn_pending(self):
+        if self.pending:
+            import warnings
+            warnings.warn('state_dict(): %d accumulated micro-batch gradient(s) are pending and are NOT saved; call step() first' % self.pending)
 
     def allreduce_grads(self):
         """Sum the flat gradient over all ranks (RCCL when the process group backend is nccl)."""
@@ -98,9 +129,18 @@ class _FlatOptimizer(object):
         return 1.0 / dist.get_world_size()
 
     def _exchanged_gscale(self):
-        """finish the gradient exchange; 1/world, and the fp16 build's gradient scale divided out"""
+        """finish the gradient exchange; 1/world, and the fp16 build's gradient scale divided out.  With k micro-batches pending
+        (accumulate()): first flat_grads = _acc + flat_grads, so that the exchange, the norm, the step and the fp16 build's finite check
+        read the group's sum where they read every gradient, and the mean over the k + 1 goes into gscale."""
+        k = self.pending
+        if k:
+            grads = self.net.flat_grads
+            check(lib().pa_grad_accumulate(ptr(grads), ptr(self._acc), ptr(grads), grads.numel(), stream()), 'pa_grad_accumulate')
         world_scale = self._finish_exchange() if self._works else self.allreduce_grads()
-        return world_scale / _lib.grad_scale()
+        gscale = world_scale / _lib.grad_scale()
+        if k:
+            gscale, self.pending = gscale / (k + 1), 0
+        return gscale
 
     def _clip_coef(self, n, gscale):
         """norm and clip coefficient of the exchanged gradient (max_grad_norm): the pointer of the device float the step reads, or None"""
@@ -199,6 +239,7 @@ class RMSprop(_FlatOptimizer):
 
     # torch.optim-compatible (de)serialisation: per-parameter state keyed by index, in parameters() order
     def state_dict(self):
+        self._warn_pending()
         state = {}
         for i, (name, shape, off, numel, kind) in enumerate(t for t in self.net._table if t[4] == 0):
             state[i] = {'step': self.steps, 'square_avg': self.square_avg[off:off + numel].view(shape).clone()}
@@ -324,6 +365,7 @@ class Adam(_FlatOptimizer):
 
     # torch.optim.Adam's format: per-parameter state keyed by index, in parameters() order; `step` a 0-dim float32 CPU tensor
     def state_dict(self):
+        self._warn_pending()
         steps = self.steps_taken()
         state = {}
         for i, (name, shape, off, numel, kind) in enumerate(self._params()):
@@ -485,6 +527,17 @@ def make_ema(opt, net):
     if decay == 0:
         return None
     return ModelEma(net, decay=decay, warmup=bool(getattr(opt, 'ema_warmup', 0)), buffers=getattr(opt, 'ema_buffers', 'ema'))
+
+
+def accum_plan(n_batches, accum_steps):
+    """--accum_steps N over an epoch of n_batches iterations: per iteration (steps, group size so far).  Iteration i ends its group with
+    an optimizer step when i % N == N - 1 or i is the last of the epoch (a short trailing group is stepped with its real size, so an
+    epoch never ends with a gradient pending); every other iteration calls accumulate().  The sizes at the stepping iterations sum to
+    n_batches.  Pure host logic."""
+    n, N = int(n_batches), int(accum_steps)
+    if N < 1:
+        raise ValueError('accum_steps must be >= 1')
+    return [(i % N == N - 1 or i == n - 1, i % N + 1) for i in range(n)]
 
 
 def make_optimizer(opt, net, lr, overlap=False):
