@@ -1,7 +1,7 @@
 """A recording stand-in for libposeadv_hip.so, for CPU tests of the HOST control flow only (what is called, in which order,
 with which arguments, on which rank).  It computes nothing of the product: every pa_* call is logged and returns 0; the few
-calls the control flow depends on (state-dict table, gradient fill, RMSprop arithmetic on the flat arrays) are emulated on
-CPU tensors.  Installed by `install()` into the already imported modules of the package -- test infrastructure, never
+calls the control flow depends on (state-dict table, gradient fill, the fold of gradient accumulation, the gradient norm, stand-ins
+for the RMSprop / Adam / EMA arithmetic on the flat arrays) are emulated on CPU tensors.  Installed by `install()` into the already imported modules of the package -- test infrastructure, never
 reachable from the product path."""
 import sys
 
@@ -108,6 +108,64 @@ class FakeLib(object):
     def pa_rmsprop_step_state(self, p, g, v, n, lr, alpha, eps, gscale, state, stream):
         assert state.numel() == 2 and state.dtype == torch.int32          # the optimizer's own {flag, skipped} pair
         return self.pa_rmsprop_step(p, g, v, n, lr, alpha, eps, gscale, stream)
+
+    # ---- options, accumulation, Adam and the EMA: logged with the addresses of their arrays (which array went where) and their scalars;
+    # the arithmetic is a stand-in that depends on every operand, so that replicas agree exactly when the operands do
+    @staticmethod
+    def _at(t):
+        return None if t is None else t.data_ptr()
+
+    def pa_grad_accumulate(self, dst, a, b, n, stream):
+        self.log.append(('pa_grad_accumulate', (self._at(dst), self._at(a), self._at(b), n, stream)))
+        dst.copy_(a.clone() if b is None else a + b)                       # really adds: the fold is part of the control flow
+        return 0
+
+    def pa_grad_norm_workspace_bytes(self, n):
+        return 64
+
+    def pa_grad_norm(self, g, n, gscale, max_norm, ws, out2, stream):
+        self.log.append(('pa_grad_norm', (self._at(g), n, gscale, max_norm, stream)))
+        norm = float((g.double() * gscale).pow(2).sum().sqrt())
+        out2[0], out2[1] = norm, min(1.0, max_norm / (norm + 1e-6))
+        return 0
+
+    def pa_rmsprop_step_opts(self, opts, p, g, v, buf, ga, n, gscale, coef, state, stream):
+        o = opts._obj
+        self.log.append(('pa_rmsprop_step_opts', (n, gscale, self._at(coef), stream, (o.lr, o.momentum, o.weight_decay, o.centered))))
+        gg = g * gscale * (1.0 if coef is None else float(coef[0])) + o.weight_decay * p
+        v.mul_(o.alpha).addcmul_(gg, gg, value=1 - o.alpha)
+        p.addcdiv_(gg, v.sqrt().add_(o.eps), value=-o.lr)
+        return 0
+
+    def pa_adam_step(self, opts, p, g, m, v, vmax, n, gscale, coef, state, stream):
+        o = opts._obj
+        assert state.numel() == 8 and state.dtype == torch.int32          # the optimizer's own pa_adam_state
+        self.log.append(('pa_adam_step', (n, gscale, self._at(coef), stream, (o.lr, o.weight_decay, o.amsgrad, o.decoupled), self._at(g))))
+        gg = g * gscale * (1.0 if coef is None else float(coef[0]))
+        state[2] += 1
+        m.mul_(o.beta1).add_(gg, alpha=1 - o.beta1)
+        v.mul_(o.beta2).addcmul_(gg, gg, value=1 - o.beta2)
+        p.mul_(1 - o.lr * o.weight_decay if o.decoupled else 1.0).addcdiv_(m, v.sqrt().add_(o.eps), value=-o.lr)
+        return 0
+
+    def pa_adam_steps(self, state, steps, skipped, stream):
+        steps._obj.value, skipped._obj.value = int(state[2]), int(state[1])
+        return 0
+
+    def pa_ema_advance(self, state, decay, warmup, flag, stream):
+        self.log.append(('pa_ema_advance', (decay, warmup, self._at(flag), stream)))
+        state[0] += 1
+        self._ema_w = 1.0 - decay
+        return 0
+
+    def pa_ema_lerp(self, ema, src, n, state, copy, stream):
+        self.log.append(('pa_ema_lerp', (self._at(ema), self._at(src), n, copy, stream)))
+        ema.copy_(src) if copy else ema.add_(src - ema, alpha=self._ema_w)
+        return 0
+
+    def pa_ema_counts(self, state, updates, held, stream):
+        updates._obj.value, held._obj.value = int(state[0]), int(state[1])
+        return 0
 
 
 def install(rank):

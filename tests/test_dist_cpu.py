@@ -69,8 +69,13 @@ def test_flat_gradient_allreduce_world4():
     assert torch.allclose(out[0][0], pref)
 
 
-def _main_worker(rank, world, init, exp_dir, out):
-    """stack_hg.main() -- the REAL host control flow -- on 2 gloo ranks with the engine stubbed at the C ABI."""
+KEPT = ('pa_sample_aug', 'pa_rmsprop_step', 'all_reduce', 'pa_net_bind')
+KEPT_OPTS = KEPT + ('pa_grad_accumulate', 'pa_grad_norm', 'pa_adam_step', 'pa_rmsprop_step_opts', 'pa_ema_advance', 'pa_ema_lerp')
+
+
+def _main_worker(rank, world, init, exp_dir, out, extra=(), kept=KEPT):
+    """stack_hg.main() -- the REAL host control flow -- on 2 gloo ranks with the engine stubbed at the C ABI.  extra: further command-line
+    arguments; kept: the calls whose arguments travel back with the log."""
     # gloo named explicitly: the stub's tensors live on the CPU, and init_distributed picks nccl (RCCL) whenever a GPU is visible
     set_env(rank, world, init, POSEADV_DIST_BACKEND='gloo')
     from tests import abi_stub
@@ -94,10 +99,10 @@ def _main_worker(rank, world, init, exp_dir, out):
         captured['net'] = orig_create(*a, **kw)
         return captured['net']
     stack_hg.create_hg = create
-    stack_hg.main(['--exp_dir', exp_dir, '--exp_id', 'dp', '--bs', '2', '--nEpochs', '1', '--is_train', '1', '--print_freq', '2'])
+    stack_hg.main(['--exp_dir', exp_dir, '--exp_id', 'dp', '--bs', '2', '--nEpochs', '1', '--is_train', '1', '--print_freq', '2'] + list(extra))
     net = captured['net']
-    out[rank] = dict(log=[(n, a if n in ('pa_sample_aug', 'pa_rmsprop_step', 'all_reduce', 'pa_net_bind') else None) for n, a in fake.log],
-                     params=net.flat_params.clone(), buffers=net.flat_buffers.clone(), saves=saves)
+    out[rank] = dict(log=[(n, a if n in kept else None) for n, a in fake.log],
+                     params=net.flat_params.clone(), buffers=net.flat_buffers.clone(), saves=saves, grads_at=net.flat_grads.data_ptr())
     dist.barrier()
     dist.destroy_process_group()
 
@@ -143,3 +148,59 @@ def test_training_main_on_two_ranks_with_the_engine_stubbed_at_the_abi(tmp_path)
     assert len(r0['saves']) == 1 and r0['saves'][0].endswith('-0.pth.tar') and r1['saves'] == []
     files = os.listdir(os.path.join(str(tmp_path), 'dp'))
     assert any(f.endswith('-0.pth.tar') for f in files) and any(f.endswith('-0-preds.mat') for f in files) and 'train-log.txt' in files
+
+
+def test_adamw_with_clipping_and_accumulation_on_two_ranks_with_the_engine_stubbed_at_the_abi(tmp_path):
+    """--optimizer adamw --clip_grad_norm 1 --accum_steps 2 through the same host code on two ranks: 4 synthetic batches per rank, so two
+    groups of 2.  A micro-batch that does not end its group: one pa_grad_accumulate into the optimizer's own sum and NO all-reduce of the
+    gradient.  The one that ends it: the fold with dst == flat_grads, then exactly ONE all-reduce of the whole flat gradient, then
+    pa_grad_norm with gscale = 1 / (2 ranks x 2 micro-batches), then pa_adam_step with the same gscale and the coefficient's device
+    pointer, then the weight re-pack; with --ema_decay 0.9 beside them, the EMA's prologue (with the optimizer's flag word) and its two
+    launches behind every optimizer step and none behind a micro-batch that only accumulates.  Replicas bit-identical at the end (the
+    stub's Adam depends on every operand)."""
+    mgr = mp.Manager()
+    out = mgr.dict()
+    extra = ['--optimizer', 'adamw', '--clip_grad_norm', '1', '--accum_steps', '2', '--ema_decay', '0.9']
+    mp.spawn(_main_worker, args=(2, file_init_method(), str(tmp_path), out, extra, KEPT_OPTS), nprocs=2, join=True)
+    r0, r1 = out[0], out[1]
+    assert torch.equal(r0['params'], r1['params'])
+    for r in (r0, r1):
+        log = r['log']
+        names = [n for n, _ in log]
+        assert 'pa_rmsprop_step' not in names and 'pa_rmsprop_step_opts' not in names
+        starts = [i for i, n in enumerate(names) if n == 'pa_hg_backward']
+        assert len(starts) == 4
+        train_end = max(i for i, n in enumerate(names) if n == 'pa_adam_step') + 1
+        accs = set()
+        for k, i in enumerate(starts):
+            end = starts[k + 1] if k + 1 < len(starts) else len(names)
+            seg = log[i:end]
+            seg_names = [n for n, _ in seg]
+            whole = [j for j, (n, a) in enumerate(seg) if n == 'all_reduce' and a[0] == 40]
+            folds = [j for j, n in enumerate(seg_names) if n == 'pa_grad_accumulate']
+            assert len(folds) == 1, seg_names
+            dst, a, b, n, stream = seg[folds[0]][1]
+            assert n == 40
+            if k % 2 == 0:                                   # does not end its group
+                assert whole == [] and 'pa_adam_step' not in seg_names and 'pa_grad_norm' not in seg_names, seg_names
+                assert dst != r['grads_at'] and a == r['grads_at'] and b is None          # the first of a group: a copy into the sum
+                accs.add(dst)
+            else:
+                assert len(whole) == 1, seg_names
+                norm, step, repack = seg_names.index('pa_grad_norm'), seg_names.index('pa_adam_step'), seg_names.index('pa_net_prepare_weights')
+                assert folds[0] < whole[0] < norm < step < repack, seg_names
+                assert seg_names.count('pa_grad_norm') == 1 and seg_names.count('pa_adam_step') == 1
+                assert dst == r['grads_at'] and a in accs and b == r['grads_at']          # flat_grads = _acc + flat_grads
+                g_at, n_norm, gscale, max_norm, _ = seg[norm][1]
+                assert g_at == r['grads_at'] and n_norm == 40 and gscale == 0.25 and max_norm == 1.0
+                n_step, gscale_step, coef_at, _, (lr, wd, amsgrad, decoupled), g_step = seg[step][1]
+                assert n_step == 40 and gscale_step == 0.25 and coef_at is not None and g_step == r['grads_at'] and decoupled == 1 and amsgrad == 0
+                # --ema_decay 0.9: behind the step, the prologue with the optimizer's flag word, then parameters and buffers
+                ema = [(j, a) for j, (n, a) in enumerate(seg) if n in ('pa_ema_advance', 'pa_ema_lerp')]
+                assert [seg_names[j] for j, _ in ema] == ['pa_ema_advance', 'pa_ema_lerp', 'pa_ema_lerp'] and ema[0][0] > step, seg_names
+                assert abs(ema[0][1][0] - 0.9) < 1e-12 and ema[0][1][2] is not None and [a[2:4] for _, a in ema[1:]] == [(40, 0), (8, 0)]
+            if k % 2 == 0:
+                assert 'pa_ema_advance' not in seg_names and 'pa_ema_lerp' not in seg_names          # the weights did not move
+        assert len(accs) == 1                                # allocated once
+        assert len([1 for n, a in log[:train_end] if n == 'all_reduce' and a[0] == 40]) == 2 and names.count('pa_adam_step') == 2
+    assert len(r0['saves']) == 1 and r1['saves'] == []
