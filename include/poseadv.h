@@ -342,6 +342,53 @@ int pa_adam_steps(const pa_adam_state* state, long long* steps, long long* skipp
 /* state->step = steps, on `stream` (load_state_dict); the other words stay.  Errors: a NULL or misaligned state, steps < 0 or > INT32_MAX. */
 int pa_adam_set_steps(pa_adam_state* state, long long steps, void* stream);
 
+/* Parameter groups: one lr, one weight_decay and a frozen bit per GROUP of tensors, inside the fused steps and the norm above
+ * (torch.optim's param_groups; the reference trains with one group, stack-hg.py:51-52, so these calls have no reference counterpart).
+ * Every tensor of a flat parameter array starts on a 16-byte boundary, so a group is a property of a 16-byte CHUNK: chunk_map, a device
+ * array of pa_opt_chunk_map_bytes(n) = ceil(n / 4) bytes owned by the caller, holds the group id (0 .. ngroups - 1) of chunk i / 4;
+ * the last, partial chunk (n % 4 elements) is chunk n / 4.  groups_host: ngroups entries on the HOST, read during the call (they
+ * travel in the kernel arguments: nothing is uploaded and the array may change after the call returns).
+ * o->lr and o->weight_decay are IGNORED by the _groups calls: the groups carry them.  Every other option is the optimizer's, shared
+ * by all groups.  Per element the formula, the order of operations and the fp32 types are those of pa_rmsprop_step_opts /
+ * pa_adam_step with the chunk's group supplying lr and weight_decay (Adam: step_size_k = lr_k / bc1 and
+ * c_dec_k = (float)(1.0 - (double)lr_k * (double)wd_k) too).  A group with weight_decay == 0 executes NO decay operation; otherwise
+ * the decay is coupled or decoupled as the optimizer says.  A FROZEN chunk is skipped entirely: nothing is loaded from or stored to
+ * param or any state array, and grad is not read there (inf / NaN in it are harmless in the bf16 build).  Zero padding stays zero.
+ * pa_opt_chunk_map_host (host only, no device call): tensor t covers floats [offsets[t], offsets[t] + numels[t]); offsets are multiples
+ * of 4, ascending, non-overlapping.  Every chunk a tensor touches gets group_host[t]; a chunk no tensor touches gets the group of the
+ * tensor in front of it (group 0 in front of the first).  map_host: pa_opt_chunk_map_bytes(n) bytes; the caller uploads it.
+ * pa_adam_step_groups: the one-thread launch in front of the step behaves as pa_adam_step's and also writes group_consts[k] =
+ * lr_k / bc1 for k < ngroups (group_consts: PA_OPT_GROUPS_MAX floats on the device, owned by the caller, read by the step kernel) and
+ * state->step_size = group_consts[0]; a skipped step leaves both as they were.
+ * pa_grad_norm_groups: pa_grad_norm over the chunks whose group is not in the 16-bit mask excluded_groups (bit k = group k; the frozen
+ * groups: clip_grad_norm_ over the trainable parameters).  The grid, the order of additions and the second launch are pa_grad_norm's,
+ * so out2 equals, bit for bit, pa_grad_norm's on a copy of grad with the excluded chunks set to +0.
+ * One group that is not frozen: chunk_map and group_consts may be NULL, and the call IS pa_rmsprop_step_opts / pa_adam_step with that
+ * group's lr and weight_decay (the same launches, the same bits; a non-NULL group_consts[0] is still written).  excluded_groups == 0:
+ * pa_grad_norm, chunk_map may be NULL.
+ * Nothing is synchronised with the host; no atomics, the same input gives the same bits.
+ * Half-precision build: the finite scan in front of the step reads the WHOLE gradient, frozen chunks included: an overflow anywhere in
+ * the scaled backward pass has already propagated into the layers below it, and the scan is the only evidence of that.  One
+ * non-finite value anywhere skips the whole step (every array, step and group_consts untouched) and counts once.
+ * Errors (non-zero, pa_last_error set with the function's name in front, nothing launched): every error of the ungrouped call (without
+ * those on o->weight_decay); a NULL groups_host; ngroups outside 1 .. 16; a NULL chunk_map with ngroups > 1 or a frozen group (norm:
+ * with excluded_groups != 0); a NULL group_consts with ngroups > 1 or a frozen group; an lr or weight_decay that is negative or not
+ * finite; excluded_groups with bits at or above 16.  Map builder: a NULL pointer, ntensors < 1, ngroups outside 1 .. 16, an offset that
+ * is not a multiple of 4, tensors out of order or overlapping, a tensor that ends past n, a group id outside 0 .. ngroups - 1. */
+#define PA_OPT_GROUPS_MAX 16
+typedef struct pa_opt_group { float lr, weight_decay; int32_t frozen, reserved; } pa_opt_group;
+size_t pa_opt_chunk_map_bytes(size_t n);
+int pa_opt_chunk_map_host(const size_t* offsets_host, const size_t* numels_host, const int32_t* group_host, int ntensors,
+                          size_t n, int ngroups, uint8_t* map_host);
+int pa_rmsprop_step_groups(const pa_rmsprop_opts* o, const pa_opt_group* groups_host, int ngroups, const uint8_t* chunk_map,
+                           float* param, const float* grad, float* square_avg, float* momentum_buf, float* grad_avg, size_t n,
+                           float gscale, const float* clip_coef, int32_t* state, void* stream);
+int pa_adam_step_groups(const pa_adam_opts* o, const pa_opt_group* groups_host, int ngroups, const uint8_t* chunk_map,
+                        float* group_consts, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                        float* max_exp_avg_sq, size_t n, float gscale, const float* clip_coef, pa_adam_state* state, void* stream);
+int pa_grad_norm_groups(const float* grad, size_t n, const uint8_t* chunk_map, uint32_t excluded_groups, float gscale,
+                        float max_norm, void* workspace, float* out2, void* stream);
+
 /* Exponential moving average of the weights, updated on the device (utils.optim.ModelEma): ema += w (src - ema) after an optimizer
  * step, w = 1 - decay.  No reference counterpart: the reference validates and saves the raw weights.
  * state: 32 bytes on the device, zeroed once by the caller and owned by ONE average.  updates = averaging steps applied so far; held =

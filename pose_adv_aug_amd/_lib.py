@@ -72,6 +72,14 @@ class AdamOpts(C.Structure):
     _fields_ = [('lr', _f), ('beta1', _f), ('beta2', _f), ('eps', _f), ('weight_decay', _f), ('amsgrad', C.c_int32), ('decoupled', C.c_int32)]
 
 
+OPT_GROUPS_MAX = 16
+
+
+class OptGroup(C.Structure):
+    """pa_opt_group of include/poseadv.h (pass an array of them, on the host, to the pa_*_step_groups calls)"""
+    _fields_ = [('lr', _f), ('weight_decay', _f), ('frozen', C.c_int32), ('reserved', C.c_int32)]
+
+
 _PROTOS = {
     'pa_last_error': (C.c_char_p, []),
     'pa_version': (_i, []),
@@ -120,6 +128,11 @@ _PROTOS = {
     'pa_adam_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
     'pa_adam_steps': (_i, [_vp, _vp, _vp, _vp]),
     'pa_adam_set_steps': (_i, [_vp, C.c_longlong, _vp]),
+    'pa_opt_chunk_map_bytes': (_sz, [_sz]),
+    'pa_opt_chunk_map_host': (_i, [_vp, _vp, _vp, _i, _sz, _i, _vp]),
+    'pa_rmsprop_step_groups': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
+    'pa_adam_step_groups': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
+    'pa_grad_norm_groups': (_i, [_vp, _sz, _vp, C.c_uint32, _f, _f, _vp, _vp, _vp]),
     'pa_ema_advance': (_i, [_vp, _f, _i, _vp, _vp]),
     'pa_ema_lerp': (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     'pa_ema_counts': (_i, [_vp, _vp, _vp, _vp]),

@@ -304,6 +304,100 @@ int pa_adam_set_steps(pa_adam_state* state, long long steps, void* s) {
     if (steps < 0 || steps > 2147483647LL) { pa_set_error_msg("pa_adam_set_steps: steps must be in 0 .. 2^31 - 1"); return 1; }
     TRY(pa_launch_adam_set_steps(reinterpret_cast<PaAdamState*>(state), (int)steps, ST(s))); return 0;
 }
+// Parameter groups: per-group lr / weight_decay / frozen through a chunk map (elementwise.hip).  The map builder is host only; the three
+// device entry points check every argument before the first device call, so an argument error launches nothing.
+static_assert(sizeof(pa_opt_group) == 16 && PA_OPT_GROUPS_MAX == PA_OPT_GROUPS, "pa_opt_group is 16 bytes, 16 groups");
+size_t pa_opt_chunk_map_bytes(size_t n) { return n / 4 + (n % 4 != 0); }
+int pa_opt_chunk_map_host(const size_t* offsets, const size_t* numels, const int32_t* group, int ntensors, size_t n, int ngroups,
+                          uint8_t* map) {
+    g_err[0] = 0;
+    const char* who = "pa_opt_chunk_map_host";
+    if (!offsets || !numels || !group || !map) { pa_set_error_msg((std::string(who) + ": offsets, numels, group or map is NULL").c_str()); return 1; }
+    if (ntensors < 1) { pa_set_error_msg((std::string(who) + ": ntensors must be >= 1").c_str()); return 1; }
+    if (ngroups < 1 || ngroups > PA_OPT_GROUPS_MAX) { pa_set_error_msg((std::string(who) + ": ngroups must be in 1 .. 16").c_str()); return 1; }
+    size_t end = 0;
+    for (int t = 0; t < ntensors; ++t) {
+        const std::string at = std::string(who) + ": tensor " + std::to_string(t);
+        if (offsets[t] & 3) { pa_set_error_msg((at + ": offset is not a multiple of 4").c_str()); return 1; }
+        if (offsets[t] < end) { pa_set_error_msg((at + ": out of order or overlapping the tensor in front of it").c_str()); return 1; }
+        if (numels[t] > n || offsets[t] > n - numels[t]) { pa_set_error_msg((at + ": ends past n").c_str()); return 1; }
+        if (group[t] < 0 || group[t] >= ngroups) { pa_set_error_msg((at + ": group id outside 0 .. ngroups - 1").c_str()); return 1; }
+        end = offsets[t] + numels[t];
+    }
+    const size_t chunks = pa_opt_chunk_map_bytes(n);
+    size_t c = 0;
+    uint8_t cur = 0;                        // a chunk no tensor touches: the group of the tensor in front of it (0 in front of the first)
+    for (int t = 0; t < ntensors; ++t) {
+        if (numels[t] == 0) continue;
+        const size_t first = offsets[t] / 4, last = (offsets[t] + numels[t] - 1) / 4;
+        for (; c < first; ++c) map[c] = cur;
+        cur = (uint8_t)group[t];
+        for (; c <= last; ++c) map[c] = cur;
+    }
+    for (; c < chunks; ++c) map[c] = cur;
+    return 0;
+}
+// groups_host -> the kernels' table; false with the error set
+static bool opt_groups_table(const char* who, const pa_opt_group* groups, int ngroups, const uint8_t* chunk_map, PaOptGroupTable* tab) {
+    const std::string w(who);
+    if (!groups) { pa_set_error_msg((w + ": groups_host is NULL").c_str()); return false; }
+    if (ngroups < 1 || ngroups > PA_OPT_GROUPS_MAX) { pa_set_error_msg((w + ": ngroups must be in 1 .. 16").c_str()); return false; }
+    bool frozen = false;
+    for (int k = 0; k < PA_OPT_GROUPS; ++k) {
+        PaOptGroupK& e = tab->g[k];
+        if (k >= ngroups) { e.lr = e.wd = 0.f; e.c_dec = 1.f; e.frozen = 1; continue; }
+        if (!(groups[k].lr >= 0.f) || !std::isfinite(groups[k].lr)) { pa_set_error_msg((w + ": lr of group " + std::to_string(k) + " must be finite and >= 0").c_str()); return false; }
+        if (!(groups[k].weight_decay >= 0.f) || !std::isfinite(groups[k].weight_decay)) {
+            pa_set_error_msg((w + ": weight_decay of group " + std::to_string(k) + " must be finite and >= 0").c_str()); return false;
+        }
+        e.lr = groups[k].lr; e.wd = groups[k].weight_decay;
+        e.c_dec = (float)(1.0 - (double)e.lr * (double)e.wd);
+        e.frozen = groups[k].frozen != 0;
+        frozen |= e.frozen != 0;
+    }
+    if (!chunk_map && (ngroups > 1 || frozen)) { pa_set_error_msg((w + ": chunk_map is NULL with more than one group or a frozen group").c_str()); return false; }
+    return true;
+}
+int pa_rmsprop_step_groups(const pa_rmsprop_opts* o, const pa_opt_group* groups, int ngroups, const uint8_t* chunk_map, float* p,
+                           const float* g, float* v, float* buf, float* ga, size_t n, float gscale, const float* clip_coef, int32_t* state,
+                           void* s) {
+    g_err[0] = 0;
+    if (!o || !p || !g || !v || !state) { pa_set_error_msg("pa_rmsprop_step_groups: opts, param, grad, square_avg or state is NULL"); return 1; }
+    if (!(o->momentum >= 0.f)) { pa_set_error_msg("pa_rmsprop_step_groups: momentum must be >= 0"); return 1; }
+    if ((o->momentum > 0.f) != (buf != nullptr)) { pa_set_error_msg("pa_rmsprop_step_groups: momentum_buf is required when momentum > 0 and must be NULL otherwise"); return 1; }
+    if ((o->centered != 0) != (ga != nullptr)) { pa_set_error_msg("pa_rmsprop_step_groups: grad_avg is required when centered and must be NULL otherwise"); return 1; }
+    PaOptGroupTable tab;
+    if (!opt_groups_table("pa_rmsprop_step_groups", groups, ngroups, chunk_map, &tab)) return 1;
+    const PaRmspropOpts k = {0.f, o->alpha, o->eps, o->momentum, 0.f};
+    TRY(pa_launch_rmsprop_groups(k, o->centered != 0, tab, ngroups, chunk_map, p, g, v, buf, ga, n, gscale, clip_coef, state, ST(s))); return 0;
+}
+int pa_adam_step_groups(const pa_adam_opts* o, const pa_opt_group* groups, int ngroups, const uint8_t* chunk_map, float* group_consts,
+                        float* p, const float* g, float* m, float* v, float* vmax, size_t n, float gscale, const float* clip_coef,
+                        pa_adam_state* state, void* s) {
+    g_err[0] = 0;
+    if (!o || !p || !g || !m || !v) { pa_set_error_msg("pa_adam_step_groups: opts, param, grad, exp_avg or exp_avg_sq is NULL"); return 1; }
+    if (!adam_state_ok("pa_adam_step_groups", state)) return 1;
+    if ((o->amsgrad != 0) != (vmax != nullptr)) { pa_set_error_msg("pa_adam_step_groups: max_exp_avg_sq is required when amsgrad and must be NULL otherwise"); return 1; }
+    if (!(o->beta1 >= 0.f && o->beta1 < 1.f) || !(o->beta2 >= 0.f && o->beta2 < 1.f)) { pa_set_error_msg("pa_adam_step_groups: beta1 and beta2 must be in [0, 1)"); return 1; }
+    if (!(o->eps > 0.f)) { pa_set_error_msg("pa_adam_step_groups: eps must be > 0"); return 1; }
+    PaOptGroupTable tab;
+    if (!opt_groups_table("pa_adam_step_groups", groups, ngroups, chunk_map, &tab)) return 1;
+    if (!group_consts && (ngroups > 1 || tab.g[0].frozen)) { pa_set_error_msg("pa_adam_step_groups: group_consts is NULL with more than one group or a frozen group"); return 1; }
+    const PaAdamOpts k = {0.f, o->beta1, o->beta2, o->eps, 0.f, 1.f, 1.f - o->beta1, 1.f - o->beta2};
+    TRY(pa_launch_adam_groups(k, o->amsgrad != 0, o->decoupled != 0, tab, ngroups, chunk_map, group_consts, p, g, m, v, vmax, n, gscale,
+                              clip_coef, reinterpret_cast<PaAdamState*>(state), ST(s)));
+    return 0;
+}
+int pa_grad_norm_groups(const float* g, size_t n, const uint8_t* chunk_map, uint32_t excluded, float gscale, float max_norm,
+                        void* workspace, float* out2, void* s) {
+    g_err[0] = 0;
+    if (!g || !workspace || !out2) { pa_set_error_msg("pa_grad_norm_groups: grad, workspace or out2 is NULL"); return 1; }
+    if (!(max_norm > 0.f)) { pa_set_error_msg("pa_grad_norm_groups: max_norm must be > 0"); return 1; }
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) { pa_set_error_msg("pa_grad_norm_groups: workspace must be 8-byte aligned (double partial sums)"); return 1; }
+    if (excluded >> PA_OPT_GROUPS_MAX) { pa_set_error_msg("pa_grad_norm_groups: excluded_groups has bits at or above 16"); return 1; }
+    if (excluded && !chunk_map) { pa_set_error_msg("pa_grad_norm_groups: chunk_map is NULL with excluded groups"); return 1; }
+    TRY(pa_launch_grad_norm_groups(g, n, chunk_map, excluded, gscale, max_norm, workspace, out2, ST(s))); return 0;
+}
 // Weight EMA (ema.hip; utils.optim.ModelEma): the update count, the hold decision and the weight w live in the caller's device state.  An
 // argument error launches nothing.
 static_assert(sizeof(pa_ema_state) == 32 && sizeof(PaEmaState) == 32, "pa_ema_state is 32 bytes");

@@ -1166,6 +1166,251 @@ int pa_launch_grad_norm(const float* g, size_t n, float gscale, float max_norm, 
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Parameter groups: per-group lr / weight_decay / frozen in the fused steps and the norm above.
+// Every tensor of a flat array starts on a 16-byte boundary (Net::add_param) and the step kernels move one 16-byte chunk per thread
+// and iteration, so the group is a property of the CHUNK: chunk_map[i / 4] (one byte, 0 .. 15) is the group of elements 4 (i / 4) ..
+// 4 (i / 4) + 3, and the tail (at most 3 elements) reads chunk_map[n / 4].  The table of at most 16 {lr, wd, c_dec, frozen} entries
+// comes by value in the kernel arguments (256 bytes); thread 0 of every workgroup copies it to LDS with constant indices (scalar
+// loads of the argument segment), and a lane then reads its chunk's entry with one 16-byte LDS load: a per-lane index into the
+// argument itself would send the table through scratch memory.  Entries at and above ngroups are marked frozen by the host, so a map
+// byte out of range (masked to 4 bits) skips its chunk instead of reading anything undefined.
+// The per-element arithmetic is rmsprop_opts_update<> / adam_update<> above, with the chunk's lr and wd (Adam: c_dec and step_size)
+// in place of the optimizer's.  The decay mode is per chunk: wd == 0 executes no decay operation (rmsprop_opts_update tests o.wd at
+// run time already; Adam picks DECAY 0), otherwise coupled or decoupled as the optimizer says.  A FROZEN chunk is skipped before any
+// load: nothing of param, grad or the state arrays is read or written.  Alignment padding stays exactly 0 in every group by the
+// argument above (p = g = state = 0; every term is 0 whatever lr and wd are) or is not touched at all.
+// Half-precision build: the finite scan stays over the WHOLE gradient, frozen chunks included.  An overflow anywhere in the scaled
+// backward pass has already propagated into the layers below it, and the scan is the only evidence of that: the whole step is skipped
+// and counted once, as without groups.  No atomics in these kernels: the same input gives the same bits.
+__device__ __forceinline__ void opt_groups_stage(const PaOptGroupTable& tab, PaOptGroupK* lds) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < PA_OPT_GROUPS; ++k) lds[k] = tab.g[k];
+    }
+}
+
+template <bool MOMENTUM, bool CENTERED>
+__global__ __launch_bounds__(256) void rmsprop_groups_kernel(float* p, const float* g, float* v, float* buf, float* ga, size_t n, PaRmspropOpts o,
+                                                             PaOptGroupTable tab, const unsigned char* __restrict__ map, float gscale,
+                                                             const float* clip_coef, int* state) {
+    __shared__ PaOptGroupK s_tab[PA_OPT_GROUPS];
+#ifdef PA_FP16
+    if (state[0]) {                         // uniform over the grid: every thread reads the same word
+        if (blockIdx.x == 0 && threadIdx.x == 0) state[1] += 1;
+        return;
+    }
+#endif
+    opt_groups_stage(tab, s_tab);
+    __syncthreads();
+    const bool clip = clip_coef != nullptr;
+    const float coef = clip ? clip_coef[0] : 1.f;
+    size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) {
+        const PaOptGroupK gk = s_tab[map[i >> 2] & (PA_OPT_GROUPS - 1)];
+        if (gk.frozen) continue;
+        PaRmspropOpts og = o;
+        og.lr = gk.lr; og.wd = gk.wd;
+        f32x4 gg = *reinterpret_cast<const f32x4*>(g + i), vv = *reinterpret_cast<f32x4*>(v + i), pp = *reinterpret_cast<f32x4*>(p + i);
+        f32x4 bb = {0.f, 0.f, 0.f, 0.f}, aa = {0.f, 0.f, 0.f, 0.f};
+        if (MOMENTUM) bb = *reinterpret_cast<f32x4*>(buf + i);
+        if (CENTERED) aa = *reinterpret_cast<f32x4*>(ga + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pj = pp[j], vj = vv[j], bj = bb[j], aj = aa[j];
+            rmsprop_opts_update<MOMENTUM, CENTERED>(pj, gg[j], vj, bj, aj, og, gscale, clip, coef);
+            pp[j] = pj; vv[j] = vj; bb[j] = bj; aa[j] = aj;
+        }
+        *reinterpret_cast<f32x4*>(v + i) = vv;
+        *reinterpret_cast<f32x4*>(p + i) = pp;
+        if (MOMENTUM) *reinterpret_cast<f32x4*>(buf + i) = bb;
+        if (CENTERED) *reinterpret_cast<f32x4*>(ga + i) = aa;
+    }
+    if (i < n && i + 3 >= n) {                  // tail (at most 3 elements, one thread): the group of chunk n / 4
+        const PaOptGroupK gk = s_tab[map[n >> 2] & (PA_OPT_GROUPS - 1)];
+        if (gk.frozen) return;
+        PaRmspropOpts og = o;
+        og.lr = gk.lr; og.wd = gk.wd;
+        for (; i < n; ++i) {
+            float pj = p[i], vj = v[i], bj = MOMENTUM ? buf[i] : 0.f, aj = CENTERED ? ga[i] : 0.f;
+            rmsprop_opts_update<MOMENTUM, CENTERED>(pj, g[i], vj, bj, aj, og, gscale, clip, coef);
+            p[i] = pj; v[i] = vj;
+            if (MOMENTUM) buf[i] = bj;
+            if (CENTERED) ga[i] = aj;
+        }
+    }
+}
+
+// With ONE group that is not frozen this IS pa_launch_rmsprop_opts with that group's lr and wd: the same launches, hence the same bits.
+int pa_launch_rmsprop_groups(const PaRmspropOpts& o, bool centered, const PaOptGroupTable& tab, int ngroups, const unsigned char* map,
+                             float* p, const float* g, float* v, float* buf, float* ga, size_t n, float gscale, const float* clip_coef,
+                             int* state, hipStream_t st) {
+    if (ngroups == 1 && !tab.g[0].frozen) {
+        PaRmspropOpts o1 = o;
+        o1.lr = tab.g[0].lr; o1.wd = tab.g[0].wd;
+        return pa_launch_rmsprop_opts(o1, centered, p, g, v, buf, ga, n, gscale, clip_coef, state, st);
+    }
+    if (n == 0) return 0;
+    const bool mom = o.mom > 0.f;
+    const int blocks = pa_grid_for(n / 4, 256, 2048);
+#ifdef PA_FP16
+    hipLaunchKernelGGL(grad_check_reset_kernel, dim3(1), dim3(1), 0, st, state);
+    hipLaunchKernelGGL(grad_check_kernel, dim3(blocks), dim3(256), 0, st, g, n, state);
+#endif
+    const dim3 grid(blocks), block(256);
+    if (mom && centered) hipLaunchKernelGGL((rmsprop_groups_kernel<true, true>), grid, block, 0, st, p, g, v, buf, ga, n, o, tab, map, gscale, clip_coef, state);
+    else if (mom) hipLaunchKernelGGL((rmsprop_groups_kernel<true, false>), grid, block, 0, st, p, g, v, buf, ga, n, o, tab, map, gscale, clip_coef, state);
+    else if (centered) hipLaunchKernelGGL((rmsprop_groups_kernel<false, true>), grid, block, 0, st, p, g, v, buf, ga, n, o, tab, map, gscale, clip_coef, state);
+    else hipLaunchKernelGGL((rmsprop_groups_kernel<false, false>), grid, block, 0, st, p, g, v, buf, ga, n, o, tab, map, gscale, clip_coef, state);
+    return (int)hipGetLastError();
+}
+
+// adam_prologue_kernel with one step size per group: group_consts[k] = lr_k / bc1 for k < ngroups (the caller's device array of 16
+// floats, which the step kernel reads and a test can read back), state->step_size = group_consts[0].  A skipped step leaves both.
+__global__ void adam_prologue_groups_kernel(PaAdamState* s, PaOptGroupTable tab, int ngroups, float* group_consts, float beta1, float beta2) {
+    if (s->flag) { s->skipped += 1; return; }
+    const int t = s->step + 1;
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+    const float bc2 = (float)(1.0 - pow((double)beta2, (double)t));
+    s->step = t;
+    s->bc1 = bc1;
+    s->bc2 = bc2;
+    s->bc2s = sqrtf(bc2);
+#pragma unroll
+    for (int k = 0; k < PA_OPT_GROUPS; ++k)
+        if (k < ngroups) group_consts[k] = tab.g[k].lr / bc1;
+    s->step_size = tab.g[0].lr / bc1;
+}
+
+template <bool AMSGRAD, bool DECOUPLED>
+__device__ __forceinline__ void adam_groups_update(float& p, float g, float& m, float& v, float& vmax, const PaAdamOpts& og, float gscale,
+                                                   bool clip, float coef, float bc2s, float step_size) {
+    if (og.wd != 0.f) adam_update<AMSGRAD, DECOUPLED ? 2 : 1>(p, g, m, v, vmax, og, gscale, clip, coef, bc2s, step_size);
+    else adam_update<AMSGRAD, 0>(p, g, m, v, vmax, og, gscale, clip, coef, bc2s, step_size);
+}
+
+template <bool AMSGRAD, bool DECOUPLED>
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* p, const float* g, float* m, float* v, float* vmax, size_t n, PaAdamOpts o,
+                                                          PaOptGroupTable tab, int ngroups, const unsigned char* __restrict__ map,
+                                                          const float* __restrict__ group_consts, float gscale, const float* clip_coef,
+                                                          const PaAdamState* state) {
+    __shared__ PaOptGroupK s_tab[PA_OPT_GROUPS];
+    __shared__ float s_step[PA_OPT_GROUPS];
+    if (state->flag) return;                // uniform over the grid (the prologue has counted the skip)
+    opt_groups_stage(tab, s_tab);
+    if (threadIdx.x < PA_OPT_GROUPS) s_step[threadIdx.x] = (int)threadIdx.x < ngroups ? group_consts[threadIdx.x] : 0.f;
+    __syncthreads();
+    const float bc2s = state->bc2s;
+    const bool clip = clip_coef != nullptr;
+    const float coef = clip ? clip_coef[0] : 1.f;
+    size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
+    for (; i + 3 < n; i += stride) {
+        const int k = map[i >> 2] & (PA_OPT_GROUPS - 1);
+        const PaOptGroupK gk = s_tab[k];
+        if (gk.frozen) continue;
+        const float step_size = s_step[k];
+        PaAdamOpts og = o;
+        og.wd = gk.wd; og.c_dec = gk.c_dec;
+        f32x4 gg = *reinterpret_cast<const f32x4*>(g + i), mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i),
+              pp = *reinterpret_cast<f32x4*>(p + i);
+        f32x4 xx = {0.f, 0.f, 0.f, 0.f};
+        if (AMSGRAD) xx = *reinterpret_cast<f32x4*>(vmax + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pj = pp[j], mj = mm[j], vj = vv[j], xj = xx[j];
+            adam_groups_update<AMSGRAD, DECOUPLED>(pj, gg[j], mj, vj, xj, og, gscale, clip, coef, bc2s, step_size);
+            pp[j] = pj; mm[j] = mj; vv[j] = vj; xx[j] = xj;
+        }
+        *reinterpret_cast<f32x4*>(m + i) = mm;
+        *reinterpret_cast<f32x4*>(v + i) = vv;
+        *reinterpret_cast<f32x4*>(p + i) = pp;
+        if (AMSGRAD) *reinterpret_cast<f32x4*>(vmax + i) = xx;
+    }
+    if (i < n && i + 3 >= n) {                  // tail (at most 3 elements, one thread): the group of chunk n / 4
+        const int k = map[n >> 2] & (PA_OPT_GROUPS - 1);
+        const PaOptGroupK gk = s_tab[k];
+        if (gk.frozen) return;
+        const float step_size = s_step[k];
+        PaAdamOpts og = o;
+        og.wd = gk.wd; og.c_dec = gk.c_dec;
+        for (; i < n; ++i) {
+            float pj = p[i], mj = m[i], vj = v[i], xj = AMSGRAD ? vmax[i] : 0.f;
+            adam_groups_update<AMSGRAD, DECOUPLED>(pj, g[i], mj, vj, xj, og, gscale, clip, coef, bc2s, step_size);
+            p[i] = pj; m[i] = mj; v[i] = vj;
+            if (AMSGRAD) vmax[i] = xj;
+        }
+    }
+}
+
+// ONE group that is not frozen: the launches of pa_launch_adam with that group's lr, wd and c_dec, hence its bits; with a
+// group_consts array the prologue is the grouped one, which writes the same state words and group_consts[0] besides.
+int pa_launch_adam_groups(const PaAdamOpts& o, bool amsgrad, bool decoupled, const PaOptGroupTable& tab, int ngroups, const unsigned char* map,
+                          float* group_consts, float* p, const float* g, float* m, float* v, float* vmax, size_t n, float gscale,
+                          const float* clip_coef, PaAdamState* state, hipStream_t st) {
+    const bool single = ngroups == 1 && !tab.g[0].frozen;
+    if (single && !group_consts) {
+        PaAdamOpts o1 = o;
+        o1.lr = tab.g[0].lr; o1.wd = tab.g[0].wd; o1.c_dec = tab.g[0].c_dec;
+        return pa_launch_adam(o1, amsgrad, o1.wd != 0.f ? (decoupled ? 2 : 1) : 0, p, g, m, v, vmax, n, gscale, clip_coef, state, st);
+    }
+    if (n == 0) return 0;
+    const int blocks = pa_grid_for(n / 4, 256, 2048);
+#ifdef PA_FP16
+    hipLaunchKernelGGL(grad_check_reset_kernel, dim3(1), dim3(1), 0, st, &state->flag);
+    hipLaunchKernelGGL(grad_check_kernel, dim3(blocks), dim3(256), 0, st, g, n, &state->flag);
+#endif
+    hipLaunchKernelGGL(adam_prologue_groups_kernel, dim3(1), dim3(1), 0, st, state, tab, ngroups, group_consts, o.beta1, o.beta2);
+    const dim3 grid(blocks), block(256);
+    if (single) {
+        PaAdamOpts o1 = o;
+        o1.lr = tab.g[0].lr; o1.wd = tab.g[0].wd; o1.c_dec = tab.g[0].c_dec;
+        const int decay = o1.wd != 0.f ? (decoupled ? 2 : 1) : 0;
+        if (amsgrad) adam_launch_decay<true>(decay, grid, block, st, p, g, m, v, vmax, n, o1, gscale, clip_coef, state);
+        else adam_launch_decay<false>(decay, grid, block, st, p, g, m, v, vmax, n, o1, gscale, clip_coef, state);
+        return (int)hipGetLastError();
+    }
+    if (amsgrad && decoupled) hipLaunchKernelGGL((adam_groups_kernel<true, true>), grid, block, 0, st, p, g, m, v, vmax, n, o, tab, ngroups, map, group_consts, gscale, clip_coef, state);
+    else if (amsgrad) hipLaunchKernelGGL((adam_groups_kernel<true, false>), grid, block, 0, st, p, g, m, v, vmax, n, o, tab, ngroups, map, group_consts, gscale, clip_coef, state);
+    else if (decoupled) hipLaunchKernelGGL((adam_groups_kernel<false, true>), grid, block, 0, st, p, g, m, v, vmax, n, o, tab, ngroups, map, group_consts, gscale, clip_coef, state);
+    else hipLaunchKernelGGL((adam_groups_kernel<false, false>), grid, block, 0, st, p, g, m, v, vmax, n, o, tab, ngroups, map, group_consts, gscale, clip_coef, state);
+    return (int)hipGetLastError();
+}
+
+// grad_sqsum_kernel over the chunks whose group is not in the 16-bit mask `excluded` (the frozen groups): an excluded chunk adds
+// nothing.  The grid, the per-thread order of additions, the block reduction and the finish kernel are pa_launch_grad_norm's, and
+// s + (+0) == s for the non-negative partial sums, so the result is, bit for bit, that of pa_launch_grad_norm on a copy of the
+// gradient with the excluded chunks set to +0 (inf and NaN in them included: they are not read).
+__global__ __launch_bounds__(256) void grad_sqsum_groups_kernel(const float* g, size_t n, float gscale, double* partial,
+                                                                const unsigned char* __restrict__ map, unsigned excluded) {
+    __shared__ double lds[4];
+    const double sc = (double)gscale;
+    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * 256 * 4;
+    double s = 0.0;
+    for (; i + 3 < n; i += stride) {
+        if ((excluded >> (map[i >> 2] & (PA_OPT_GROUPS - 1))) & 1u) continue;
+        const f32x4 gg = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const double t = (double)gg[j] * sc; s += t * t; }
+    }
+    if (i < n && i + 3 >= n && !((excluded >> (map[n >> 2] & (PA_OPT_GROUPS - 1))) & 1u))
+        for (; i < n; ++i) { const double t = (double)g[i] * sc; s += t * t; }
+    s = block_sum_double(s, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+int pa_launch_grad_norm_groups(const float* g, size_t n, const unsigned char* map, unsigned excluded, float gscale, float max_norm,
+                               void* workspace, float* out2, hipStream_t st) {
+    if (!excluded) return pa_launch_grad_norm(g, n, gscale, max_norm, workspace, out2, st);
+    const int blocks = pa_grid_for(n / 4, 256, 2048);
+    double* partial = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(grad_sqsum_groups_kernel, dim3(blocks), dim3(256), 0, st, g, n, gscale, partial, map, excluded);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, st, partial, blocks, max_norm, out2);
+    return (int)hipGetLastError();
+}
+
 // plain streaming copy, 16 bytes per lane, 4 independent loads per thread and iteration: what "just moving the bytes" reaches on this
 // part at a given size (bench.py roofline.floor calibrates with it instead of a framework kernel)
 __global__ __launch_bounds__(256) void copy16_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {

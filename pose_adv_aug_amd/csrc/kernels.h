@@ -148,6 +148,20 @@ int pa_launch_adam(const PaAdamOpts& o, bool amsgrad, int decay, float* p, const
                    float gscale, const float* clip_coef, PaAdamState* state, hipStream_t st);
 int pa_adam_read_steps(const PaAdamState* state, long long* steps, long long* skipped, hipStream_t st);
 int pa_launch_adam_set_steps(PaAdamState* state, int steps, hipStream_t st);
+// Parameter groups (elementwise.hip): chunk_map[i / 4] = group of the 16-byte chunk of element i; the table of PA_OPT_GROUPS entries goes
+// to the kernels by value (256 bytes).  c_dec = (float)(1.0 - (double)lr * (double)wd); entries at and above ngroups: frozen = 1.
+// One group that is not frozen: the launches of the calls above.  excluded: bit k set = group k adds nothing to the norm.
+constexpr int PA_OPT_GROUPS = 16;
+struct PaOptGroupK { float lr, wd, c_dec; int frozen; };
+struct PaOptGroupTable { PaOptGroupK g[PA_OPT_GROUPS]; };
+int pa_launch_rmsprop_groups(const PaRmspropOpts& o, bool centered, const PaOptGroupTable& tab, int ngroups, const unsigned char* map,
+                             float* p, const float* g, float* v, float* buf, float* ga, size_t n, float gscale, const float* clip_coef,
+                             int* state, hipStream_t st);
+int pa_launch_adam_groups(const PaAdamOpts& o, bool amsgrad, bool decoupled, const PaOptGroupTable& tab, int ngroups, const unsigned char* map,
+                          float* group_consts, float* p, const float* g, float* m, float* v, float* vmax, size_t n, float gscale,
+                          const float* clip_coef, PaAdamState* state, hipStream_t st);
+int pa_launch_grad_norm_groups(const float* g, size_t n, const unsigned char* map, unsigned excluded, float gscale, float max_norm,
+                               void* workspace, float* out2, hipStream_t st);
 int pa_launch_loss_out(float* acc, float* keep, float* out, float* total, int n, hipStream_t st);      // per-stack losses + their sum out, accumulators cleared
 int pa_launch_copy16(void* dst, const void* src, size_t bytes, hipStream_t st, int form = 0);      // plain 16-B/lane streaming copy (bandwidth calibration)
 int pa_rmsprop_skipped(const int* state, long long* out, hipStream_t st);     // half-precision build: steps skipped for a non-finite gradient

@@ -204,7 +204,7 @@ def main(argv=None):
         checkpoint_hg.load_prefix = exp + '/' + opt.load_prefix_pose[0:-1]
         ok = checkpoint_hg.load_checkpoint(hg, optimizer_hg, train_history_pose)
         for g in optimizer_hg.param_groups:
-            g['lr'] = opt.lr
+            g['lr'] = opt.lr * g.get('lr_mult', 1.0)
     if not ok:
         raise SystemExit('pose checkpoint %s.pth.tar not found' % checkpoint_hg.load_prefix)
     checkpoint_hg.save_prefix = joint_dir + '/pose-'                                          # :81
@@ -221,10 +221,14 @@ def main(argv=None):
         checkpoint_sr.load_prefix = sr_pretrain_dir + '/' + opt.load_prefix_sr[0:-1]
         ok = checkpoint_sr.load_checkpoint(agent_sr, optimizer_sr, train_history_sr)
         for g in optimizer_sr.param_groups:
-            g['lr'] = opt.agent_lr
+            g['lr'] = opt.agent_lr * g.get('lr_mult', 1.0)
     if not ok:
         raise SystemExit('agent checkpoint %s.pth.tar not found' % checkpoint_sr.load_prefix)
     checkpoint_sr.save_prefix = joint_dir + '/agent-'                                         # :110
+    for name, o in (('pose net', optimizer_hg), ('agent', optimizer_sr)):                     # (parameter groups: once, what each holds)
+        if len(o.param_groups) > 1:
+            for line in o.describe_groups():
+                log('%s %s' % (name, line))
     broadcast_parameters(hg)
     broadcast_parameters(agent_sr)
     # the pose net's weight EMA (--ema_decay 0: None): a copy of the loaded, broadcast weights, or the average the file carries.  The

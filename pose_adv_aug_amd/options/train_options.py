@@ -22,6 +22,12 @@ class TrainOptions(BaseOptions):
         p.add_argument('--beta2', type=float, default=0.999, help='Adam / AdamW: decay of the second moment')
         p.add_argument('--adam_eps', type=float, default=1e-8, help='Adam / AdamW: eps added to the denominator')
         p.add_argument('--amsgrad', type=int, default=0, help='1: Adam / AdamW with AMSGrad (0: off)')
+        # parameter groups (utils/optim.py make_optimizer, group_specs): all off by default, and then the optimizer has the one group it
+        # always had.  --freeze and --lr_group select tensors of the POSE net by state-dict name (re.search); the agent's optimizer takes
+        # --no_decay_1d only
+        p.add_argument('--no_decay_1d', type=int, default=0, choices=(0, 1), help='1: no weight decay on BatchNorm weights / biases and conv / linear biases')
+        p.add_argument('--freeze', type=str, default='', help='REGEX: pose-net tensors that keep their loaded values')
+        p.add_argument('--lr_group', type=str, action='append', default=[], help='REGEX:MULT (repeatable): pose-net tensors trained at MULT times the learning rate')
         # coordinate loss beside the heat-map MSE (stack_hg.coord_criterion): W * mean |soft-arg-max(out, beta) - pts| per stack; 0 = off, the
         # reference's recipe and the fused step
         p.add_argument('--coord_loss', type=float, default=0., help='weight of the soft-arg-max coordinate L1 loss (0: off)')

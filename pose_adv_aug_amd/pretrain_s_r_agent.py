@@ -158,6 +158,8 @@ def main(argv=None):
     agent = create_asn(chan_in=256, chan_out=256, scale_num=len(SCALE_MEANS), rotation_num=len(ROT_MEANS), is_aug=True,
                        default_batch=opt.bs)
     optimizer = make_optimizer(opt, agent, opt.lr)                              # :93-94 (opt.lr, not agent_lr)
+    if len(optimizer.param_groups) > 1:                                         # (--no_decay_1d: once, what each group holds)
+        print('\n'.join(optimizer.describe_groups()))
     history, ckpt = ASNTrainHistory(), Checkpoint()
     if opt.load_prefix_sr != '':                                                              # resume (:64-70)
         ckpt.load_prefix = sr_dir + '/' + opt.load_prefix_sr[0:-1]

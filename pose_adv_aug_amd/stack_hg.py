@@ -277,6 +277,9 @@ def main(argv=None):
     augmenter = Augmenter(seed=1234 + rank, stretch=bool(opt.crop_stretch))     # (training and validation: the reference stretches both)
     vis = Visualizer(opt, log_path=os.path.join(exp_dir, 'train-log.txt' if opt.is_train else 'val-log.txt') if rank == 0 else None)
     log = (lambda m: (print(m), vis.write_log(m))) if rank == 0 else (lambda m: None)
+    if len(optimizer.param_groups) > 1:               # (--no_decay_1d / --freeze / --lr_group: once, what each group holds)
+        for line in optimizer.describe_groups():
+            log(line)
     batches, val_batches = make_feeds(opt, rank, world, log)
     if not opt.is_train:                                                                     # stack-hg.py:90-96
         epoch = history.epoch[-1]['epoch'] if history.epoch else 0

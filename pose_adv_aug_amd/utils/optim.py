@@ -142,16 +142,21 @@ class _FlatOptimizer(object):
             gscale, self.pending = gscale / (k + 1), 0
         return gscale
 
-    def _clip_coef(self, n, gscale):
-        """norm and clip coefficient of the exchanged gradient (max_grad_norm): the pointer of the device float the step reads, or None"""
+    def _clip_coef(self, n, gscale, frozen=0):
+        """norm and clip coefficient of the exchanged gradient (max_grad_norm): the pointer of the device float the step reads, or None.
+        frozen: the bit mask of the frozen parameter groups, whose chunks the norm leaves out (pa_grad_norm_groups)"""
         if self.max_grad_norm is None:
             return None
         grads = self.net.flat_grads
         if self._norm_out is None:
             self._norm_ws = torch.empty(int(lib().pa_grad_norm_workspace_bytes(n)) // 8, dtype=torch.float64, device=grads.device)
             self._norm_out = torch.zeros(2, dtype=torch.float32, device=grads.device)
-        check(lib().pa_grad_norm(ptr(grads), n, float(gscale), float(self.max_grad_norm), ptr(self._norm_ws), ptr(self._norm_out), stream()),
-              'pa_grad_norm')
+        if frozen:
+            check(lib().pa_grad_norm_groups(ptr(grads), n, ptr(self._map), int(frozen), float(gscale), float(self.max_grad_norm),
+                                            ptr(self._norm_ws), ptr(self._norm_out), stream()), 'pa_grad_norm_groups')
+        else:
+            check(lib().pa_grad_norm(ptr(grads), n, float(gscale), float(self.max_grad_norm), ptr(self._norm_ws), ptr(self._norm_out), stream()),
+                  'pa_grad_norm')
         self._clipped = True
         return ptr(self._norm_out[1:])
 
@@ -160,17 +165,196 @@ class _FlatOptimizer(object):
         self.net._net(self.net._last_B or self.net.default_batch)      # refresh the bf16 weight copies now
 
     def last_grad_norm(self):
-        """The norm of the (averaged, unscaled) gradient of the last step taken with max_grad_norm, before clipping: a 0-dim tensor on
-        the device, so reading it is the caller's synchronisation (at print time); None before the first such step."""
+        """The norm of the (averaged, unscaled) gradient of the last step taken with max_grad_norm, before clipping, over the
+        parameter groups that are not frozen: a 0-dim tensor on the device, so reading it is the caller's synchronisation (at print time); None before the first such step."""
         return self._norm_out[0] if self._clipped else None
 
     def _params(self):
         """(name, shape, offset, numel, kind) of the parameters, in parameters() order"""
         return [t for t in self.net._table if t[4] == 0]
 
+    # ---- parameter groups
+    def _init_groups(self, base, groups):
+        """self.param_groups from the constructor's options `base` and its `groups` argument.  None: the one group there has always
+        been, with exactly the keys it has always had, and no call of this class changes.  A list of specs {'params': selector, 'lr',
+        'weight_decay', 'frozen', 'lr_mult'}: param_groups[0] is the default group (what no spec takes, base's lr and weight_decay), spec
+        k is param_groups[k + 1]; every group is a dict with all option keys, 'frozen', 'lr_mult', 'params' (indices in parameters()
+        order) and 'names'.  The first spec that matches a parameter takes it.  The chunk map (pa_opt_chunk_map_host on the net's
+        table) is built and uploaded here, once."""
+        self._map = self._group_consts = None
+        self._shared = tuple(k for k in base if k not in ('lr', 'weight_decay'))
+        if groups is None:
+            self.param_groups = [base]
+            return
+        params = self._params()
+        names = [t[0] for t in params]
+        specs = list(groups)
+        if len(specs) + 1 > _lib.OPT_GROUPS_MAX:
+            raise ValueError('%d parameter groups (the default group and %d specs): at most %d' % (len(specs) + 1, len(specs), _lib.OPT_GROUPS_MAX))
+        owner = [0] * len(params)
+        taken = [False] * len(params)
+        for k, spec in enumerate(specs):
+            unknown = set(spec) - set(('params', 'lr', 'weight_decay', 'frozen', 'lr_mult'))
+            if 'params' not in spec or unknown:
+                raise ValueError("group %d: a spec is {'params': selector, 'lr', 'weight_decay', 'frozen', 'lr_mult'}; got keys %s" % (k, sorted(spec)))
+            hit = _select(spec['params'], params)
+            if not any(hit):
+                raise ValueError('group %d: the selector %r matches no parameter' % (k, spec['params']))
+            for i, h in enumerate(hit):
+                if h and not taken[i]:
+                    owner[i], taken[i] = k + 1, True
+        base_lr = float(base['lr'])
+        self.param_groups = []
+        for k, spec in enumerate([{}] + specs):
+            g = dict(base)
+            if 'lr' in spec and 'lr_mult' in spec:
+                raise ValueError("group %d: give 'lr' or 'lr_mult', not both" % (k - 1))
+            if 'lr' in spec:
+                g['lr'] = spec['lr']
+                g['lr_mult'] = float(spec['lr']) / base_lr if base_lr != 0 else 1.0
+            else:
+                g['lr_mult'] = float(spec.get('lr_mult', 1.0))
+                if 'lr_mult' in spec:
+                    g['lr'] = base_lr * g['lr_mult']
+            if not float(g['lr']) >= 0 or not g['lr_mult'] >= 0:
+                raise ValueError('group %d: lr and lr_mult must be >= 0' % (k - 1))
+            g['weight_decay'] = spec.get('weight_decay', base['weight_decay'])
+            if not float(g['weight_decay']) >= 0:
+                raise ValueError('group %d: weight_decay must be >= 0' % (k - 1))
+            g['frozen'] = bool(spec.get('frozen', False))
+            g['params'] = [i for i in range(len(params)) if owner[i] == k]
+            g['names'] = [names[i] for i in g['params']]
+            self.param_groups.append(g)
+        n = self.net.flat_params.numel()
+        nt = len(params)
+        offsets = (C.c_size_t * nt)(*[t[2] for t in params])
+        numels = (C.c_size_t * nt)(*[t[3] for t in params])
+        group = (C.c_int32 * nt)(*owner)
+        host = (C.c_uint8 * ((n + 3) // 4))()
+        check(lib().pa_opt_chunk_map_host(offsets, numels, group, nt, n, len(self.param_groups), host), 'pa_opt_chunk_map_host')
+        dev = self.net.flat_params.device
+        self._map = torch.frombuffer(host, dtype=torch.uint8).clone().to(dev)
+        self._group_consts = torch.zeros(_lib.OPT_GROUPS_MAX, dtype=torch.float32, device=dev)      # Adam: lr_k / bc1 of the last taken step
+
+    def _grouped(self):
+        return self._map is not None
+
+    def _group_table(self):
+        """(pa_opt_group array, ngroups, 16-bit mask of the frozen groups) from param_groups as they are NOW; the shared options are
+        group 0's, and another group's copy that differs is an error"""
+        gs = self.param_groups
+        if len(gs) > _lib.OPT_GROUPS_MAX:
+            raise ValueError('%d parameter groups: at most %d' % (len(gs), _lib.OPT_GROUPS_MAX))
+        for k, g in enumerate(gs[1:], 1):
+            for key in self._shared:
+                a, b = g.get(key), gs[0].get(key)
+                if (tuple(a) if isinstance(a, (list, tuple)) else a) != (tuple(b) if isinstance(b, (list, tuple)) else b):
+                    raise ValueError('param_groups[%d][%r] = %r differs from param_groups[0][%r] = %r: %s is shared by all groups '
+                                     '(only lr, weight_decay and frozen are per group)' % (k, key, a, key, b, key))
+        tab = (_lib.OptGroup * len(gs))()
+        mask = 0
+        for k, g in enumerate(gs):
+            tab[k].lr, tab[k].weight_decay, tab[k].frozen = float(g['lr']), float(g.get('weight_decay', 0)), int(bool(g.get('frozen', False)))
+            mask |= tab[k].frozen << k
+        return tab, len(gs), mask
+
+    def _frozen_params(self):
+        """indices (parameters() order) of the parameters in a frozen group"""
+        return set(i for g in self.param_groups if g.get('frozen', False) for i in g.get('params', ()))
+
+    def describe_groups(self):
+        """one line per parameter group for the log: tensors, floats, lr, weight_decay, frozen"""
+        params = self._params()
+        lines = []
+        for k, g in enumerate(self.param_groups):
+            idx = g.get('params', range(len(params)))
+            lines.append('param group %d: %d tensors, %d floats, lr %g, weight_decay %g, frozen %d' % (
+                k, len(idx), sum(params[i][3] for i in idx), g['lr'], g.get('weight_decay', 0), int(bool(g.get('frozen', False)))))
+        return lines
+
+    def _state_groups(self):
+        """state_dict()'s 'param_groups': torch's format, the 'params' lists partition 0 .. P - 1"""
+        out = []
+        for g in self.param_groups:
+            pg = dict(g)
+            if 'betas' in pg:
+                pg['betas'] = tuple(pg['betas'])
+            pg['params'] = list(g['params']) if 'params' in g else list(range(len(self._params())))
+            if 'names' in pg:
+                pg['names'] = list(pg['names'])
+            out.append(pg)
+        return out
+
+    def _file_keys(self, sd):
+        """The file's state keys in parameters() order, and whether its groups partition the parameters as this optimizer's do.  The
+        ids of a file are positions in ITS chained group order (torch numbers them so; this class's own files use the parameter
+        index, which is the same thing read through the groups' 'params' lists).  Same group sizes: position j of the file's chain is
+        position j of this optimizer's chain.  Otherwise: position j of the file is parameter j.
+        A file of this class with several groups says which parameters each group holds ('names', and its ids ARE parameter indices):
+        its membership is compared exactly, and where it differs the state still goes to the parameter each id names."""
+        nparams = len(self._params())
+        fgs = sd['param_groups']
+        chain = [key for fg in fgs for key in fg.get('params', [])] if all('params' in fg for fg in fgs) else list(range(nparams))
+        if len(chain) != nparams:
+            return None, False
+        mine = [list(g['params']) if 'params' in g else list(range(nparams)) for g in self.param_groups]
+        if all('names' in fg and 'params' in fg for fg in fgs) and sorted(chain) == list(range(nparams)):
+            names = [t[0] for t in self._params()]
+            same = len(fgs) == len(mine) and all(list(fg['params']) == m and list(fg['names']) == [names[i] for i in m] for fg, m in zip(fgs, mine))
+            return list(range(nparams)), same
+        if [len(fg.get('params', chain)) for fg in fgs] == [len(m) for m in mine]:
+            keys = [None] * nparams
+            for key, i in zip(chain, [i for m in mine for i in m]):
+                keys[i] = key
+            return keys, True
+        return chain, False
+
+    def _load_groups(self, sd, matched, shared_keys):
+        """the group options of a file.  A file with this optimizer's partition: lr, weight_decay, frozen, lr_mult per group.  Any
+        other file into a grouped optimizer: the per-group values stay this optimizer's (one warning).  The shared options come from
+        the file's group 0 either way, into every group."""
+        fgs = sd['param_groups']
+        shared = dict((k, v) for k, v in fgs[0].items() if k in shared_keys)
+        if 'betas' in shared:
+            shared['betas'] = tuple(shared['betas'])
+        for g in self.param_groups:
+            g.update(shared)
+        if matched:
+            for g, fg in zip(self.param_groups, fgs):
+                for k in ('lr', 'weight_decay') + (('frozen', 'lr_mult') if self._grouped() else ()):
+                    if k in fg:
+                        g[k] = fg[k]
+        else:
+            import warnings
+            warnings.warn('optimizer state: the file has %d parameter group(s) that do not partition the parameters as the %d of this '
+                          'optimizer do: the state is loaded by position and the shared options from its group 0; every group keeps its '
+                          'own lr, weight_decay, frozen and lr_mult' % (len(fgs), len(self.param_groups)))
+
+
+def _select(selector, params):
+    """which of `params` ((name, shape, ...) in parameters() order) a group selector takes: a regular expression (re.search on the
+    state-dict name), a callable (name, shape) -> bool, or a list of names (each must exist)"""
+    if callable(selector):
+        return [bool(selector(t[0], tuple(t[1]))) for t in params]
+    if isinstance(selector, str):
+        import re
+        rx = re.compile(selector)
+        return [rx.search(t[0]) is not None for t in params]
+    wanted = set(selector)
+    unknown = sorted(wanted - set(t[0] for t in params))
+    if unknown:
+        raise ValueError('group selector names parameters that do not exist: %s' % ', '.join(unknown))
+    return [t[0] in wanted for t in params]
+
+
+def no_decay_1d(name, shape):
+    """group selector: the tensors with ndim <= 1 (BatchNorm weight and bias, conv and linear biases), which an AdamW recipe does not decay"""
+    return len(shape) <= 1
+
 
 class RMSprop(_FlatOptimizer):
-    def __init__(self, net, lr=2.5e-4, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0, centered=False, max_grad_norm=None, overlap=False):
+    def __init__(self, net, lr=2.5e-4, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0, centered=False, max_grad_norm=None, overlap=False,
+                 groups=None):
         """momentum, weight_decay, centered: torch.optim.RMSprop's (torch 2.10 _single_tensor_rmsprop), except that the centered
         variance max(0, square_avg - grad_avg^2) is clamped where torch returns NaN for a difference that rounding made negative.
         They live in param_groups[0] and are read at every step, like lr.  max_grad_norm (None = off): the gradient is multiplied by
@@ -178,11 +362,13 @@ class RMSprop(_FlatOptimizer):
         reads the coefficient there (no host synchronisation); last_grad_norm() is the device float for logging.
         overlap (pose net, world > 1 only): exchange the gradients of a stack's hourglass (one contiguous 42 % of a 2-stack
         net) on a communication stream as soon as that stack's backward pass is enqueued, while the earlier stacks and the stem
-        still run; the rest follows at the end.  Same sums, same result as the single all-reduce (off by default)."""
+        still run; the rest follows at the end.  Same sums, same result as the single all-reduce (off by default).
+        groups (None: one group, everything as ever): parameter groups with their own lr / weight_decay / frozen, see _init_groups;
+        every step then goes through pa_rmsprop_step_groups, and the norm through pa_grad_norm_groups when a group is frozen."""
         if momentum < 0 or weight_decay < 0:
             raise ValueError('momentum and weight_decay must be >= 0')
         self._attach(net, max_grad_norm, overlap)
-        self.param_groups = [{'lr': lr, 'alpha': alpha, 'eps': eps, 'momentum': momentum, 'weight_decay': weight_decay, 'centered': bool(centered)}]
+        self._init_groups({'lr': lr, 'alpha': alpha, 'eps': eps, 'momentum': momentum, 'weight_decay': weight_decay, 'centered': bool(centered)}, groups)
         self.square_avg = torch.zeros_like(net.flat_params)
         # flat like square_avg, allocated when their option is on (_ensure_state)
         self.momentum_buffer = self.grad_avg = None
@@ -204,7 +390,9 @@ class RMSprop(_FlatOptimizer):
         gscale = self._exchanged_gscale()
         n = self.net.flat_params.numel()
         mom, wd, centered = float(g.get('momentum', 0)), float(g.get('weight_decay', 0)), bool(g.get('centered', False))
-        if mom == 0 and wd == 0 and not centered and self.max_grad_norm is None:          # the reference's recipe: one launch, as ever
+        if self._grouped():
+            self._step_groups(g, mom, centered, n, gscale)
+        elif mom == 0 and wd == 0 and not centered and self.max_grad_norm is None:          # the reference's recipe: one launch, as ever
             check(lib().pa_rmsprop_step_state(ptr(self.net.flat_params), ptr(self.net.flat_grads), ptr(self.square_avg), n,
                                               float(g['lr']), float(g['alpha']), float(g['eps']), float(gscale), ptr(self._skip_state), stream()),
                   'pa_rmsprop_step_state')
@@ -221,6 +409,17 @@ class RMSprop(_FlatOptimizer):
         check(lib().pa_rmsprop_step_opts(C.byref(o), ptr(self.net.flat_params), ptr(grads), ptr(self.square_avg),
                                          ptr(self.momentum_buffer) if mom > 0 else None, ptr(self.grad_avg) if centered else None,
                                          n, float(gscale), coef, ptr(self._skip_state), stream()), 'pa_rmsprop_step_opts')
+
+    def _step_groups(self, g, mom, centered, n, gscale):
+        """the step with parameter groups: lr, weight_decay and frozen of every group as they are now, the other options group 0's"""
+        tab, ngroups, frozen = self._group_table()
+        self._ensure_state(g)
+        coef = self._clip_coef(n, gscale, frozen)
+        o = _lib.RmspropOpts(float(g['lr']), float(g['alpha']), float(g['eps']), mom, 0.0, int(centered))
+        check(lib().pa_rmsprop_step_groups(C.byref(o), tab, ngroups, ptr(self._map), ptr(self.net.flat_params), ptr(self.net.flat_grads),
+                                           ptr(self.square_avg), ptr(self.momentum_buffer) if mom > 0 else None,
+                                           ptr(self.grad_avg) if centered else None, n, float(gscale), coef, ptr(self._skip_state), stream()),
+              'pa_rmsprop_step_groups')
 
     def skip_flag_ptr(self):
         """device address of the int32 "the last step was skipped" flag (ModelEma.update reads it on the device)"""
@@ -245,9 +444,7 @@ class RMSprop(_FlatOptimizer):
             state[i] = {'step': self.steps, 'square_avg': self.square_avg[off:off + numel].view(shape).clone()}
             for key, flat in self._option_state(self.param_groups[0]):          # torch's keys, present when the option is on
                 state[i][key] = flat[off:off + numel].view(shape).clone()
-        pg = dict(self.param_groups[0])
-        pg['params'] = list(range(len(state)))
-        return {'state': state, 'param_groups': [pg]}
+        return {'state': state, 'param_groups': self._state_groups()}
 
     def load_state_dict(self, sd):
         """Accepts this class's own files and torch.optim.RMSprop's: `state` is keyed by the entries of
@@ -264,13 +461,19 @@ class RMSprop(_FlatOptimizer):
         for _, flat in extra:
             flat.zero_()
         state = sd.get('state', {})
-        keys = list(sd['param_groups'][0].get('params', range(len(params))))
-        if len(keys) != len(params):
-            warnings.warn('optimizer state has %d parameters, the network %d: square_avg not loaded' % (len(keys), len(params)))
+        keys, matched = self._file_keys(sd)
+        if keys is None:
+            warnings.warn('optimizer state has %d parameters, the network %d: square_avg not loaded'
+                          % (sum(len(fg.get('params', [])) for fg in sd['param_groups']), len(params)))
             keys = []
         missing = 0
-        for key, (name, shape, off, numel, kind) in zip(keys, params):
+        frozen = self._frozen_params()
+        for i, (key, (name, shape, off, numel, kind)) in enumerate(zip(keys, params)):
             st = state.get(key)
+            if st is None and i in frozen:              # (torch keeps no state for a parameter it never stepped)
+                for ekey in loaded:
+                    loaded[ekey] += 1
+                continue
             if st is None or 'square_avg' not in st:
                 missing += 1
                 continue
@@ -291,9 +494,12 @@ class RMSprop(_FlatOptimizer):
                 warnings.warn('optimizer state: %d of %d parameters had no %s entry (left at zero)' % (len(params) - loaded[ekey], len(params), ekey))
         if missing and state:
             warnings.warn('optimizer state: %d of %d parameters had no square_avg entry (left at their current value)' % (missing, len(params)))
-        for k, v in sd['param_groups'][0].items():
-            if k != 'params':
-                self.param_groups[0][k] = v
+        if not self._grouped() and len(sd['param_groups']) == 1:
+            for k, v in sd['param_groups'][0].items():
+                if k != 'params':
+                    self.param_groups[0][k] = v
+        else:
+            self._load_groups(sd, matched, self._shared)
 
 
 _ADAM_KEYS = ('lr', 'betas', 'eps', 'weight_decay', 'amsgrad', 'decoupled_weight_decay')
@@ -301,11 +507,12 @@ _ADAM_KEYS = ('lr', 'betas', 'eps', 'weight_decay', 'amsgrad', 'decoupled_weight
 
 class Adam(_FlatOptimizer):
     def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, decoupled_weight_decay=False,
-                 max_grad_norm=None, overlap=False):
+                 max_grad_norm=None, overlap=False, groups=None):
         """torch.optim.Adam (torch 2.10 _single_tensor_adam) as one fused step on the flat arrays (pa_adam_step): weight_decay coupled
         (added to the gradient) or, with decoupled_weight_decay, AdamW's p *= 1 - lr weight_decay; amsgrad keeps the running maximum
         of exp_avg_sq (max_exp_avg_sq, allocated when amsgrad is first on).  All of them live in param_groups[0] and are read at every
-        step, like lr.  max_grad_norm and overlap: as for RMSprop.
+        step, like lr.  max_grad_norm, overlap and groups: as for RMSprop (pa_adam_step_groups; the step sizes lr_k / bc1 of the groups
+        live in self._group_consts on the device).
         The step count of the bias correction lives on the device (self._state, a pa_adam_state): the fp16 build decides there whether
         a step is taken, and a skipped step must not advance it.  steps_taken() and state_dict() read it, which synchronises."""
         b1, b2 = betas
@@ -314,8 +521,8 @@ class Adam(_FlatOptimizer):
         if not eps > 0 or weight_decay < 0:
             raise ValueError('eps must be > 0 and weight_decay >= 0')
         self._attach(net, max_grad_norm, overlap)
-        self.param_groups = [{'lr': lr, 'betas': (b1, b2), 'eps': eps, 'weight_decay': weight_decay, 'amsgrad': bool(amsgrad),
-                              'decoupled_weight_decay': bool(decoupled_weight_decay)}]
+        self._init_groups({'lr': lr, 'betas': (b1, b2), 'eps': eps, 'weight_decay': weight_decay, 'amsgrad': bool(amsgrad),
+                           'decoupled_weight_decay': bool(decoupled_weight_decay)}, groups)
         self.exp_avg = torch.zeros_like(net.flat_params)
         self.exp_avg_sq = torch.zeros_like(net.flat_params)
         self.max_exp_avg_sq = None
@@ -333,10 +540,19 @@ class Adam(_FlatOptimizer):
         n = self.net.flat_params.numel()
         amsgrad = bool(g.get('amsgrad', False))
         self._ensure_state(g)
-        coef = self._clip_coef(n, gscale)
         b1, b2 = g['betas']
         o = _lib.AdamOpts(float(g['lr']), float(b1), float(b2), float(g['eps']), float(g.get('weight_decay', 0)), int(amsgrad),
                           int(bool(g.get('decoupled_weight_decay', False))))
+        if self._grouped():
+            tab, ngroups, frozen = self._group_table()
+            coef = self._clip_coef(n, gscale, frozen)
+            check(lib().pa_adam_step_groups(C.byref(o), tab, ngroups, ptr(self._map), ptr(self._group_consts), ptr(self.net.flat_params),
+                                            ptr(self.net.flat_grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                                            ptr(self.max_exp_avg_sq) if amsgrad else None, n, float(gscale), coef, ptr(self._state), stream()),
+                  'pa_adam_step_groups')
+            self._weights_stepped()
+            return
+        coef = self._clip_coef(n, gscale)
         check(lib().pa_adam_step(C.byref(o), ptr(self.net.flat_params), ptr(self.net.flat_grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                                  ptr(self.max_exp_avg_sq) if amsgrad else None, n, float(gscale), coef, ptr(self._state), stream()),
               'pa_adam_step')
@@ -372,10 +588,7 @@ class Adam(_FlatOptimizer):
             state[i] = {'step': torch.tensor(float(steps), dtype=torch.float32)}
             for key, flat in self._moments(self.param_groups[0]):
                 state[i][key] = flat[off:off + numel].view(shape).clone()
-        pg = dict(self.param_groups[0])
-        pg['betas'] = tuple(pg['betas'])
-        pg['params'] = list(range(len(state)))
-        return {'state': state, 'param_groups': [pg]}
+        return {'state': state, 'param_groups': self._state_groups()}
 
     def load_state_dict(self, sd):
         """Accepts this class's own files and torch.optim.Adam's / AdamW's: `state` is keyed by the entries of param_groups[0]['params']
@@ -402,14 +615,19 @@ class Adam(_FlatOptimizer):
         for _, flat in moments:
             flat.zero_()
         loaded = dict((key, 0) for key, _ in moments)
-        keys = list(file_group.get('params', range(len(params))))
-        if len(keys) != len(params):
-            warnings.warn('optimizer state has %d parameters, the network %d: the moments are not loaded' % (len(keys), len(params)))
+        keys, matched = self._file_keys(sd)
+        if keys is None:
+            warnings.warn('optimizer state has %d parameters, the network %d: the moments are not loaded'
+                          % (sum(len(fg.get('params', [])) for fg in sd['param_groups']), len(params)))
             keys = []
         steps = set()
-        for key, (name, shape, off, numel, kind) in zip(keys, params):
+        frozen = self._frozen_params()
+        for i, (key, (name, shape, off, numel, kind)) in enumerate(zip(keys, params)):
             st = state.get(key)
             if st is None:
+                if i in frozen:                         # (torch keeps no state for a parameter it never stepped)
+                    for mkey in loaded:
+                        loaded[mkey] += 1
                 continue
             for mkey, flat in moments:
                 e = st.get(mkey)
@@ -430,17 +648,20 @@ class Adam(_FlatOptimizer):
         if len(steps) > 1:
             warnings.warn('optimizer state: the parameters have different step counts %s; the largest is used' % sorted(steps))
         self._set_steps(max(steps) if steps else 0)
-        self.param_groups[0].update(group)
+        if not self._grouped() and len(sd['param_groups']) == 1:
+            self.param_groups[0].update(group)
+        else:
+            self._load_groups(sd, matched, tuple(k for k in _ADAM_KEYS if k not in ('lr', 'weight_decay')))
 
     def _set_steps(self, steps):
         check(lib().pa_adam_set_steps(ptr(self._state), int(steps), stream()), 'pa_adam_set_steps')
 
 
 class AdamW(Adam):
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, max_grad_norm=None, overlap=False):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, max_grad_norm=None, overlap=False, groups=None):
         """torch.optim.AdamW: Adam with decoupled weight decay and torch's default weight_decay"""
         Adam.__init__(self, net, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, decoupled_weight_decay=True,
-                      max_grad_norm=max_grad_norm, overlap=overlap)
+                      max_grad_norm=max_grad_norm, overlap=overlap, groups=groups)
 
 
 class ModelEma(object):
@@ -546,8 +767,9 @@ def make_optimizer(opt, net, lr, overlap=False):
     --weight_decay (coupled for adam, decoupled for adamw; passed as given, so 0 means none for adamw too) and --clip_grad_norm are
     shared between the kinds."""
     kind = getattr(opt, 'optimizer', 'rmsprop')
+    groups = group_specs(opt, net)
     if kind == 'rmsprop':
-        return RMSprop(net, lr=lr, alpha=0.99, eps=1e-8, overlap=overlap, **optim_options(opt))
+        return RMSprop(net, lr=lr, alpha=0.99, eps=1e-8, overlap=overlap, groups=groups, **optim_options(opt))
     if kind not in ('adam', 'adamw'):
         raise ValueError('unknown optimizer %r' % (kind,))
     if float(getattr(opt, 'momentum', 0) or 0) != 0 or getattr(opt, 'centered', 0):
@@ -555,5 +777,52 @@ def make_optimizer(opt, net, lr, overlap=False):
     clip = float(getattr(opt, 'clip_grad_norm', 0) or 0)
     kw = dict(lr=lr, betas=(float(getattr(opt, 'beta1', 0.9)), float(getattr(opt, 'beta2', 0.999))), eps=float(getattr(opt, 'adam_eps', 1e-8)),
               weight_decay=float(getattr(opt, 'weight_decay', 0) or 0), amsgrad=bool(getattr(opt, 'amsgrad', 0)),
-              max_grad_norm=clip if clip > 0 else None, overlap=overlap)
+              max_grad_norm=clip if clip > 0 else None, overlap=overlap, groups=groups)
     return (AdamW if kind == 'adamw' else Adam)(net, **kw)
+
+
+def group_specs(opt, net):
+    """The `groups` argument the command line asks for (options/train_options.py: --no_decay_1d 1, --freeze REGEX, --lr_group REGEX:MULT,
+    repeatable); None with all of them off, the default: one group.  --freeze and --lr_group are the pose net's (a net with
+    num_stacks); the agent's optimizer takes --no_decay_1d only.  Order, first match wins: the frozen tensors, then every --lr_group
+    in the order given, then the remaining 1-D tensors.  With --no_decay_1d the 1-D tensors of an --lr_group form a group of their own
+    (that rate, no decay).  A REGEX that matches no parameter is an error, so a typo cannot silently train everything."""
+    import re
+    no_decay = bool(getattr(opt, 'no_decay_1d', 0))
+    pose = hasattr(net, 'num_stacks')
+    freeze = (getattr(opt, 'freeze', '') or '') if pose else ''
+    lr_groups = list(getattr(opt, 'lr_group', None) or []) if pose else []
+    if not (no_decay or freeze or lr_groups):
+        return None
+    net._ensure_table()
+    params = [(t[0], tuple(t[1])) for t in net._table if t[4] == 0]
+    left = list(params)
+    specs = []
+
+    def take(what, rx, **values):
+        hit = [(n, s) for n, s in left if re.search(rx, n)]
+        if not [1 for n, s in params if re.search(rx, n)]:
+            raise ValueError('%s %r matches no parameter of the net' % (what, rx))
+        split = no_decay and 'frozen' not in values          # the 1-D tensors of the match: a group of their own, without decay
+        one_d = [t for t in hit if len(t[1]) <= 1] if split else []
+        for part, v in ((one_d, dict(values, weight_decay=0.0)), ([t for t in hit if t not in one_d], values)):
+            if part:
+                specs.append(dict(v, params=[n for n, _ in part]))
+        left[:] = [t for t in left if t not in hit]
+
+    if freeze:
+        take('--freeze', freeze, frozen=True)
+    for item in lr_groups:
+        rx, sep, mult = item.rpartition(':')
+        try:
+            mult = float(mult)
+        except ValueError:
+            sep = ''
+        if not sep or not rx or not mult >= 0:
+            raise ValueError('--lr_group %r: expected REGEX:MULT with MULT >= 0' % (item,))
+        take('--lr_group', rx, lr_mult=mult)
+    if no_decay:
+        rest = [n for n, s in left if len(s) <= 1]
+        if rest:
+            specs.append(dict(params=rest, weight_decay=0.0))
+    return specs

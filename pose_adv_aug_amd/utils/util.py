@@ -116,7 +116,7 @@ def adjust_lr(opt, optimizer, epoch):
     elif epoch == 140:
         opt.lr = opt.lr * 0.5
     for g in optimizer.param_groups:
-        g['lr'] = opt.lr
+        g['lr'] = opt.lr * g.get('lr_mult', 1.0)          # (a parameter group keeps its own multiple of the schedule; one group: 1)
 
 
 def mkdirs(paths):
