@@ -8,7 +8,7 @@
 //     / BatchNorm backward is applied in this pass), then loops over the output-channel blocks itself,
 //     so the input is not re-read per 128 output channels;
 //   * the weight slices [BN][64] are streamed with global_load_lds, double buffered (conv3x3_tile.hip);
-//   * two or three workgroups per CU (48-64 KB LDS): one stages while the others compute; 64-row tiles so that a
+//   * two to four workgroups per CU (28-64 KB LDS, pa_conv1_occ): one stages while the others compute; 64-row tiles so that a
 //     24 x 64 x 64 map is 1536 workgroups = full rounds (conv_plan.h).
 // LDS images: activation tile [BM][CIN] and weight slice [BN][64] bf16, 16-byte slots XOR-swizzled by the
 // row so that the ds_read_b128 fragment reads are bank-conflict free.  Epilogue: conv_epilogue.h (forward modes through
@@ -30,8 +30,38 @@ PA_STAMP_DECL(pa_conv1t_clk, pa_debug_conv1t_clocks)
 #ifndef PA_CONV1_UP_OCC
 #define PA_CONV1_UP_OCC(up) 3          // workgroups per CU of the 3-workgroup instances (the UP instance included)
 #endif
+#ifndef PA_CONV1_OCC4
+#define PA_CONV1_OCC4(cin, bm, bn, ld) 4   // workgroups per CU of the 4-workgroup instances (A/B builds: -D'PA_CONV1_OCC4(cin,bm,bn,ld)=3' restores the 3-workgroup code)
+#endif
 #define PA_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define PA_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
+
+// Workgroups per CU of an instance (its __launch_bounds__): 2, 3 or 4.
+//   4: instances of the 128 x 128 maps of residual1 (64 input channels; 128 -> 64 channels in 64-row tiles).  Their LDS (28-35 KB) leaves room
+//      for four; what held them at three was the register budget alone (154-168 VGPRs, filled because they were there: <= 128 registers give
+//      four waves per SIMD).  Every load variant of these shapes compiles to 128 registers without scratch; four is kept for the variants whose
+//      time in the step's kernel trace fell by more than the run-to-run spread (DESIGN.md "Four workgroups per CU"):
+//        128 -> 64, 64-row tiles: plain load (76 -> 31 us) and the pool-routed input (103 -> 91); BatchNorm backward on load stayed at 30
+//        64 -> 64, 128-row tiles: BatchNorm + ReLU on load (27.8 -> 26.3); BatchNorm backward on load measured slower at four (103 -> 126 us, beside the
+//        adapter's data gradient on the other queue: the pair's times trade places, see DESIGN.md before moving it)
+//        64 -> 128, 64-row tiles: plain (31.0 -> 30.2) and BatchNorm backward on load (22.4 -> 19.3); BatchNorm + ReLU stayed at 41
+//      (variants the benchmark does not launch stay at three: nothing was measured)
+//   3: the other 64-row instances with 128 input channels or 32-channel weight slices (52 KB of LDS), and the rest of the shapes above
+//   2: everything else
+constexpr bool pa_conv1_occ4_inst(int CIN, int BM, int BN, int LD, bool PIN) {
+    if (CIN == 128 && BM == 64 && BN == 64) return LD == PA_LD_PLAIN || PIN;
+    if (CIN == 64 && BM == 128 && BN == 64) return LD == PA_LD_BNRELU;
+    if (CIN == 64 && BM == 64 && BN == 128) return LD == PA_LD_PLAIN || LD == PA_LD_LIN2;
+    return false;
+}
+constexpr int pa_conv1_occ(int CIN, int BM, int BN, int LD, int KS, bool UP, bool PIN) {
+    if (pa_conv1_occ4_inst(CIN, BM, BN, LD, PIN)) return PA_CONV1_OCC4(CIN, BM, BN, LD);
+    if (((CIN == 128 || KS == 32) && BM == 64) || (CIN == 64 && (BN == 64 || BM == 64))) return PA_CONV1_UP_OCC(UP);
+    return 2;
+}
+// channels per weight slice: 64, but 32 for the 256-channel 64-row instance (below) and for the 64 -> 128 channel instances at four workgroups
+// per CU (8 KB of activations + 2 x 8 KB of ring + 4 KB table = 28 KB instead of 44); the MFMA steps walk the 32-wide k-blocks in the same order
+constexpr int pa_conv1_ks(int CIN, int BM, int BN, int LD) { return (CIN == 64 && BM == 64 && BN == 128 && pa_conv1_occ(CIN, BM, BN, LD, 64, false, false) == 4) ? 32 : 64; }
 
 // KS: channels per weight slice of the ring.  64 (two 32-wide MFMA steps per slice) everywhere but the 256-channel, 64-row instance of
 // round 5 (KS = 32): its LDS is 32 KB of activations + 2 x 8 KB of ring (+ 4 KB table) = 52 KB and its registers <= 168, so that THREE
@@ -47,7 +77,8 @@ PA_STAMP_DECL(pa_conv1t_clk, pa_debug_conv1t_clocks)
 // arg-max map, masked by the ReLU of the pooled tensor q (a.ep2.scale / shift: the epilogue the pool backward launch would have applied; its
 // reductions come from maxpool_bwd_stats_kernel).  The transformed tile goes to dz_out as in every LIN2 instance.
 template <int CIN, int BM, int BN, int LDMODE, int KS = 64, bool UP = false, int POOL = PA_POOL_EP_NONE, bool PIN = false>
-__global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CIN == 64 && (BN == 64 || BM == 64))) ? PA_CONV1_UP_OCC(UP) : 2) void conv1x1_tile_kernel(PaConvArgs a, int nb_per_wg) {
+__global__ __launch_bounds__(256, pa_conv1_occ(CIN, BM, BN, LDMODE, KS, UP, PIN)) void conv1x1_tile_kernel(PaConvArgs a, int nb_per_wg) {
+    constexpr bool OCC4 = pa_conv1_occ(CIN, BM, BN, LDMODE, KS, UP, PIN) == 4;      // four workgroups per CU: 128 registers, the leaner forms below
     constexpr int CPP = CIN / 8;                     // 16-byte chunks per pixel row
     constexpr int NI = BN / 32, MI = BM / 32;
     constexpr int KT = CIN / KS;
@@ -60,7 +91,8 @@ __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CI
     // (the table form is the only BatchNorm-backward epilogue these instances carry; 64 input channels -- the 128 x 128 maps of residual1:
     // 64 output channels in 128-row tiles or 128 in 64-row tiles, three workgroups per CU either way)
     constexpr bool CTAB = (BM == 64 && ((CIN == 128 && LDMODE == PA_LD_LIN2) || KS == 32)) || (CIN == 64 && (BN == 64 || BM == 64));
-    __shared__ __attribute__((aligned(16))) bf16 lds[BM * CIN + 2 * BN * KS + (CTAB ? 2 * BN * 8 : 0)];
+    // (OCC4: the forward epilogue's table as well -- 2 KB more for the 128 -> 64 channel instances with plain / BatchNorm+ReLU loads)
+    __shared__ __attribute__((aligned(16))) bf16 lds[BM * CIN + 2 * BN * KS + ((CTAB || OCC4) ? 2 * BN * 8 : 0)];
     bf16* As = lds;
     bf16* wbuf = lds + BM * CIN;
 
@@ -241,9 +273,9 @@ __global__ __launch_bounds__(256, (((CIN == 128 || KS == 32) && BM == 64) || (CI
                                                 [&](int x) { return up_rp * (a.W / 2) + up_cx * (BM / 4) + (x >> 1); },
                                                 T, (int)blockIdx.x, reinterpret_cast<float4*>(lds + BM * CIN + 2 * BN * KS));
         } else
-        pa_conv_epilogue_auto<BN, NI, MI, (CIN == 256 || CIN == 64 || CTAB), CTAB, 256, (BN < 128), POOL>(a, acc, (nb0 + nbi) * BN, wm, wn,
+        pa_conv_epilogue_auto<BN, NI, MI, (CIN == 256 || CIN == 64 || CTAB), CTAB, 256, (BN < 128), POOL, OCC4>(a, acc, (nb0 + nbi) * BN, wm, wn,
                                          [&](int wr, int mi, int p) { const int m = m0 + wr * (BM / 2) + mi * 16 + p; return m < M ? m : -1; },
-                                         T, (int)blockIdx.x, CTAB ? reinterpret_cast<float4*>(lds + BM * CIN + 2 * BN * KS) : nullptr);
+                                         T, (int)blockIdx.x, (CTAB || OCC4) ? reinterpret_cast<float4*>(lds + BM * CIN + 2 * BN * KS) : nullptr);
         if (nbi == 0) PA_STAMPT(5);                   // its epilogue
         __syncthreads();            // T is handed back to the weight ring
     }
@@ -282,7 +314,13 @@ int pa_launch_conv1x1_tile(const PaConvArgs& a0, const PaConvPlan& p, hipStream_
         case PA_CT_R128_64_64: launch_row_ld<128, 64, 64>(a, v, grid, nbw, st); break;
         case PA_CT_R128_128_128: launch_row_ld<128, 128, 128, 64, true>(a, v, grid, nbw, st); break;
         case PA_CT_R128_128_64: launch_row_ld<128, 128, 64, 64, true>(a, v, grid, nbw, st); break;
-        case PA_CT_R64_64_128: launch_row_ld<64, 64, 128>(a, v, grid, nbw, st); break;
+        case PA_CT_R64_64_128:          // (the weight slice width goes with the variant's workgroups per CU)
+            switch (v) {
+                case PA_LD_PLAIN: hipLaunchKernelGGL((conv1x1_tile_kernel<64, 64, 128, PA_LD_PLAIN, pa_conv1_ks(64, 64, 128, PA_LD_PLAIN)>), grid, dim3(256), 0, st, a, nbw); break;
+                case PA_LD_BNRELU: hipLaunchKernelGGL((conv1x1_tile_kernel<64, 64, 128, PA_LD_BNRELU, pa_conv1_ks(64, 64, 128, PA_LD_BNRELU)>), grid, dim3(256), 0, st, a, nbw); break;
+                default: hipLaunchKernelGGL((conv1x1_tile_kernel<64, 64, 128, PA_LD_LIN2, pa_conv1_ks(64, 64, 128, PA_LD_LIN2)>), grid, dim3(256), 0, st, a, nbw); break;
+            }
+            break;
         case PA_CT_R64_128_128: launch_row_ld<64, 128, 128>(a, v, grid, nbw, st); break;
         case PA_CT_R64_128_64: launch_row_ld<64, 128, 64>(a, v, grid, nbw, st); break;
         default: pa_set_error_msg("pa_launch_conv1x1_tile: the plan names no instance of conv1x1_tile.hip"); return 1;

@@ -60,11 +60,27 @@ template <int N> __device__ __forceinline__ void pa_wait_vmcnt() {
 // round trip ~150, 17 per MFMA: 45-60 cycles per MFMA instead of 17), and the staging / epilogue are load / store round trips of 4 waves.  Two
 // waves per SIMD (the same 128 pixels x 64 channels, MI = 2 fragments per wave) let one wave's MFMAs run under another's waits (measured 8x8:
 // 14.1 / 10.6 / 12.8 us at 256 / 512 / 1024 threads).
+// Workgroups per CU of an instance (its __launch_bounds__).  512 threads: 1.  16 x 8 tiles: 2, but 4 for 64 -> 64 channels with a BatchNorm on
+// load (the 128 x 128 maps of residual1: 38.5 KB of LDS; under a bound of 2 they took 157 registers and ran three, stopped by registers, not
+// LDS; at four 60.5 -> 53.5 us with BatchNorm backward on load, 32.7 -> 31.6 with BatchNorm + ReLU).  16 x 4 tiles: 3 (one slice per step) or 2.
+// 8 x 8 / 4 x 4 tiles: 1.   A/B builds: -D'PA_CONV3_OCC4(cin,bn)=2' restores the earlier bound and code
+// (the plain-load variant stays at 2: the benchmark does not launch it, nothing was measured.  The FIN instances of that tiling stay at 2: the
+// finalize prologue keeps 32 16-byte loads = 128 registers in flight by design (bn_fin.h) and spills 108 bytes under a 128-register bound;
+// they serve launches of at most 128 tiles, less than one workgroup per CU)
+#ifndef PA_CONV3_OCC4
+#define PA_CONV3_OCC4(cin, bn) 4
+#endif
+constexpr int pa_conv3_occ(int CIN, int BN, int LD, int TW, int TH, int SPS, int NT, bool FIN) {
+    if (NT >= 512) return 1;
+    if (TW != 16) return 1;
+    if (TH == 4) return SPS == 1 ? 3 : 2;
+    return (CIN == 64 && BN == 64 && LD != PA_LD_PLAIN && !FIN) ? PA_CONV3_OCC4(CIN, BN) : 2;
+}
 // cycle stamps (tuning builds, a.dbg & 64): entry / weight ring issued / own halo part staged / K loop / barrier / epilogue
 PA_STAMP_DECL(pa_conv3_clk, pa_debug_conv3_clocks)
 #define PA_STAMP(i) PA_STAMP_AT(pa_conv3_clk, a.dbg & 64, i)
 template <int CIN, int BN, int LDMODE, int TW = 16, int TH = 8, int SPS = 1, bool PF = false, int NT = 256, bool FIN = false>
-__global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS == 1 ? 3 : 2) : 2) : 1))) void conv3x3_tile_kernel(PaConvArgs a) {
+__global__ __launch_bounds__(NT, pa_conv3_occ(CIN, BN, LDMODE, TW, TH, SPS, NT, FIN)) void conv3x3_tile_kernel(PaConvArgs a) {
     PA_SET_MAIN_PRIO();
     PA_STAMP(0);
 #if defined(PA_TUNING) && !defined(PA_CONV3_CONSTDBG)      // (PA_EXTRA=-DPA_CONV3_CONSTDBG: the release code with the cycle stamps only)
@@ -393,7 +409,10 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
         return;
     }
 
-    pa_conv_epilogue_auto<BN, NI, MI, true, false, NT>(a, acc, n0, wm, wn,
+    // (four workgroups per CU: the table forms of the epilogues; their 2 KB table sits behind T in the dead halo / ring)
+    constexpr bool OCC4 = pa_conv3_occ(CIN, BN, LDMODE, TW, TH, SPS, NT, FIN) == 4;
+    static_assert(!OCC4 || sizeof(lds) >= 16 * NT * sizeof(float) + 2 * BN * sizeof(float4), "epilogue tile + constant table");
+    pa_conv_epilogue_auto<BN, NI, MI, true, false, NT, false, 0, OCC4>(a, acc, n0, wm, wn,
                                      [&](int wr, int mi, int p) {
                                          const int l = (wr * MI + mi) * 16 + p;
                                          const int im = l / (TW * TH), r = l - im * (TW * TH);
@@ -401,7 +420,7 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? 1 : (TW == 16 ? (TH == 4 ? (SPS ==
                                          origin(im, bb, yy, xx);
                                          return (bb < a.B && yy + r / TW < a.H && xx + r % TW < a.W) ? (bb * a.H + yy + r / TW) * a.W + xx + r % TW : -1;
                                      },
-                                     reinterpret_cast<float*>(lds), (int)blockIdx.x);
+                                     reinterpret_cast<float*>(lds), (int)blockIdx.x, OCC4 ? reinterpret_cast<float4*>(lds) + 4 * NT : nullptr);
     PA_STAMP(5);
 }
 

@@ -10,6 +10,9 @@
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#ifndef PA_EPI_LEAN_MG
+#define PA_EPI_LEAN_MG 2                             // pixels per operand request of the direct epilogue inside a 128-register (LEAN) kernel
+#endif
 #ifndef PA_EPI_STAMP
 #define PA_EPI_STAMP(i) do { } while (0)
 #endif
@@ -39,8 +42,9 @@ __device__ __forceinline__ int pa_lds_row_of_weight_row(int c) {
 // The per-channel constants (BatchNorm-backward scale/shift/mean/invstd, the transforms of the two addends, the bias)
 // are staged ONCE per call into LDS: read from global per use they were ~180 of the ~200 load instructions of a
 // data-gradient epilogue, all in front of the data loads in the in-order vmcnt queue.  Per 8-channel chunk the
-// operand loads of all MI pixels are issued together, before the first use.
-template <int BN, int NI, int MI, class PixFn>
+// operand loads of all MI pixels are issued together, before the first use (MG < MI, the 128-register kernels: of MG pixels at a time, in
+// the same order).
+template <int BN, int NI, int MI, int MG = MI, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
                                                  PixFn pix, float* red, int stat_row) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -71,7 +75,9 @@ __device__ __forceinline__ void pa_conv_epilogue(const PaConvArgs& a, f32x4 (&ac
         unsigned idx[MI];                            // 32-bit element offsets: pa_launch_conv admits M * Cout < 2^31 only
         bf16x8 xr[MI], p1[MI], q1[MI], p2[MI], q2[MI];
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
+        for (int mg = 0; mg < MI; mg += MG) {
+#pragma unroll
+        for (int mi = mg; mi < mg + MG; ++mi) {
             const int m = pix(mi);
             idx[mi] = m < 0 ? 0u : (unsigned)m * (unsigned)N + (unsigned)n;     // clamped: unconditional loads, the store is guarded
             if (a.ep.mode == PA_OUT_BWD) xr[mi] = *reinterpret_cast<const bf16x8*>(a.ep.xref + idx[mi]);
@@ -81,7 +87,7 @@ __device__ __forceinline__ void pa_conv_epilogue(const PaConvArgs& a, f32x4 (&ac
             if (m2 == PA_LD_LIN2) q2[mi] = *reinterpret_cast<const bf16x8*>(a.add2.q + idx[mi]);
         }
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
+        for (int mi = mg; mi < mg + MG; ++mi) {
             if (pix(mi) < 0) continue;
             bf16x8 o;
 #pragma unroll
@@ -111,6 +117,7 @@ __device__ __forceinline__ void pa_conv_epilogue(const PaConvArgs& a, f32x4 (&ac
                 }
             }
             *reinterpret_cast<bf16x8*>(a.out + idx[mi]) = o;
+        }
         }
     }
     if (a.ep.mode != PA_OUT_PLAIN) {
@@ -245,21 +252,28 @@ __device__ __forceinline__ float pa_pool_value(const PaPoolRaw& r, bool has_e, i
 // FUSE (MI * BN <= 128, i.e. the whole workgroup tile fits the 16 * NT floats the statistics reduction needs anyway): all MI passes are staged at
 // once -- one barrier instead of 2 * MI - 1
 // POOL: the second addend is pool-routed (PA_LD_POOL, pa_pool_request) -- instances of their own
-template <int BN, int NI, int MI, int NT = 256, bool TSMALL = false, bool FUSE = false, bool POOL = false, class PixFn>
+// LEAN (the kernels that run four workgroups per CU in 128 registers): the bias and the addends' per-channel constants live in LDS (ctab, 2 * BN
+// float4 outside T: {k0, k1, k2, bias} of addend 1, {k0, k1, k2, -} of addend 2, entry j * CPR + chunk as in pa_conv_epilogue_lds_bwd) instead of
+// in up to 56 registers, nothing is requested ahead of the sweep that uses it, and the thread index is opaque so that no address arithmetic is
+// hoisted out of the caller's channel-block loop.  Same expressions, same order.
+template <int BN, int NI, int MI, int NT = 256, bool TSMALL = false, bool FUSE = false, bool POOL = false, bool LEAN = false, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
-                                                     PixFn pix, float* T, int stat_row) {
+                                                     PixFn pix, float* T, int stat_row, float4* ctab = nullptr) {
+    static_assert(!LEAN || (!POOL && !FUSE && BN <= NT), "table form: plain addends, staged pass by pass");
     constexpr int CPR = BN / 8;                      // 8-channel chunks per pixel row
     constexpr int RPS = NT / CPR;                    // pixel rows per sweep of the NT threads
     constexpr int SW = (NT / 8) / RPS;               // sweeps per pass of NT / 8 rows (16 per wave row)
     constexpr int NW = NT / 64;
-    const int tid = threadIdx.x, lane = tid & 63;
+    int tid = threadIdx.x;
+    if constexpr (LEAN) asm volatile("" : "+v"(tid));      // (opaque: nothing derived from it is hoisted out of the caller's channel-block loop, across the K loop)
+    const int lane = tid & 63;
     const int N = a.Cout;
     const int chunk = tid % CPR, rsub = tid / CPR;
     const int n = n0 + chunk * 8;
     float bias[8], s1[8], s2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; bias[j] = 0.f; }
-    if (a.bias) {                                    // (one uniform branch around the eight loads: a select per element made hipcc wait for them in front of the staging)
+    if (!LEAN && a.bias) {                           // (one uniform branch around the eight loads: a select per element made hipcc wait for them in front of the staging)
 #pragma unroll
         for (int j = 0; j < 8; ++j) bias[j] = a.bias[n + j];
     }
@@ -267,8 +281,33 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
     // per-channel constants are requested HERE, before the staging barrier, instead of inside each sweep (a memory round trip per sweep with
     // one wave per SIMD).  Same arithmetic as pa_read8 (pa_apply8).
     constexpr int IT = MI * SW;
-    constexpr bool PRE = IT <= 2;
+    constexpr bool PRE = IT <= 2 && !LEAN;
     const int m1 = a.add1.mode, m2 = a.add2.mode;
+    if constexpr (LEAN) {
+        if (tid < BN) {
+            const int e = (tid & 7) * CPR + (tid >> 3), c = n0 + tid;
+            float4 k1 = make_float4(0.f, 0.f, 0.f, a.bias ? a.bias[c] : 0.f), k2 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (m1 == PA_LD_BNRELU || m1 == PA_LD_LIN2) { k1.x = a.add1.k0[c]; k1.y = a.add1.k1[c]; if (m1 == PA_LD_LIN2) k1.z = a.add1.k2[c]; }
+            if (m2 == PA_LD_BNRELU || m2 == PA_LD_LIN2) { k2.x = a.add2.k0[c]; k2.y = a.add2.k1[c]; if (m2 == PA_LD_LIN2) k2.z = a.add2.k2[c]; }
+            ctab[e] = k1; ctab[BN + e] = k2;
+        }                                            // (visible after the first pass barrier below)
+    }
+    // one addend of a sweep from its raw operands and the table (LEAN)
+    auto addend_tab = [&](int md, const bf16x8& p, const bf16x8& q, const float4* kt, float (&v)[8]) {
+        if (md == PA_LD_NONE) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = 0.f;
+        } else if (md == PA_LD_PLAIN) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (float)p[j];
+        } else if (md == PA_LD_BNRELU) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float4 k = kt[j * CPR + chunk]; v[j] = fmaxf(fmaf(k.x, (float)p[j], k.y), 0.f); }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float4 k = kt[j * CPR + chunk]; v[j] = fmaf(k.x, (float)p[j], fmaf(k.y, (float)q[j], k.z)); }
+        }
+    };
     bf16x8 p1[PRE ? IT : 1], q1[PRE ? IT : 1], p2[PRE ? IT : 1], q2[PRE ? IT : 1];
     PaPoolRaw pr[POOL && PRE ? IT : 1];
     const bool pool_e = POOL && a.add2.q != nullptr;
@@ -362,6 +401,16 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
                     for (int j = 0; j < 8; ++j) e2[j] = pa_pool_value(pr[mi * SW + sw], pool_e, j);
                 } else
                 addend(m2, p2[mi * SW + sw], q2[mi * SW + sw], ka2, kb2, kc2, e2);
+            } else if constexpr (LEAN) {
+                bf16x8 rp1, rq1, rp2, rq2;
+                if (m1 != PA_LD_NONE) rp1 = *reinterpret_cast<const bf16x8*>(a.add1.p + idx);
+                if (m1 == PA_LD_LIN2) rq1 = *reinterpret_cast<const bf16x8*>(a.add1.q + idx);
+                if (m2 != PA_LD_NONE) rp2 = *reinterpret_cast<const bf16x8*>(a.add2.p + idx);
+                if (m2 == PA_LD_LIN2) rq2 = *reinterpret_cast<const bf16x8*>(a.add2.q + idx);
+                addend_tab(m1, rp1, rq1, ctab, e1);
+                addend_tab(m2, rp2, rq2, ctab + BN, e2);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) bias[j] = reinterpret_cast<const float*>(ctab + j * CPR + chunk)[3];
             } else {
                 if constexpr (POOL) {
                     PaPoolRaw r;
@@ -403,7 +452,7 @@ __device__ __forceinline__ void pa_conv_epilogue_lds(const PaConvArgs& a, f32x4 
 // is accumulated as sum(dz * x) and turned into sum(dz * xhat) = invstd * (sum(dz*x) - mean * sum(dz)) once per
 // workgroup row, which removes mean / invstd from the per-element work.
 // POOL: the second addend is pool-routed (PA_LD_POOL, pa_pool_request) instead of plain -- instances of their own
-template <int BN, int NI, int MI, bool TAB, int NT = 256, bool TSMALL = false, bool FUSE = false, bool POOL = false, class PixFn>
+template <int BN, int NI, int MI, bool TAB, int NT = 256, bool TSMALL = false, bool FUSE = false, bool POOL = false, bool LEAN = false, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue_lds_bwd(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
                                                          PixFn pix, float* T, int stat_row, float4* ctab = nullptr) {
     // ctab (optional, 2 * BN float4 of LDS outside T): the per-channel constants live there instead of in 40 registers
@@ -416,7 +465,9 @@ __device__ __forceinline__ void pa_conv_epilogue_lds_bwd(const PaConvArgs& a, f3
     constexpr int ROWS = NT / 8;
     static_assert(!FUSE || !TAB, "fused staging: constants in registers");
     constexpr int IT = G * SW;
-    const int tid = threadIdx.x, lane = tid & 63;
+    int tid = threadIdx.x;
+    if constexpr (LEAN) asm volatile("" : "+v"(tid));      // (opaque, as in pa_conv_epilogue_lds)
+    const int lane = tid & 63;
     const int N = a.Cout;
     const int chunk = tid % CPR, rsub = tid / CPR;
     const int n = n0 + chunk * 8;
@@ -615,7 +666,7 @@ __host__ __device__ inline bool pa_bwd_epilogue_lds_ok(const PaConvArgs& a) {
 // T: >= NT * 16 floats, or (TSMALL) >= NT * 8
 // POOL: an instance for launches whose second addend is pool-routed (PaConvPlan::pool_route): 1 with the LDS form of the
 // BatchNorm-backward epilogue, 2 with plain output -- one epilogue per instance (each keeps its pixel offsets in registers across the kernel)
-template <int BN, int NI, int MI, bool BWD_LDS = true, bool TAB = false, int NT = 256, bool TSMALL = false, int POOL = 0, class PixFn>
+template <int BN, int NI, int MI, bool BWD_LDS = true, bool TAB = false, int NT = 256, bool TSMALL = false, int POOL = 0, bool LEAN = false, class PixFn>
 __device__ __forceinline__ void pa_conv_epilogue_auto(const PaConvArgs& a, f32x4 (&acc)[NI][MI], int n0, int wm, int wn,
                                                       PixFn pix, float* T, int stat_row, float4* ctab = nullptr) {
     constexpr bool FUSE = !TSMALL && !TAB && MI > 1 && MI * BN <= 128;
@@ -631,14 +682,14 @@ __device__ __forceinline__ void pa_conv_epilogue_auto(const PaConvArgs& a, f32x4
         // the networks); anything else takes the direct epilogue
         const bool lds_ok = BWD_LDS && pa_bwd_epilogue_lds_ok(a);
         if (lds_ok) {
-            pa_conv_epilogue_lds_bwd<BN, NI, MI, TAB, NT, TSMALL, FUSE>(a, acc, n0, wm, wn, pix, T, stat_row, ctab);
+            pa_conv_epilogue_lds_bwd<BN, NI, MI, (TAB || LEAN), NT, TSMALL, FUSE, false, LEAN>(a, acc, n0, wm, wn, pix, T, stat_row, ctab);
         } else if constexpr (TAB || NT != 256) {
             __builtin_trap();       // the 168-register / 512-thread kernels carry no direct epilogue: pa_conv_plan routes such launches elsewhere
         } else {
             const int p = threadIdx.x & 15;
-            pa_conv_epilogue<BN, NI, MI>(a, acc, n0, wm, wn, [&](int mi) { return pix(wm, mi, p); }, T, stat_row);
+            pa_conv_epilogue<BN, NI, MI, (LEAN && MI > PA_EPI_LEAN_MG) ? PA_EPI_LEAN_MG : MI>(a, acc, n0, wm, wn, [&](int mi) { return pix(wm, mi, p); }, T, stat_row);
         }
     } else {
-        pa_conv_epilogue_lds<BN, NI, MI, NT, TSMALL, FUSE>(a, acc, n0, wm, wn, pix, T, stat_row);
+        pa_conv_epilogue_lds<BN, NI, MI, NT, TSMALL, FUSE, false, LEAN>(a, acc, n0, wm, wn, pix, T, stat_row, ctab);
     }
 }
