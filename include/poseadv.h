@@ -389,6 +389,88 @@ int pa_adam_step_groups(const pa_adam_opts* o, const pa_opt_group* groups_host, 
 int pa_grad_norm_groups(const float* grad, size_t n, const uint8_t* chunk_map, uint32_t excluded_groups, float gscale,
                         float max_norm, void* workspace, float* out2, void* stream);
 
+/* Layer-wise trust ratios: LAMB (You et al. 2020) on Adam's moments, LARS (You, Gitman, Ginsburg 2017) on SGD with momentum, plain SGD
+ * (torch.optim.SGD), and per-tensor norms for logging.  The reference trains with RMSprop only: these calls have no reference counterpart.
+ * All of them work on a SEGMENT list instead of a chunk map: a per-tensor norm needs to know the tensor, and a net has more tensors
+ * than a byte holds.
+ *
+ * pa_opt_segments_host (host only, no device call).  Tensor t covers floats [offsets[t], offsets[t] + numels[t]); offsets are multiples
+ * of 4, ascending, non-overlapping; the gaps are zero padding.  The array is cut at every tensor start and then every
+ * PA_OPT_SEGMENT_FLOATS floats inside a tensor: segments are ascending, lie inside ONE tensor, cover no padding, a tensor's segments
+ * are contiguous in the list, and only a tensor's last segment may have nfloats % 4 != 0.  chunk0 = first float / 4; group =
+ * group_host[t] (0 .. 15).  An empty tensor has no segment.  Returns the number of segments; segs_host == NULL: count only; otherwise cap
+ * is the room in segs_host (in segments).  Returns 0 with pa_last_error set, and writes nothing, on: a NULL offsets / numels / group,
+ * ntensors < 1, an offset that is not a multiple of 4, tensors out of order or overlapping, a tensor that ends past n, a group id outside
+ * 0 .. 15, cap too small, an array past 2^34 floats.  The caller uploads the list (16-byte aligned) and owns it.
+ *
+ * Work and sums.  One wave works on one segment, four segments per 256-thread workgroup.  A per-tensor sum of squares is formed in
+ * double without atomics: one partial per segment (lanes add their elements in element order, then a fixed butterfly over the 64
+ * lanes), and a second launch adds a tensor's partials in segment order.  The order depends only on the tensor's length: the same input
+ * gives the same bits, and the same tensor gives the same norm wherever it lies.  workspace: pa_opt_layer_workspace_bytes(nsegs,
+ * ntensors) bytes on the device, 8-byte aligned (two doubles per segment).  Every value is stored by ordinary vector stores.
+ *
+ * pa_tensor_norms: norms[t] = (float)sqrt(sum over tensor t of ((double)x[i] * (double)scale)^2), ntensors floats on the device; the entry
+ * of an empty tensor is not written.  Two launches (sums, finish).  Errors: a NULL x / segs / workspace / norms, nsegs == 0,
+ * ntensors < 1, a misaligned x / segs / workspace, a scale that is not finite.
+ *
+ * Groups.  groups_host: 1 .. 16 entries {lr, weight_decay, frozen} on the HOST as for the _groups calls above; a segment's group field
+ * selects the entry; one group is group 0 everywhere (there is no ungrouped path).  A FROZEN segment is skipped before any load: nothing
+ * of param, grad or a state array is read or written there, it adds to no norm, and its tensor's norms and trust ratio stay as they were.
+ * Padding is covered by no segment and is never touched.  adapt_t = always_adapt || weight_decay of the tensor's group != 0 (the default
+ * of apex FusedLAMB and timm: tensors without decay are not adapted).
+ * norms: 2 * ntensors floats on the device, norms[t] = W_t = (float)sqrt(sum p^2) of the parameters BEFORE the step and
+ * norms[ntensors + t] = U_t (LAMB) or G_t (LARS); trust: ntensors floats, r_t, to be set to 1 once by the caller.  clip_coef: one device
+ * float (out2 + 1 of pa_grad_norm) or NULL.
+ *
+ * pa_lamb_step, per element in fp32 and in this order:
+ *   gr = (grad * gscale) * clip_coef[0]                        (no multiply without a clip pointer)
+ *   m' = m + (gr - m) * (1.f - beta1);   v' = beta2 * v + ((1.f - beta2) * gr) * gr
+ *   den = sqrtf(v') / bc2s + eps;   u = (m' / bc1) / den;   weight_decay of the group != 0:  u = u + weight_decay * param
+ *   per tensor: W = sqrt(sum param^2), U = sqrt(sum u^2), squares and sums in double;
+ *   r_t = (adapt_t && W > 0 && U > 0) ? W / U : 1;  max_trust > 0: r_t = min(r_t, max_trust)     (double, rounded once to float)
+ *   param' = param - (lr_group * r_t) * u
+ * state, bc1, bc2s and the step count t: pa_adam_step's pa_adam_state and its one-thread launch in front (step_size = lr of group 0 / bc1
+ * is written and not used).  Launches: prologue; pass 1 (m', v' and the per-segment sums of param^2 and u^2); finish (norms, trust);
+ * pass 2 (the step, u recomputed from m', v' and param: 10 floats moved per element, no scratch array).
+ * Errors (non-zero, pa_last_error set with the function's name in front, nothing launched): a NULL opts / param / grad / exp_avg /
+ * exp_avg_sq / state / segs / workspace / norms / trust / groups_host; a state or an array that is not 16-byte aligned; amsgrad != 0;
+ * beta1 or beta2 outside [0, 1); eps <= 0 or not finite; max_trust negative or not finite; an lr or weight_decay that is negative or not
+ * finite; ngroups outside 1 .. 16; ntensors < 1; nsegs == 0 with n > 0.
+ *
+ * pa_lars_step, per element in fp32 and in this order:
+ *   gr = (grad * gscale) * clip_coef[0]
+ *   per tensor: W = sqrt(sum param^2), G = sqrt(sum gr^2), gr formed and squared in double as pa_grad_norm does;
+ *   r_t = (trust_coef > 0 && adapt_t && W > 0 && G > 0) ? trust_coef * W / (G + weight_decay * W + lars_eps) : 1     (double, rounded once)
+ *   d = gr;  weight_decay != 0: d = gr + weight_decay * param;  trust_coef > 0: d = r_t * d
+ *   momentum != 0:  buf' = momentum * buf + d;  d = nesterov ? d + momentum * buf' : buf'
+ *   param' = param - lr_group * d
+ * trust_coef == 0 is torch.optim.SGD(momentum, weight_decay, nesterov, dampening = 0) from a zero momentum buffer: ONE step launch, no
+ * norm launch; workspace, norms and trust may then be NULL.  Otherwise: sums, finish, step.  state: the two device int32 of
+ * pa_rmsprop_step_state.  momentum_buf: n floats, required iff momentum != 0.
+ * Errors: a NULL opts / param / grad / state / segs / groups_host, with trust_coef > 0 a NULL workspace / norms / trust; a missing or
+ * superfluous momentum_buf; nesterov with momentum == 0; a momentum, trust_coef, lars_eps, lr or weight_decay that is negative or not
+ * finite; an array that is not 16-byte aligned; ngroups outside 1 .. 16; ntensors < 1; nsegs == 0 with n > 0.
+ *
+ * Half-precision build: the reset + finite scan of the WHOLE gradient (n floats, frozen segments and padding included) runs in front.
+ * With the flag set every later launch returns at once: param, every state array, the step count and its constants, norms and trust
+ * stay bit for bit, and the skip is counted once (pa_adam_steps / pa_rmsprop_skipped_steps_state read it).
+ * segs must be the list pa_opt_segments_host made for arrays of n floats: the kernels trust it.  n == 0: nothing is launched. */
+#define PA_OPT_SEGMENT_FLOATS 1024
+typedef struct pa_opt_segment { uint32_t chunk0, nfloats; int32_t tensor, group; } pa_opt_segment;   /* chunk0 = first float / 4 */
+typedef struct pa_lamb_opts { float beta1, beta2, eps, max_trust; int32_t always_adapt, amsgrad; } pa_lamb_opts;
+typedef struct pa_lars_opts { float momentum, trust_coef, lars_eps; int32_t nesterov, always_adapt; } pa_lars_opts;
+size_t pa_opt_segments_host(const size_t* offsets_host, const size_t* numels_host, const int32_t* group_host, int ntensors, size_t n,
+                            pa_opt_segment* segs_host, size_t cap);
+size_t pa_opt_layer_workspace_bytes(size_t nsegs, int ntensors);
+int pa_tensor_norms(const float* x, const pa_opt_segment* segs, size_t nsegs, int ntensors, float scale, void* workspace, float* norms,
+                    void* stream);
+int pa_lamb_step(const pa_lamb_opts* o, const pa_opt_group* groups_host, int ngroups, const pa_opt_segment* segs, size_t nsegs,
+                 int ntensors, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float gscale,
+                 const float* clip_coef, void* workspace, float* norms, float* trust, pa_adam_state* state, void* stream);
+int pa_lars_step(const pa_lars_opts* o, const pa_opt_group* groups_host, int ngroups, const pa_opt_segment* segs, size_t nsegs,
+                 int ntensors, float* param, const float* grad, float* momentum_buf, size_t n, float gscale, const float* clip_coef,
+                 void* workspace, float* norms, float* trust, int32_t* state, void* stream);
+
 /* Exponential moving average of the weights, updated on the device (utils.optim.ModelEma): ema += w (src - ema) after an optimizer
  * step, w = 1 - decay.  No reference counterpart: the reference validates and saves the raw weights.
  * state: 32 bytes on the device, zeroed once by the caller and owned by ONE average.  updates = averaging steps applied so far; held =

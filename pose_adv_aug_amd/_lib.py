@@ -80,6 +80,24 @@ class OptGroup(C.Structure):
     _fields_ = [('lr', _f), ('weight_decay', _f), ('frozen', C.c_int32), ('reserved', C.c_int32)]
 
 
+OPT_SEGMENT_FLOATS = 1024          # PA_OPT_SEGMENT_FLOATS of include/poseadv.h
+
+
+class OptSegment(C.Structure):
+    """pa_opt_segment of include/poseadv.h (pa_opt_segments_host fills an array of them on the host)"""
+    _fields_ = [('chunk0', C.c_uint32), ('nfloats', C.c_uint32), ('tensor', C.c_int32), ('group', C.c_int32)]
+
+
+class LambOpts(C.Structure):
+    """pa_lamb_opts of include/poseadv.h (pass C.byref of it to pa_lamb_step)"""
+    _fields_ = [('beta1', _f), ('beta2', _f), ('eps', _f), ('max_trust', _f), ('always_adapt', C.c_int32), ('amsgrad', C.c_int32)]
+
+
+class LarsOpts(C.Structure):
+    """pa_lars_opts of include/poseadv.h (pass C.byref of it to pa_lars_step)"""
+    _fields_ = [('momentum', _f), ('trust_coef', _f), ('lars_eps', _f), ('nesterov', C.c_int32), ('always_adapt', C.c_int32)]
+
+
 _PROTOS = {
     'pa_last_error': (C.c_char_p, []),
     'pa_version': (_i, []),
@@ -133,6 +151,11 @@ _PROTOS = {
     'pa_rmsprop_step_groups': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
     'pa_adam_step_groups': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp]),
     'pa_grad_norm_groups': (_i, [_vp, _sz, _vp, C.c_uint32, _f, _f, _vp, _vp, _vp]),
+    'pa_opt_segments_host': (_sz, [_vp, _vp, _vp, _i, _sz, _vp, _sz]),
+    'pa_opt_layer_workspace_bytes': (_sz, [_sz, _i]),
+    'pa_tensor_norms': (_i, [_vp, _vp, _sz, _i, _f, _vp, _vp, _vp]),
+    'pa_lamb_step': (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pa_lars_step': (_i, [_vp, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp, _sz, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pa_ema_advance': (_i, [_vp, _f, _i, _vp, _vp]),
     'pa_ema_lerp': (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
     'pa_ema_counts': (_i, [_vp, _vp, _vp, _vp]),

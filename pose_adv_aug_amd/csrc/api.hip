@@ -398,6 +398,106 @@ int pa_grad_norm_groups(const float* g, size_t n, const uint8_t* chunk_map, uint
     if (excluded && !chunk_map) { pa_set_error_msg("pa_grad_norm_groups: chunk_map is NULL with excluded groups"); return 1; }
     TRY(pa_launch_grad_norm_groups(g, n, chunk_map, excluded, gscale, max_norm, workspace, out2, ST(s))); return 0;
 }
+// Layer-wise trust ratios (opt_layerwise.hip; utils.optim.SGD / LARS / LAMB): the segment plan is host only; the device entry points check
+// every argument before the first device call, so an argument error launches nothing.
+static_assert(sizeof(pa_opt_segment) == 16 && sizeof(PaOptSegment) == 16 && PA_OPT_SEGMENT_FLOATS % 4 == 0, "pa_opt_segment is 16 bytes");
+size_t pa_opt_segments_host(const size_t* offsets, const size_t* numels, const int32_t* group, int ntensors, size_t n, pa_opt_segment* segs,
+                            size_t cap) {
+    g_err[0] = 0;
+    const std::string who = "pa_opt_segments_host";
+    if (!offsets || !numels || !group) { pa_set_error_msg((who + ": offsets, numels or group is NULL").c_str()); return 0; }
+    if (ntensors < 1) { pa_set_error_msg((who + ": ntensors must be >= 1").c_str()); return 0; }
+    size_t end = 0, count = 0;
+    for (int t = 0; t < ntensors; ++t) {                // every input error first: nothing is written on an error
+        const std::string at = who + ": tensor " + std::to_string(t);
+        if (offsets[t] & 3) { pa_set_error_msg((at + ": offset is not a multiple of 4").c_str()); return 0; }
+        if (offsets[t] < end) { pa_set_error_msg((at + ": out of order or overlapping the tensor in front of it").c_str()); return 0; }
+        if (numels[t] > n || offsets[t] > n - numels[t]) { pa_set_error_msg((at + ": ends past n").c_str()); return 0; }
+        if (group[t] < 0 || group[t] >= PA_OPT_GROUPS_MAX) { pa_set_error_msg((at + ": group id outside 0 .. 15").c_str()); return 0; }
+        if (offsets[t] / 4 + numels[t] / 4 > 0xffffffffull) { pa_set_error_msg((at + ": lies past 2^34 floats (chunk0 is 32 bits)").c_str()); return 0; }
+        end = offsets[t] + numels[t];
+        count += (numels[t] + PA_OPT_SEGMENT_FLOATS - 1) / PA_OPT_SEGMENT_FLOATS;
+    }
+    if (count == 0) { pa_set_error_msg((who + ": every tensor is empty").c_str()); return 0; }
+    if (count > 0xffffffffull) { pa_set_error_msg((who + ": more than 2^32 - 1 segments").c_str()); return 0; }
+    if (!segs) return count;
+    if (cap < count) { pa_set_error_msg((who + ": cap " + std::to_string(cap) + " is smaller than the " + std::to_string(count) + " segments").c_str()); return 0; }
+    size_t k = 0;
+    for (int t = 0; t < ntensors; ++t)
+        for (size_t done = 0; done < numels[t]; done += PA_OPT_SEGMENT_FLOATS, ++k) {
+            const size_t left = numels[t] - done;
+            segs[k].chunk0 = (uint32_t)((offsets[t] + done) / 4);
+            segs[k].nfloats = (uint32_t)(left < PA_OPT_SEGMENT_FLOATS ? left : PA_OPT_SEGMENT_FLOATS);
+            segs[k].tensor = t;
+            segs[k].group = group[t];
+        }
+    return count;
+}
+size_t pa_opt_layer_workspace_bytes(size_t nsegs, int ntensors) { return pa_opt_layer_workspace_size(nsegs, ntensors); }
+// what pa_tensor_norms, pa_lamb_step and pa_lars_step share: the segment list against n and the arrays of the two norm launches
+static bool layer_args_ok(const std::string& w, const void* segs, size_t nsegs, int ntensors, size_t n, bool need_ws, const void* workspace,
+                          const void* norms, const void* trust) {
+    if (!segs && nsegs) { pa_set_error_msg((w + ": segs is NULL").c_str()); return false; }
+    if (nsegs == 0 && n > 0) { pa_set_error_msg((w + ": nsegs is 0 with n > 0").c_str()); return false; }
+    if (nsegs > 0xffffffffull) { pa_set_error_msg((w + ": nsegs must stay below 2^32").c_str()); return false; }
+    if (ntensors < 1) { pa_set_error_msg((w + ": ntensors must be >= 1").c_str()); return false; }
+    if (reinterpret_cast<uintptr_t>(segs) & 15) { pa_set_error_msg((w + ": segs must be 16-byte aligned").c_str()); return false; }
+    if (need_ws && (!workspace || !norms || !trust)) { pa_set_error_msg((w + ": workspace, norms or trust is NULL").c_str()); return false; }
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) { pa_set_error_msg((w + ": workspace must be 8-byte aligned (double partial sums)").c_str()); return false; }
+    return true;
+}
+static bool finite_nonneg(float v) { return v >= 0.f && std::isfinite(v); }
+int pa_tensor_norms(const float* x, const pa_opt_segment* segs, size_t nsegs, int ntensors, float scale, void* workspace, float* norms, void* s) {
+    g_err[0] = 0;
+    if (!x || !segs || !workspace || !norms) { pa_set_error_msg("pa_tensor_norms: x, segs, workspace or norms is NULL"); return 1; }
+    if (nsegs == 0) { pa_set_error_msg("pa_tensor_norms: nsegs must be >= 1"); return 1; }
+    if (!layer_args_ok("pa_tensor_norms", segs, nsegs, ntensors, 1, false, workspace, norms, nullptr)) return 1;
+    if (reinterpret_cast<uintptr_t>(x) & 15) { pa_set_error_msg("pa_tensor_norms: x must be 16-byte aligned"); return 1; }
+    if (!std::isfinite(scale)) { pa_set_error_msg("pa_tensor_norms: scale must be finite"); return 1; }
+    TRY(pa_launch_tensor_norms(x, reinterpret_cast<const PaOptSegment*>(segs), nsegs, ntensors, scale, workspace, norms, ST(s))); return 0;
+}
+int pa_lamb_step(const pa_lamb_opts* o, const pa_opt_group* groups, int ngroups, const pa_opt_segment* segs, size_t nsegs, int ntensors,
+                 float* p, const float* g, float* m, float* v, size_t n, float gscale, const float* clip_coef, void* workspace, float* norms,
+                 float* trust, pa_adam_state* state, void* s) {
+    g_err[0] = 0;
+    if (!o || !p || !g || !m || !v) { pa_set_error_msg("pa_lamb_step: opts, param, grad, exp_avg or exp_avg_sq is NULL"); return 1; }
+    if (!adam_state_ok("pa_lamb_step", state)) return 1;
+    if (o->amsgrad) { pa_set_error_msg("pa_lamb_step: amsgrad is not supported with LAMB"); return 1; }
+    if (!(o->beta1 >= 0.f && o->beta1 < 1.f) || !(o->beta2 >= 0.f && o->beta2 < 1.f)) { pa_set_error_msg("pa_lamb_step: beta1 and beta2 must be in [0, 1)"); return 1; }
+    if (!(o->eps > 0.f) || !std::isfinite(o->eps)) { pa_set_error_msg("pa_lamb_step: eps must be finite and > 0"); return 1; }
+    if (!finite_nonneg(o->max_trust)) { pa_set_error_msg("pa_lamb_step: max_trust must be finite and >= 0 (0: no cap)"); return 1; }
+    if (!layer_args_ok("pa_lamb_step", segs, nsegs, ntensors, n, true, workspace, norms, trust)) return 1;
+    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) {
+        pa_set_error_msg("pa_lamb_step: param, grad, exp_avg and exp_avg_sq must be 16-byte aligned"); return 1;
+    }
+    PaOptGroupTable tab;          // (the segment list stands where the grouped steps take their chunk map: it carries the group ids)
+    if (!opt_groups_table("pa_lamb_step", groups, ngroups, reinterpret_cast<const uint8_t*>(segs ? (const void*)segs : (const void*)o), &tab)) return 1;
+    const PaLambOpts k = {o->beta1, o->beta2, o->eps, 1.f - o->beta1, 1.f - o->beta2, o->max_trust, o->always_adapt != 0};
+    TRY(pa_launch_lamb(k, tab, reinterpret_cast<const PaOptSegment*>(segs), nsegs, ntensors, p, g, m, v, n, gscale, clip_coef, workspace, norms,
+                       trust, reinterpret_cast<PaAdamState*>(state), ST(s)));
+    return 0;
+}
+int pa_lars_step(const pa_lars_opts* o, const pa_opt_group* groups, int ngroups, const pa_opt_segment* segs, size_t nsegs, int ntensors,
+                 float* p, const float* g, float* buf, size_t n, float gscale, const float* clip_coef, void* workspace, float* norms,
+                 float* trust, int32_t* state, void* s) {
+    g_err[0] = 0;
+    if (!o || !p || !g || !state) { pa_set_error_msg("pa_lars_step: opts, param, grad or state is NULL"); return 1; }
+    if (!finite_nonneg(o->momentum) || !finite_nonneg(o->trust_coef) || !finite_nonneg(o->lars_eps)) {
+        pa_set_error_msg("pa_lars_step: momentum, trust_coef and lars_eps must be finite and >= 0"); return 1;
+    }
+    if ((o->momentum != 0.f) != (buf != nullptr)) { pa_set_error_msg("pa_lars_step: momentum_buf is required when momentum != 0 and must be NULL otherwise"); return 1; }
+    if (o->nesterov && o->momentum == 0.f) { pa_set_error_msg("pa_lars_step: nesterov needs momentum != 0"); return 1; }
+    if (!layer_args_ok("pa_lars_step", segs, nsegs, ntensors, n, o->trust_coef > 0.f, workspace, norms, trust)) return 1;
+    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(buf)) & 15) {
+        pa_set_error_msg("pa_lars_step: param, grad and momentum_buf must be 16-byte aligned"); return 1;
+    }
+    PaOptGroupTable tab;
+    if (!opt_groups_table("pa_lars_step", groups, ngroups, reinterpret_cast<const uint8_t*>(segs ? (const void*)segs : (const void*)o), &tab)) return 1;
+    const PaLarsOpts k = {o->momentum, o->trust_coef, o->lars_eps, o->nesterov != 0, o->always_adapt != 0};
+    TRY(pa_launch_lars(k, tab, reinterpret_cast<const PaOptSegment*>(segs), nsegs, ntensors, p, g, buf, n, gscale, clip_coef, workspace, norms,
+                       trust, state, ST(s)));
+    return 0;
+}
 // Weight EMA (ema.hip; utils.optim.ModelEma): the update count, the hold decision and the weight w live in the caller's device state.  An
 // argument error launches nothing.
 static_assert(sizeof(pa_ema_state) == 32 && sizeof(PaEmaState) == 32, "pa_ema_state is 32 bytes");

@@ -4,7 +4,7 @@
 # (release) build reads no environment.
 set -e
 cd "$(dirname "$0")"
-SRCS="conv_igemm conv3x3_tile conv1x1_tile conv_wgrad conv_wgrad_tile stem_dgrad elementwise pose_ops soft_argmax warp_bwd ema grad_accum crop_warp jpeg net asn api"
+SRCS="conv_igemm conv3x3_tile conv1x1_tile conv_wgrad conv_wgrad_tile stem_dgrad elementwise opt_layerwise pose_ops soft_argmax warp_bwd ema grad_accum crop_warp jpeg net asn api"
 build_variant() {      # $1 = object directory, $2 = extra flags, $3 = library name
   local dir=$1 flags=$2 lib=$3
   mkdir -p $dir

@@ -162,6 +162,23 @@ int pa_launch_adam_groups(const PaAdamOpts& o, bool amsgrad, bool decoupled, con
                           const float* clip_coef, PaAdamState* state, hipStream_t st);
 int pa_launch_grad_norm_groups(const float* g, size_t n, const unsigned char* map, unsigned excluded, float gscale, float max_norm,
                                void* workspace, float* out2, hipStream_t st);
+// Layer-wise trust ratios (opt_layerwise.hip): LAMB, LARS / SGD and per-tensor norms over a SEGMENT list.  PaOptSegment is
+// pa_opt_segment of include/poseadv.h (chunk0 = first float / 4; a segment lies inside one tensor and covers no padding); one wave works
+// on one segment, PA_LW_WAVES segments per 256-thread workgroup.  workspace: two double partial sums per segment.  norms: [2][ntensors]
+// floats (W, then U or G); trust: ntensors floats.  The group table travels by value as above and is staged in LDS.
+struct PaOptSegment { unsigned chunk0, nfloats; int tensor, group; };
+constexpr int PA_LW_WAVES = 4;
+struct PaLambOpts { float beta1, beta2, eps, om_b1, om_b2, max_trust; int always_adapt; };
+struct PaLarsOpts { float mom, trust_coef, lars_eps; int nesterov, always_adapt; };
+size_t pa_opt_layer_workspace_size(size_t nsegs, int ntensors);
+int pa_launch_tensor_norms(const float* x, const PaOptSegment* segs, size_t nsegs, int ntensors, float scale, void* workspace, float* norms,
+                           hipStream_t st);
+int pa_launch_lamb(const PaLambOpts& o, const PaOptGroupTable& tab, const PaOptSegment* segs, size_t nsegs, int ntensors, float* p,
+                   const float* g, float* m, float* v, size_t n, float gscale, const float* clip_coef, void* workspace, float* norms,
+                   float* trust, PaAdamState* state, hipStream_t st);
+int pa_launch_lars(const PaLarsOpts& o, const PaOptGroupTable& tab, const PaOptSegment* segs, size_t nsegs, int ntensors, float* p,
+                   const float* g, float* buf, size_t n, float gscale, const float* clip_coef, void* workspace, float* norms, float* trust,
+                   int* state, hipStream_t st);
 int pa_launch_loss_out(float* acc, float* keep, float* out, float* total, int n, hipStream_t st);      // per-stack losses + their sum out, accumulators cleared
 int pa_launch_copy16(void* dst, const void* src, size_t bytes, hipStream_t st, int form = 0);      // plain 16-B/lane streaming copy (bandwidth calibration)
 int pa_rmsprop_skipped(const int* state, long long* out, hipStream_t st);     // half-precision build: steps skipped for a non-finite gradient

@@ -17,11 +17,20 @@ class TrainOptions(BaseOptions):
         # the optimizer itself (utils/optim.py make_optimizer; rmsprop: the reference's).  adam / adamw: torch.optim.Adam's formula,
         # --weight_decay coupled (adam) or decoupled (adamw) and passed as given, --clip_grad_norm as above; --momentum and --centered
         # are RMSprop's and refused with them
-        p.add_argument('--optimizer', type=str, default='rmsprop', choices=('rmsprop', 'adam', 'adamw'), help='optimizer of the pose net and the agent')
+        p.add_argument('--optimizer', type=str, default='rmsprop', choices=('rmsprop', 'adam', 'adamw', 'sgd', 'lars', 'lamb'),
+                       help='optimizer of the pose net and the agent')
         p.add_argument('--beta1', type=float, default=0.9, help='Adam / AdamW: decay of the first moment')
         p.add_argument('--beta2', type=float, default=0.999, help='Adam / AdamW: decay of the second moment')
         p.add_argument('--adam_eps', type=float, default=1e-8, help='Adam / AdamW: eps added to the denominator')
         p.add_argument('--amsgrad', type=int, default=0, help='1: Adam / AdamW with AMSGrad (0: off)')
+        # sgd / lars / lamb (utils/optim.py SGD, LARS, LAMB): torch.optim.SGD's formula with --momentum (required > 0 with sgd: the flag's
+        # default is RMSprop's 0, and a bare --optimizer sgd stays refused as it always was), --nesterov and --weight_decay; lars
+        # scales every tensor's step by --trust_coef ||w|| / (||g|| + wd ||w|| + 1e-8); lamb is Adam's update (--beta1 --beta2 --adam_eps)
+        # scaled per tensor by ||w|| / ||update||, capped at --max_trust.  Tensors without weight decay are not adapted unless --always_adapt
+        p.add_argument('--nesterov', type=int, default=0, choices=(0, 1), help='sgd / lars: 1 = Nesterov momentum (needs --momentum)')
+        p.add_argument('--trust_coef', type=float, default=1e-3, help='lars: trust coefficient')
+        p.add_argument('--max_trust', type=float, default=0., help='lamb: cap of the trust ratio (0: none)')
+        p.add_argument('--always_adapt', type=int, default=0, choices=(0, 1), help='lars / lamb: 1 = adapt tensors without weight decay too')
         # parameter groups (utils/optim.py make_optimizer, group_specs): all off by default, and then the optimizer has the one group it
         # always had.  --freeze and --lr_group select tensors of the POSE net by state-dict name (re.search); the agent's optimizer takes
         # --no_decay_1d only
@@ -64,8 +73,15 @@ class TrainOptions(BaseOptions):
         if not self.initialized:
             self.initialize()
         o = self.parser.parse_args(args)
-        if o.optimizer != 'rmsprop' and (o.momentum != 0 or o.centered):
+        if o.optimizer in ('adam', 'adamw') and (o.momentum != 0 or o.centered):
             self.parser.error('--momentum and --centered are RMSprop options: not with --optimizer %s' % o.optimizer)
+        if o.optimizer in ('sgd', 'lars', 'lamb') and (o.centered or o.amsgrad or (o.optimizer == 'lamb' and o.momentum != 0)):
+            self.parser.error('--centered and --amsgrad (and, for lamb, --momentum) do not go with --optimizer %s' % o.optimizer)
+        if o.optimizer == 'sgd' and o.momentum == 0:
+            self.parser.error('--optimizer sgd needs --momentum > 0 (the default 0 is that of RMSprop; gradient descent without momentum is '
+                              'utils.optim.SGD(net, lr) in code)')
+        if o.nesterov and (o.optimizer not in ('sgd', 'lars') or o.momentum == 0):
+            self.parser.error('--nesterov needs --optimizer sgd or lars and --momentum > 0')
         if o.coord_loss < 0 or not o.coord_beta > 0:
             self.parser.error('--coord_loss must be >= 0 and --coord_beta > 0')
         if not 0 <= o.ema_decay < 1:

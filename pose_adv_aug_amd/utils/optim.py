@@ -9,6 +9,9 @@ every one of them off, step() is the one pa_rmsprop_step_state call it has alway
 Adam / AdamW (torch.optim.Adam's formula with weight decay coupled or decoupled, AMSGrad, the same clipping): one fused step
 (pa_adam_step) whose step count and bias-correction constants live on the device.  make_optimizer picks one from the command line.
 
+SGD / LARS / LAMB: torch.optim.SGD (momentum, Nesterov), and the two optimizers for large batches that scale every tensor's step by
+||w|| / ||update|| on the device (pa_lars_step, pa_lamb_step: a segmented per-tensor reduction, no host synchronisation).
+
 ModelEma: an exponential moving average of the weights in a twin net, updated on the device behind the step (pa_ema_advance, pa_ema_lerp);
 its update count and the decision to hold on a skipped step live on the device, next to the optimizer's flag.  make_ema: from the command line.
 
@@ -261,6 +264,46 @@ class _FlatOptimizer(object):
     def _frozen_params(self):
         """indices (parameters() order) of the parameters in a frozen group"""
         return set(i for g in self.param_groups if g.get('frozen', False) for i in g.get('params', ()))
+
+    # ---- per-tensor work (SGD / LARS / LAMB)
+    def _init_segments(self):
+        """The segment list of the flat parameter array (pa_opt_segments_host on the net's table, with the group of every tensor), built
+        and uploaded here, once; the workspace of the per-tensor sums, the norms [2][ntensors] and the trust ratios (1 until a step
+        writes them), in _params() order."""
+        params = self._params()
+        nt, n = len(params), self.net.flat_params.numel()
+        owner = [0] * nt
+        for k, g in enumerate(self.param_groups):
+            for i in g.get('params', ()):
+                owner[i] = k
+        offsets = (C.c_size_t * nt)(*[t[2] for t in params])
+        numels = (C.c_size_t * nt)(*[t[3] for t in params])
+        group = (C.c_int32 * nt)(*owner)
+        count = int(lib().pa_opt_segments_host(offsets, numels, group, nt, n, None, 0))
+        if count == 0:
+            check(1, 'pa_opt_segments_host')
+        host = (_lib.OptSegment * count)()
+        if int(lib().pa_opt_segments_host(offsets, numels, group, nt, n, host, count)) != count:
+            check(1, 'pa_opt_segments_host')
+        dev = self.net.flat_params.device
+        self._segs = torch.frombuffer(host, dtype=torch.int32).clone().to(dev)
+        self._nsegs, self._ntensors = count, nt
+        self._layer_ws = torch.empty(int(lib().pa_opt_layer_workspace_bytes(count, nt)) // 8, dtype=torch.float64, device=dev)
+        self._norms = torch.zeros(2 * nt, dtype=torch.float32, device=dev)
+        self._trust = torch.ones(nt, dtype=torch.float32, device=dev)
+        self._trusted = False
+
+    def last_trust(self):
+        """The trust ratio r_t of every parameter at the last step, in _params() order (1 for a tensor that is not adapted, the value
+        of the last step taken for a frozen one): a device tensor, so reading it is the caller's synchronisation.  None before the
+        first step, and for SGD without trust."""
+        return self._trust if getattr(self, '_trusted', False) else None
+
+    def tensor_norms(self):
+        """(||w||, ||update|| or ||gradient||) per parameter at the last step, the weights BEFORE it: two device tensors of one float
+        per parameter, in _params() order.  None when last_trust() is."""
+        nt = self._ntensors
+        return (self._norms[:nt], self._norms[nt:]) if getattr(self, '_trusted', False) else None
 
     def describe_groups(self):
         """one line per parameter group for the log: tensors, floats, lr, weight_decay, frozen"""
@@ -664,6 +707,190 @@ class AdamW(Adam):
                       max_grad_norm=max_grad_norm, overlap=overlap, groups=groups)
 
 
+_SGD_KEYS = ('lr', 'momentum', 'weight_decay', 'nesterov', 'trust_coefficient', 'lars_eps', 'always_adapt')
+# what torch.optim.SGD's step reads from a loaded param group beside this class's keys
+_TORCH_SGD_EXTRA = {'dampening': 0, 'maximize': False, 'foreach': None, 'differentiable': False, 'fused': None}
+
+
+class SGD(_FlatOptimizer):
+    def __init__(self, net, lr, momentum=0, weight_decay=0, nesterov=False, max_grad_norm=None, overlap=False, groups=None,
+                 trust_coefficient=0.0, eps=1e-8, always_adapt=False):
+        """torch.optim.SGD(momentum, weight_decay, nesterov, dampening=0) as ONE launch on the flat arrays (pa_lars_step with
+        trust_coefficient 0): d = g + weight_decay p; buf = momentum buf + d; d = nesterov ? d + momentum buf : buf; p -= lr d.
+        momentum, nesterov (and LARS's trust_coefficient, lars_eps, always_adapt) live in param_groups[0] and are read at every step;
+        lr, weight_decay and frozen are per group.  max_grad_norm, overlap, groups, accumulate(): as for RMSprop.  momentum_buffer is
+        allocated when momentum is first non-zero (zeros, which gives torch's first step buf = d)."""
+        if not momentum >= 0 or not weight_decay >= 0 or not float(lr) >= 0:
+            raise ValueError('lr, momentum and weight_decay must be >= 0')
+        if nesterov and momentum == 0:
+            raise ValueError('nesterov needs momentum > 0')
+        if not trust_coefficient >= 0 or not eps >= 0:
+            raise ValueError('trust_coefficient and eps must be >= 0')
+        self._attach(net, max_grad_norm, overlap)
+        self._init_groups({'lr': lr, 'momentum': momentum, 'weight_decay': weight_decay, 'nesterov': bool(nesterov),
+                           'trust_coefficient': trust_coefficient, 'lars_eps': eps, 'always_adapt': bool(always_adapt)}, groups)
+        self._init_segments()
+        self.momentum_buffer = None
+        self._ensure_state(self.param_groups[0])
+        self._skip_state = torch.zeros(2, dtype=torch.int32, device=net.flat_params.device)
+        self.steps = 0
+
+    def _ensure_state(self, g):
+        if g.get('momentum', 0) != 0 and self.momentum_buffer is None:
+            self.momentum_buffer = torch.zeros_like(self.net.flat_params)
+
+    def step(self):
+        g = self.param_groups[0]
+        gscale = self._exchanged_gscale()
+        n = self.net.flat_params.numel()
+        mom, tc = float(g.get('momentum', 0)), float(g.get('trust_coefficient', 0))
+        if g.get('nesterov', False) and mom == 0:
+            raise ValueError('nesterov needs momentum > 0')
+        self._ensure_state(g)
+        tab, ngroups, frozen = self._group_table()
+        coef = self._clip_coef(n, gscale, frozen)
+        o = _lib.LarsOpts(mom, tc, float(g.get('lars_eps', 0)), int(bool(g.get('nesterov', False))), int(bool(g.get('always_adapt', False))))
+        trust = tc > 0
+        check(lib().pa_lars_step(C.byref(o), tab, ngroups, ptr(self._segs), self._nsegs, self._ntensors, ptr(self.net.flat_params),
+                                 ptr(self.net.flat_grads), ptr(self.momentum_buffer) if mom != 0 else None, n, float(gscale), coef,
+                                 ptr(self._layer_ws) if trust else None, ptr(self._norms) if trust else None,
+                                 ptr(self._trust) if trust else None, ptr(self._skip_state), stream()), 'pa_lars_step')
+        self._trusted = trust
+        self.steps += 1
+        self._weights_stepped()
+
+    skip_flag_ptr = RMSprop.skip_flag_ptr
+    skipped_steps = RMSprop.skipped_steps
+
+    # torch.optim.SGD's format: state[i] = {'momentum_buffer': tensor} in parameters() order, empty without momentum
+    def state_dict(self):
+        self._warn_pending()
+        state = {}
+        if self.param_groups[0].get('momentum', 0) != 0:
+            self._ensure_state(self.param_groups[0])
+            for i, (name, shape, off, numel, kind) in enumerate(self._params()):
+                state[i] = {'momentum_buffer': self.momentum_buffer[off:off + numel].view(shape).clone()}
+        groups = self._state_groups()
+        for pg in groups:
+            for k, v in _TORCH_SGD_EXTRA.items():
+                pg.setdefault(k, v)
+        return {'state': state, 'param_groups': groups}
+
+    def load_state_dict(self, sd):
+        """Accepts this class's own files and torch.optim.SGD's.  momentum_buffer is replaced: an entry that is missing or has another
+        size is reported and left at zero.  The file of another optimizer (square_avg or exp_avg and no momentum_buffer) loads with ONE
+        warning that says so and leaves this optimizer's options and a zero momentum buffer."""
+        import warnings
+        params = self._params()
+        state = sd.get('state', {})
+        entries = [st for st in state.values() if isinstance(st, dict) and st]
+        if entries and not any('momentum_buffer' in st for st in entries):
+            other = sorted(set(k for st in entries for k in st) - set(['step']))
+            warnings.warn('optimizer state holds %s and no momentum_buffer: not an SGD file (another optimizer wrote it); the momentum '
+                          'buffer starts at zero and this optimizer keeps its own options' % (', '.join(other) or 'no buffers'))
+            if self.momentum_buffer is not None:
+                self.momentum_buffer.zero_()
+            return
+        group = dict(self.param_groups[0])
+        group.update((k, v) for k, v in sd['param_groups'][0].items() if k in _SGD_KEYS)
+        self._ensure_state(group)
+        if self.momentum_buffer is not None:
+            self.momentum_buffer.zero_()
+        keys, matched = self._file_keys(sd)
+        if keys is None:
+            warnings.warn('optimizer state has %d parameters, the network %d: momentum_buffer not loaded'
+                          % (sum(len(fg.get('params', [])) for fg in sd['param_groups']), len(params)))
+            keys = []
+        loaded, frozen = 0, self._frozen_params()
+        if group.get('momentum', 0) != 0:
+            for i, (key, (name, shape, off, numel, kind)) in enumerate(zip(keys, params)):
+                e = (state.get(key) or {}).get('momentum_buffer')
+                if e is None:
+                    loaded += i in frozen               # (torch keeps no state for a parameter it never stepped)
+                    continue
+                e = torch.as_tensor(e)
+                if e.numel() != numel:
+                    warnings.warn('optimizer state of %s: momentum_buffer has %d elements, expected %d: skipped' % (name, e.numel(), numel))
+                    continue
+                self.momentum_buffer[off:off + numel] = e.reshape(-1).to(self.momentum_buffer.device, torch.float32)
+                loaded += 1
+            if state and keys and loaded < len(params):
+                warnings.warn('optimizer state: %d of %d parameters had no momentum_buffer entry (left at zero)' % (len(params) - loaded, len(params)))
+        if not self._grouped() and len(sd['param_groups']) == 1:
+            self.param_groups[0].update(group)
+        else:
+            self._load_groups(sd, matched, tuple(k for k in _SGD_KEYS if k not in ('lr', 'weight_decay')))
+
+
+class LARS(SGD):
+    def __init__(self, net, lr, momentum=0.9, weight_decay=0, nesterov=False, trust_coefficient=1e-3, eps=1e-8, always_adapt=False,
+                 max_grad_norm=None, overlap=False, groups=None):
+        """LARS (You, Gitman, Ginsburg 2017) on SGD with momentum: every tensor's d = g + weight_decay p is multiplied by
+        r_t = trust_coefficient ||w|| / (||g|| + weight_decay ||w|| + eps) before the momentum, with the norms taken per tensor on the
+        device (two more launches in front of the step; squares and sums in double, no atomics).  r_t = 1 for an all-zero tensor, a zero
+        gradient and -- unless always_adapt -- a tensor whose group has no weight decay (BatchNorm and biases under --no_decay_1d).
+        last_trust() / tensor_norms(): the ratios and norms of the last step, on the device, for logging."""
+        SGD.__init__(self, net, lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov, max_grad_norm=max_grad_norm,
+                     overlap=overlap, groups=groups, trust_coefficient=trust_coefficient, eps=eps, always_adapt=always_adapt)
+
+
+_LAMB_KEYS = ('max_trust', 'always_adapt')
+
+
+class LAMB(Adam):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, max_trust=0, always_adapt=False, max_grad_norm=None,
+                 overlap=False, groups=None):
+        """LAMB (You et al. 2020): Adam's moments, u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + weight_decay p, and per tensor
+        p -= lr r_t u with r_t = ||w|| / ||u|| (1 where either norm is 0, and -- unless always_adapt, the default of apex FusedLAMB and
+        timm -- for a tensor whose group has no weight decay), capped at max_trust when that is > 0.  pa_lamb_step: prologue, a pass
+        that updates the moments and sums ||w||^2 and ||u||^2 per tensor, the ratios, a pass that applies the step.  The state is
+        Adam's (exp_avg, exp_avg_sq, the step count on the device): state_dict() has Adam's keys, and a file goes both ways.  amsgrad is
+        not supported.  last_trust() / tensor_norms(): as for LARS."""
+        b1, b2 = betas
+        if not (0 <= b1 < 1 and 0 <= b2 < 1):
+            raise ValueError('betas must be in [0, 1)')
+        if not eps > 0 or weight_decay < 0 or not max_trust >= 0:
+            raise ValueError('eps must be > 0, weight_decay and max_trust >= 0')
+        self._attach(net, max_grad_norm, overlap)
+        self._init_groups({'lr': lr, 'betas': (b1, b2), 'eps': eps, 'weight_decay': weight_decay, 'amsgrad': False, 'max_trust': max_trust,
+                           'always_adapt': bool(always_adapt)}, groups)
+        self._init_segments()
+        self.exp_avg = torch.zeros_like(net.flat_params)
+        self.exp_avg_sq = torch.zeros_like(net.flat_params)
+        self.max_exp_avg_sq = None
+        self._state = torch.zeros(8, dtype=torch.int32, device=net.flat_params.device)
+
+    def _ensure_state(self, g):
+        if g.get('amsgrad', False):
+            raise ValueError('LAMB: amsgrad is not supported')
+
+    def step(self):
+        g = self.param_groups[0]
+        self._ensure_state(g)
+        gscale = self._exchanged_gscale()
+        n = self.net.flat_params.numel()
+        b1, b2 = g['betas']
+        tab, ngroups, frozen = self._group_table()
+        coef = self._clip_coef(n, gscale, frozen)
+        o = _lib.LambOpts(float(b1), float(b2), float(g['eps']), float(g.get('max_trust', 0)), int(bool(g.get('always_adapt', False))), 0)
+        check(lib().pa_lamb_step(C.byref(o), tab, ngroups, ptr(self._segs), self._nsegs, self._ntensors, ptr(self.net.flat_params),
+                                 ptr(self.net.flat_grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), n, float(gscale), coef, ptr(self._layer_ws),
+                                 ptr(self._norms), ptr(self._trust), ptr(self._state), stream()), 'pa_lamb_step')
+        self._trusted = True
+        self._weights_stepped()
+
+    def load_state_dict(self, sd):
+        """Adam.load_state_dict (an Adam / AdamW file loads: its moments and step count; max_exp_avg_sq and the decay mode are not
+        LAMB's and are dropped); max_trust and always_adapt come from a LAMB file's group 0."""
+        fgs = [dict((k, v) for k, v in fg.items() if k != 'decoupled_weight_decay') for fg in sd['param_groups']]
+        for fg in fgs:
+            fg['amsgrad'] = False
+        Adam.load_state_dict(self, dict(sd, param_groups=fgs))
+        for g in self.param_groups:
+            g.pop('decoupled_weight_decay', None)
+            g.update((k, fgs[0][k]) for k in _LAMB_KEYS if k in fgs[0])
+
+
 class ModelEma(object):
     def __init__(self, net, decay=0.999, warmup=False, buffers='ema'):
         """Exponential moving average of the weights of `net` (any _HipModule: the pose net or an agent), kept on the device:
@@ -762,14 +989,35 @@ def accum_plan(n_batches, accum_steps):
 
 
 def make_optimizer(opt, net, lr, overlap=False):
-    """The optimizer the command line asks for (options/train_options.py: --optimizer rmsprop | adam | adamw).  rmsprop, the default:
+    """The optimizer the command line asks for (options/train_options.py: --optimizer rmsprop | adam | adamw | sgd | lars | lamb).  rmsprop, the default:
     the reference's recipe (alpha 0.99, eps 1e-8) with optim_options(opt).  adam / adamw: --beta1 --beta2 --adam_eps --amsgrad;
     --weight_decay (coupled for adam, decoupled for adamw; passed as given, so 0 means none for adamw too) and --clip_grad_norm are
-    shared between the kinds."""
+    shared between the kinds.  sgd / lars: --momentum (sgd: required > 0) --nesterov (lars: --trust_coef --always_adapt); lamb: --beta1 --beta2 --adam_eps
+    --max_trust --always_adapt; --centered, --amsgrad and --nesterov without momentum are refused with them."""
     kind = getattr(opt, 'optimizer', 'rmsprop')
     groups = group_specs(opt, net)
     if kind == 'rmsprop':
         return RMSprop(net, lr=lr, alpha=0.99, eps=1e-8, overlap=overlap, groups=groups, **optim_options(opt))
+    clip = float(getattr(opt, 'clip_grad_norm', 0) or 0)
+    if kind in ('sgd', 'lars', 'lamb'):
+        mom, nesterov = float(getattr(opt, 'momentum', 0) or 0), bool(getattr(opt, 'nesterov', 0))
+        if getattr(opt, 'centered', 0) or getattr(opt, 'amsgrad', 0):
+            raise ValueError('--centered and --amsgrad are RMSprop / Adam options: not with --optimizer %s' % kind)
+        if kind == 'sgd' and mom == 0:
+            raise ValueError('--optimizer sgd needs --momentum > 0 (gradient descent without momentum: utils.optim.SGD(net, lr) in code)')
+        if nesterov and (kind == 'lamb' or mom == 0):
+            raise ValueError('--nesterov needs --optimizer sgd or lars and --momentum > 0')
+        kw = dict(lr=lr, weight_decay=float(getattr(opt, 'weight_decay', 0) or 0), max_grad_norm=clip if clip > 0 else None, overlap=overlap,
+                  groups=groups)
+        always = bool(getattr(opt, 'always_adapt', 0))
+        if kind == 'lamb':
+            if mom != 0:
+                raise ValueError('--momentum is an RMSprop / SGD option: not with --optimizer lamb')
+            return LAMB(net, betas=(float(getattr(opt, 'beta1', 0.9)), float(getattr(opt, 'beta2', 0.999))), eps=float(getattr(opt, 'adam_eps', 1e-8)),
+                        max_trust=float(getattr(opt, 'max_trust', 0) or 0), always_adapt=always, **kw)
+        if kind == 'lars':
+            return LARS(net, momentum=mom, nesterov=nesterov, trust_coefficient=float(getattr(opt, 'trust_coef', 1e-3)), always_adapt=always, **kw)
+        return SGD(net, momentum=mom, nesterov=nesterov, **kw)
     if kind not in ('adam', 'adamw'):
         raise ValueError('unknown optimizer %r' % (kind,))
     if float(getattr(opt, 'momentum', 0) or 0) != 0 or getattr(opt, 'centered', 0):
